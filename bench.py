@@ -6,11 +6,18 @@ One "step" = one pass of the hot path over one batch of synthetic class labels:
 (and, with more than one rank, the all_gather of codes / counts / p-values: SURVEY 8e's one exchange step).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full --dump-outputs bench_out/outputs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Weights are seeded random-init tensors of the real architecture (no checkpoints offline);
 inputs are resident in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the headline line.  --full adds, after the timed region, the per-role
+kernel timings and rooflines, the stage split, parity on the golden fixtures, the CPU baseline and the secondary configurations
+(each leg can still be dropped with its --no-* option).  --dump-outputs DIR writes what the last timed step returned to rank 0
+(codes, images, re-encoded codes, p-values, detector counts) as DIR/<name>.npy in float32 / float64; with the same arguments
+the inputs are identical from run to run.
 
 Test hook (tests/test_bench_distributed_cpu.py): WMAR_BENCH_BACKEND=gloo + WMAR_BENCH_ENGINE="module:factory" run the SAME
 control flow (process group, key broadcast, barriers, max-over-ranks timing, gather, JSON line) on CPU with a stand-in engine;
@@ -35,6 +42,7 @@ PEAK_F32_MFMA_TF = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_BF16_MFMA_TF = 2500.0     # dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E spec
 METRIC = "watermarked images/sec at 256x256 (16x16 tok), batch 64; detector p-value delta vs ref"
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
 
 
 def usable_cores() -> int:
@@ -455,15 +463,34 @@ def gpu_analysis(model, wm, extra, cond, args, world, log):
     return out
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: the arrays as d/<name>.npy, float32 kept, everything else (int64 codes, int32 counts, f64 p-values)
+    as float64, which holds every value exactly.  The timed step's outputs are ~51 MB at batch 64 (the images: 50.3 MB)."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region: per-role timings, rooflines, parity, CPU baseline and secondary configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity block")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the RAR-XL / Chameleon-7B numbers (after the timed region)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the RAR-XL / Chameleon-7B / small-batch numbers")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -519,15 +546,16 @@ def main():
         dist.all_gather(outs, t.contiguous())
         return torch.cat(outs)
 
-    def step():
+    def step(keep_images=False):
         codes = model.sample(cond, GEN, apply_watermark=True)
         imgs = model.codes_to_images(codes)
         codes2 = model.images_to_codes(imgs)
         pv, ns, ng = wm.detect_counts(codes2)
+        imgs = imgs if keep_images else None      # held only after the last timed step: the steps reuse one cached buffer
         if world > 1:      # the path's one exchange step: codes int64[64,256], counts int32[64], p-values f64[64] per rank
             codes2_all, ns_all, ng_all, pv_all = gather(codes2), gather(ns), gather(ng), gather(pv)
-            return (pv_all, ns_all, ng_all), codes, codes2, codes2_all
-        return (pv, ns, ng), codes, codes2, codes2
+            return (pv_all, ns_all, ng_all), codes, imgs, codes2, codes2_all
+        return (pv, ns, ng), codes, imgs, codes2, codes2
 
     for _ in range(args.warmup):
         step()
@@ -536,8 +564,8 @@ def main():
         dist.barrier()
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        (pv, ns, ng), codes, codes2, codes2_all = step()
+    for i in range(args.steps):
+        (pv, ns, ng), codes, imgs, codes2, codes2_all = step(keep_images=i == args.steps - 1)
     sync()
     if world > 1:
         dist.barrier()
@@ -549,6 +577,9 @@ def main():
         dt = float(tt.item())
     value = world * B * args.steps / dt
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"codes": codes, "images": imgs, "codes_reencoded": codes2_all, "pvalues": pv,
+                                         "n_scored": ns, "n_green": ng})
     if rank == 0:
         S = codes.shape[1]
         out = {
@@ -565,7 +596,7 @@ def main():
             "detector": {"n_scored_mean": float(ns.float().mean()), "n_green_mean": float(ng.float().mean()),
                          "token_match_after_roundtrip": float((codes == codes2).float().mean())},
         }
-        if on_gpu and factory is default_engine:
+        if args.full and on_gpu and factory is default_engine:
             out.update(gpu_analysis(model, wm, extra, cond, args, world, log))
             out["end_to_end_frac_of_roofline"] = round(value / world / out["end_to_end_roofline"]["images_per_s"], 3)
             out["parity"] = None if args.no_parity else parity_block(log)

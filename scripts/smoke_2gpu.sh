@@ -7,4 +7,4 @@ N=${1:-2}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29511 \
-    bench.py --gpus "$N" --steps 1 --warmup 1 --no-cpu-baseline --no-parity
+    bench.py --gpus "$N" --steps 1 --warmup 1 --full --no-cpu-baseline --no-parity

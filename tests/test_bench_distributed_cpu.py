@@ -39,6 +39,32 @@ def test_bench_two_ranks_gloo():
     assert out["config"]["backend"] == "gloo"
 
 
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 / float64 .npy files; the same arguments give the same
+    inputs, so two runs of the (seeded) stand-in engine dump identical arrays."""
+    import numpy as np
+    env = dict(os.environ, WMAR_BENCH_BACKEND="gloo", WMAR_BENCH_ENGINE="tests.bench_stub:make", PYTHONPATH=REPO)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == ["codes", "codes_reencoded", "images", "n_green", "n_scored", "pvalues"]
+    assert a["codes"].shape == (64, 256) and a["images"].shape == (64, 3, 16, 16) and a["pvalues"].shape == (64,)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_refuses_to_run_the_product_path_without_a_gpu():
     import torch
     if torch.cuda.is_available():
