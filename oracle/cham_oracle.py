@@ -120,6 +120,52 @@ def forward_tokens(sd: Dict[str, T], cfg, tok: T, pos: T, cache: Cache, fold: bo
     return _norm_linear(x, sd["norm.weight"], sd["output.weight"], cfg.norm_eps, fold)
 
 
+def prefix(sd: Dict[str, T], cfg, seq: T, positions=None, fold: bool = False) -> T:
+    """Transformer.forward_with_attn_bias on whole sequences at once (transformer.py:316-337 with q_seqlen = T; the causal mask of
+    memory_efficient_attention_forward, :151-155): the logits `forward_tokens` produces when fed seq[:, t] at position t for
+    t = 0..T-1, with the same bf16 rounding points (both `fold` modes), in ONE causally masked pass per layer over all rows*T tokens.
+    What makes long caches and the 7B width checkable in seconds on a CPU (the incremental form re-converts every weight per step).
+
+    seq int64 [R, T] -> fp32 logits [R, len(positions), V]; the output head runs at the requested positions only (all when None)."""
+    R, Tn = seq.shape
+    H, Hkv, hd = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+    N = R * Tn
+    pos = torch.arange(Tn).repeat(R)                                   # rope_padded's per-token positions (row-major tokens)
+    causal = torch.ones(Tn, Tn, dtype=torch.bool).tril()
+    x = sd["tok_embeddings.weight"][seq.reshape(-1)].float()
+    for l in range(cfg.n_layers):
+        p = f"layers.{l}."
+        qkv = _norm_linear(x, sd[p + "attention_norm.weight"], sd[p + "attention.wqkv.weight"], cfg.norm_eps, fold)   # :112-115
+        q = qkv[:, : H * hd].view(N, H, hd)
+        k, v = qkv[:, H * hd:].chunk(2, 1)
+        k, v = k.reshape(N, Hkv, hd), v.reshape(N, Hkv, hd)
+        if cfg.qk_normalization:                                                                                         # :117-124
+            q = bf(F.layer_norm(q, (hd,), sd[p + "attention.q_normalization.weight"].float(),
+                                sd[p + "attention.q_normalization.bias"].float(), 1e-5))
+            k = bf(F.layer_norm(k, (hd,), sd[p + "attention.k_normalization.weight"].float(),
+                                sd[p + "attention.k_normalization.bias"].float(), 1e-5))
+        q, k = _rope(q, pos, cfg.rope_theta), _rope(k, pos, cfg.rope_theta)                                              # :132-140
+        q = q.view(R, Tn, H, hd).transpose(1, 2)                                                      # [R, H, T, hd]
+        k = k.view(R, Tn, Hkv, hd).repeat_interleave(H // Hkv, dim=2).transpose(1, 2)                  # GQA, :142-149: kv head h // (H / Hkv)
+        v = v.view(R, Tn, Hkv, hd).repeat_interleave(H // Hkv, dim=2).transpose(1, 2)
+        s = (q @ k.transpose(-1, -2)) / hd ** 0.5                                                     # :153-155, fp32 accumulation
+        s = s.masked_fill(~causal, float("-inf"))
+        out = (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(N, H * hd)
+        del q, k, v, s
+        attn = _linear(bf(out), sd[p + "attention.wo.weight"])                                                           # :157
+        h = bf(x + attn)                                                                                                 # :278-283
+        x13 = _norm_linear(h, sd[p + "ffn_norm.weight"], sd[p + "feed_forward.w13.weight"], cfg.norm_eps, fold)          # :216-218
+        x1, x3 = x13.chunk(2, -1)
+        ff = _linear(bf(bf(F.silu(x1)) * x3), sd[p + "feed_forward.w2.weight"])
+        x = bf(h + ff)                                                                                                   # :284
+    x = x.view(R, Tn, -1)
+    if positions is not None:
+        x = x[:, list(positions)]
+    P = x.shape[1]
+    lg = _norm_linear(x.reshape(R * P, -1), sd["norm.weight"], sd["output.weight"], cfg.norm_eps, fold)                  # :332
+    return lg.view(R, P, -1)
+
+
 def prefill_right_aligned(sd, cfg, prompts: List[List[int]], cache: Cache, fold: bool = False) -> Tuple[T, T]:
     """Feed right-aligned prompts one position at a time (what the engine does; equivalent to the reference's ragged
     first pass, model_adapter.py:76-100).  Returns (logits of each row's last prompt token [M, V], next positions [M])."""

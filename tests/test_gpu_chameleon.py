@@ -106,6 +106,34 @@ def test_cham_sample_reference_tokens(cv, name, seed, compact):
     assert np.array_equal(out.cpu().numpy(), cv[f"cham_{name}_tok"])
 
 
+def replay_oracle_chain(m, wm, cfg, sd, cond, q, codes, h, n_tokens):
+    """Every token of `codes` (the captured loop's output) equals the oracle's sampling chain applied to the logits of a second
+    engine fed the same prompts and the same tokens, step by step."""
+    from wmar_amd.models.engine import ChameleonEngine
+    from oracle import wm_oracle as W
+    e2 = ChameleonEngine(cfg, sd, max_batch=3, max_seq_len=16 + n_tokens)
+    prompts = m.split_inputs_for_cfg([m.tokens_from_ui([{"type": "ids", "value": p}, {"type": "sentinel", "value": "<END-OF-TURN>"}])
+                                      for _, p in cond])
+    M, maxlen = len(prompts), max(len(p) for p in prompts)
+    lg = None
+    for j in range(maxlen):
+        tok = [p[j - (maxlen - len(p))] if j - (maxlen - len(p)) >= 0 else 0 for p in prompts]
+        pos = [max(j - (maxlen - len(p)), 0) for p in prompts]
+        lg = e2.forward_tokens(torch.tensor(tok).cuda(), torch.tensor(pos, dtype=torch.int32).cuda())
+    key = W.KeyParams(wm._alive_host, wm._dead_host, cfg.vocab_size, 0.25, seed="linear", context_size=h)
+    padded = [[m.vocab.pad_id] * (maxlen - len(p)) + list(p) for p in prompts[:3]]        # AlignPromptRight, alignment.py:27-41
+    past = np.array(padded, dtype=np.int64)
+    pos = torch.tensor([len(p) for p in prompts], dtype=torch.int32)
+    for n in range(n_tokens):
+        tok, _ = CO.sample_step(lg.cpu(), q[n].cpu().numpy(), 0.9, 0.8, 3.0, 1.2, allow_ids=m.vocab.image_tokens, key=key, past_ids=past,
+                                delta=3.0)
+        assert np.array_equal(tok, codes[:, n].cpu().numpy()), n
+        past = np.concatenate([past, tok[:, None]], axis=1)
+        if n < n_tokens - 1:
+            t3 = torch.from_numpy(np.concatenate([tok, tok, tok]))
+            lg = e2.forward_tokens(t3.cuda(), (pos + n).cuda())
+
+
 @pytest.mark.parametrize("graph,h", [(True, 1), (False, 1), (True, 2), (True, 3)])
 def test_generate_image_loop(graph, h):
     """The captured generation loop: every sampled token equals the oracle's sampling chain applied to the engine's own
@@ -114,7 +142,6 @@ def test_generate_image_loop(graph, h):
     is the last two prompt tokens, and a prompt shorter than the context would reach into the padding."""
     from wmar_amd.models.chameleon_wrapper import ChameleonARMMWrapper
     from wmar_amd.watermarking.gentime_watermark import GentimeWatermark, SeedStrategy, SplitStrategy
-    from oracle import wm_oracle as W
     cfg = _cfg(hd=64, dim=256, vocab=2048)
     vq_cfg = synth.VQConfig(ch=32, ch_mult=(1, 2), num_res_blocks=1, attn_resolutions=(), resolution=16, z_channels=32, embed_dim=32,
                             n_embed=512)
@@ -132,29 +159,7 @@ def test_generate_image_loop(graph, h):
     q = m.draw_noise(3)
     codes = m.sample(cond, {"temperature": 0.9, "top_p": 0.8}, apply_watermark=True, q=q)
     assert set(codes.flatten().tolist()) <= set(m.vocab.image_tokens)
-    # replay on a second engine, step by step
-    from wmar_amd.models.engine import ChameleonEngine
-    e2 = ChameleonEngine(cfg, sd, max_batch=3, max_seq_len=16 + 64)
-    prompts = m.split_inputs_for_cfg([m.tokens_from_ui([{"type": "ids", "value": p}, {"type": "sentinel", "value": "<END-OF-TURN>"}])
-                                      for _, p in cond])
-    M, maxlen = len(prompts), max(len(p) for p in prompts)
-    lg = None
-    for j in range(maxlen):
-        tok = [p[j - (maxlen - len(p))] if j - (maxlen - len(p)) >= 0 else 0 for p in prompts]
-        pos = [max(j - (maxlen - len(p)), 0) for p in prompts]
-        lg = e2.forward_tokens(torch.tensor(tok).cuda(), torch.tensor(pos, dtype=torch.int32).cuda())
-    key = W.KeyParams(wm._alive_host, wm._dead_host, 2048, 0.25, seed="linear", context_size=h)
-    padded = [[m.vocab.pad_id] * (maxlen - len(p)) + list(p) for p in prompts[:3]]        # AlignPromptRight, alignment.py:27-41
-    past = np.array(padded, dtype=np.int64)
-    pos = torch.tensor([len(p) for p in prompts], dtype=torch.int32)
-    for n in range(64):
-        tok, _ = CO.sample_step(lg.cpu(), q[n].cpu().numpy(), 0.9, 0.8, 3.0, 1.2, allow_ids=m.vocab.image_tokens, key=key, past_ids=past,
-                                delta=3.0)
-        assert np.array_equal(tok, codes[:, n].cpu().numpy()), n
-        past = np.concatenate([past, tok[:, None]], axis=1)
-        if n < 63:
-            t3 = torch.from_numpy(np.concatenate([tok, tok, tok]))
-            lg = e2.forward_tokens(t3.cuda(), (pos + n).cuda())
+    replay_oracle_chain(m, wm, cfg, sd, cond, q, codes, h, 64)
     # decode -> re-encode -> detect through the wrapper
     imgs = m.codes_to_images(codes)
     assert imgs.shape == (3, 3, 16, 16)
