@@ -402,9 +402,19 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
  * noise_dev = standard normal draws of the image shape), 3 brightness (p0 = factor), 4 rotation (p0 = counter-clockwise quarter turns,
  * p1 = remainder in degrees, [0, 90)), 5 horizontal flip, 6 upper-left crop of p0 x p1 pixels resized back (antialiased bilinear),
  * 7 the same crop padded back with zeros.  pm1 != 0: pixels cross this call in [-1, 1] (the decoder's range) and are transformed in
- * [0, 1] and clamped, as generate.py:146-150 does around every transform.  JPEG stays on the host (PIL), as in the reference. */
+ * [0, 1] and clamped, as generate.py:146-150 does around every transform.  JPEG is wmar_jpeg below. */
 int wmar_augment(int32_t op, const float* in_dev, float* out_dev, const float* noise_dev, int64_t B, int32_t C, int32_t H,
                  int32_t W, int32_t pm1, double p0, double p1, void* stream);
+
+/* JPEG round trip at `quality` (1..100), valuemetric.py:30-75: bit for bit the pixels PIL's save(format="JPEG", quality=q) +
+ * Image.open(...).convert("RGB") return (libjpeg-turbo's baseline path: 4:2:0, integer DCT, fancy upsampling), computed without a
+ * bitstream.  [B, 3, H, W] fp32 in [0, 1] (clamped on entry), H and W multiples of 16; buffers 16-byte aligned, in != out.
+ * passthrough != 0: the output is x + (jpeg(x) - x) in fp32, as the module's straight-through form, else jpeg(x); clamped to [0, 1].
+ * pm1 != 0: pixels cross the call in [-1, 1], as wmar_augment.  Two launches; `workspace_dev` holds the reconstructed Y / Cb / Cr
+ * samples in between: at least wmar_jpeg_workspace_bytes(B, H, W) bytes (0 if the kernel needs none), owned by the caller. */
+int64_t wmar_jpeg_workspace_bytes(int64_t B, int32_t H, int32_t W);
+int wmar_jpeg(const float* in_dev, float* out_dev, void* workspace_dev, int64_t workspace_bytes, int64_t B, int32_t H, int32_t W,
+              int32_t quality, int32_t pm1, int32_t passthrough, void* stream);
 
 /* ------------------------------------------------------------------------ exchange step (RCCL over xGMI)
  * The sharded job (one process per GPU; rank r == the reference's `--chunk_id r --num_chunks world`, generate.py:204, :304) has no

@@ -1,7 +1,9 @@
-"""The evaluation transforms as kernels of this build (``wmar_augment``, wmar_amd/csrc/augment.hip): what the transform modules run
-for tensors on the MI355X, and the harness's fused form -- one launch that reads the decoder's [-1, 1] batch, transforms it in
-[0, 1], clamps and writes [-1, 1] for the encoder (generate.py:146-150 around every (transform, parameter) pair; ~90 pairs per
-image).  CPU tensors keep the torch restatements in valuemetric.py / geometric.py (host-side utilities, as in the reference)."""
+"""The evaluation transforms as kernels of this build (``wmar_augment``, wmar_amd/csrc/augment.hip; ``wmar_jpeg``,
+wmar_amd/csrc/jpeg.hip): what the transform modules run for tensors on the MI355X, and the harness's fused form -- one launch (two
+for JPEG) that reads the decoder's [-1, 1] batch, transforms it in [0, 1], clamps and writes [-1, 1] for the encoder
+(generate.py:146-150 around every (transform, parameter) pair; ~90 pairs per image).  CPU tensors keep the torch restatements in
+valuemetric.py / geometric.py and PIL for JPEG (host-side utilities, as in the reference); so do JPEG inputs whose height or width is
+not a multiple of 16."""
 from __future__ import annotations
 
 import os
@@ -34,15 +36,40 @@ def run(op: int, image: torch.Tensor, p0: float = 0.0, p1: float = 0.0, noise: t
     return out[0] if image.dim() == 3 else out
 
 
+def jpeg_supported(image: torch.Tensor) -> bool:
+    """the device JPEG covers 3-channel images whose height and width are multiples of 16 (whole 4:2:0 MCUs, no edge padding)"""
+    return eligible(image) and image.shape[-3] == 3 and image.shape[-2] % 16 == 0 and image.shape[-1] % 16 == 0
+
+
+def jpeg(image: torch.Tensor, quality: int, pm1: bool = False, passthrough: bool = True) -> torch.Tensor:
+    """``JPEG(passthrough=passthrough)(image, quality)`` of valuemetric.py for a [B, 3, H, W] / [3, H, W] tensor on the device, H and W
+    multiples of 16: the pixels PIL's encoder + decoder return, bit for bit, without the host round trip (wmar_jpeg, two launches
+    over the whole batch).  With `pm1` the pixels cross the call in [-1, 1] (the harness's fused form)."""
+    x = image.unsqueeze(0) if image.dim() == 3 else image
+    x = x.contiguous()
+    if x.data_ptr() % 16:                       # a view at an odd offset: the kernels read and write 16-byte vectors
+        x = x.clone()
+    B, C, H, W = x.shape
+    if C != 3:
+        raise ValueError(f"jpeg: {C}-channel image (RGB only)")
+    out = torch.empty_like(x)
+    L = _lib.load()
+    ws = torch.empty(int(L.wmar_jpeg_workspace_bytes(B, H, W)), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.wmar_jpeg(x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, int(quality), 1 if pm1 else 0,
+                               1 if passthrough else 0, _lib.stream_ptr(x.device)))
+    return out[0] if image.dim() == 3 else out
+
+
 def _rotation(angle):
     quarters, rest = divmod(angle, 90)          # floor division: -20 -> (-1, 70), as Rotate.forward
     return quarters % 4, rest
 
 
 def fused(name: str, imgs_pm1: torch.Tensor, param):
-    """`aug(imgs / 2 + 0.5, param).clamp(0, 1) * 2 - 1` of the AugmentationManager table entry `name` as ONE launch, or None when the
-    entry has no device form (jpeg: host PIL) or the tensor is not eligible.  Bit-identical to the unfused sequence
-    (tests/test_gpu_augment_kernels.py)."""
+    """`aug(imgs / 2 + 0.5, param).clamp(0, 1) * 2 - 1` of the AugmentationManager table entry `name` as ONE launch (jpeg: two), or
+    None when the entry has no device form for this tensor (not eligible; jpeg: not 3 channels or a size that is not a multiple of
+    16).  Bit-identical to the unfused sequence (tests/test_gpu_augment_kernels.py, tests/test_gpu_jpeg.py)."""
     if not eligible(imgs_pm1) or imgs_pm1.dim() != 4:
         return None
     H, W = imgs_pm1.shape[-2:]
@@ -62,4 +89,6 @@ def fused(name: str, imgs_pm1: torch.Tensor, param):
     if name == "upperleft-crop":
         oh, ow = int(param * H), int(param * W)
         return run(IDENTITY if (oh, ow) == (H, W) else CROP_RESIZE, imgs_pm1, oh, ow, pm1=True)
+    if name == "jpeg":
+        return jpeg(imgs_pm1, param, pm1=True) if jpeg_supported(imgs_pm1) else None
     return None

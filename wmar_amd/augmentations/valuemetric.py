@@ -5,7 +5,9 @@ parameter one is drawn from the range given at construction.
 The reference delegates to ``torchvision.transforms.functional`` (absent offline).  Its tensor code paths are restated here:
 ``gaussian_blur(img, k)`` = separable kernel exp(-x^2 / 2 sigma^2) on x = -(k-1)/2 .. (k-1)/2 with
 sigma = 0.3 ((k-1)/2 - 1) + 0.8, reflect padding, depthwise convolution; ``adjust_brightness`` = factor * img clamped to [0, 1].
-JPEG stays on the host (PIL), as in the reference.
+``JPEG`` runs PIL's encoder and decoder on the host, as the reference does, for CPU tensors; for an eligible device tensor whose
+height and width are multiples of 16 it runs ``device_ops.jpeg`` (csrc/jpeg.hip), which computes the same pixels bit for bit without
+leaving the device.
 """
 from __future__ import annotations
 
@@ -102,6 +104,12 @@ class JPEG(_Ranged):
 
     def forward(self, image, quality=None):
         quality = quality or self.get_random_quality()
+        if _dev.jpeg_supported(image):          # MI355X: the whole batch in two launches (csrc/jpeg.hip), PIL's pixels bit for bit
+            if self.passthrough and image.requires_grad and torch.is_grad_enabled():
+                image = image.clamp(0, 1)       # the straight-through gradient of jpeg_single, formed in torch
+                coded = _dev.jpeg(image.detach(), quality, passthrough=False)
+                return (image + (coded - image).detach()).clamp(0, 1)
+            return _dev.jpeg(image, quality, passthrough=self.passthrough)
         image = image.clamp(0, 1)
         out = torch.stack([self.jpeg_single(one, quality) for one in image]) if image.dim() == 4 else self.jpeg_single(image, quality)
         return out.clamp(0, 1)
