@@ -46,24 +46,9 @@ struct wmar_cham {
     long long *tok = nullptr, *ids = nullptr;
     float2* rope = nullptr;
     int *pos = nullptr, *ctr = nullptr;     // ctr: [unused, step, len]
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool pending = false;
-    void drop_graph() {
-        if (pending && ev) (void)hipEventSynchronize(ev);
-        pending = false;
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        exec = nullptr; graph = nullptr;
-    }
-    ~wmar_cham() {
-        drop_graph();
-        mem.release();
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        if (ev) (void)hipEventDestroy(ev);
-    }
+    // wmar_cham_generate_image waits for its stream before it returns (it frees the prompt tables): no replay outlives the call,
+    // so it never marks the graph as replaying
+    GraphSlots<1> gr;
 };
 
 namespace {
@@ -233,102 +218,80 @@ int wmar_cham_create(const wmar_cham_config* cfg, const char* const* names, cons
     WMAR_REQUIRE(cfg->max_rows >= 1 && cfg->max_rows <= 128, "cham_create: max_rows must be in 1..128");
     WMAR_REQUIRE(cfg->max_seq_len >= 2, "cham_create: max_seq_len too small");
     WMAR_REQUIRE((D / 16 + CHAM_STAT_KB - 1) / CHAM_STAT_KB <= 128, "cham_create: dim %d gives more than 128 statistics chunks (k_cham_attn reads two per lane)", D);
-    TensorMap tm;
-    for (int i = 0; i < n_tensors; ++i) tm.m[names[i]] = tensors_dev[i];
+    TensorMap tm(names, tensors_dev, n_tensors);
     hipStream_t st = (hipStream_t)stream;
     auto* g = new wmar_cham();
     g->cfg = *cfg; g->D = D; g->H = H; g->Hkv = Hkv; g->hd = hd; g->V = V; g->L = L; g->F = F; g->Dkv = Hkv * hd;
     g->T = cfg->max_seq_len; g->Mmax = cfg->max_rows; g->MT = (cfg->max_rows + 31) / 32;
     const int bf = cfg->tensors_bf16;
-    int rc = WMAR_OK;
-    auto need = [&](const std::string& k) -> const void* {
-        auto it = tm.m.find(k);
-        if (it == tm.m.end()) {
-            if (rc == WMAR_OK) { set_error("checkpoint tensor '%s' is missing", k.c_str()); rc = WMAR_EMISSING; }
-            return nullptr;
-        }
-        return it->second;
-    };
-#define TRY(x) do { if (rc == WMAR_OK) rc = (x); } while (0)
+    int& rc = tm.rc;
     auto vec_f32 = [&](float** dst, const void* src, size_t n) -> int {
         if (int r = g->mem.alloc(dst, n)) return r;
         hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, *dst, (long long)n, bf);
         return launch_status("k_to_f32");
     };
-    const void *e = need("tok_embeddings.weight"), *nw = need("norm.weight"), *ow = need("output.weight");
+    const void *e = tm.need("tok_embeddings.weight"), *nw = tm.need("norm.weight"), *ow = tm.need("output.weight");
     if (rc == WMAR_OK) {
-        TRY(g->mem.alloc(&g->emb, (size_t)V * D));
+        WMAR_TRY(g->mem.alloc(&g->emb, (size_t)V * D));
         if (rc == WMAR_OK) {
             const long long n = (long long)V * D;
             hipLaunchKernelGGL(k_to_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e, g->emb, n, bf);
             rc = launch_status("k_to_bf16");
         }
-        TRY(g->mem.alloc(&g->whead, (size_t)V * D / 8));
-        TRY(bpack(ow, nw, g->whead, V, D, 0, 0, bf, st));
+        WMAR_TRY(g->mem.alloc(&g->whead, (size_t)V * D / 8));
+        WMAR_TRY(bpack(ow, nw, g->whead, V, D, 0, 0, bf, st));
     }
     g->layers.resize(L);
     const int Nqkv = D + 2 * g->Dkv;
     for (int l = 0; l < L && rc == WMAR_OK; ++l) {
         const std::string p = "layers." + std::to_string(l) + ".";
         ChamLayer& w = g->layers[l];
-        const void *qkv = need(p + "attention.wqkv.weight"), *wo = need(p + "attention.wo.weight"),
-                   *w13 = need(p + "feed_forward.w13.weight"), *w2 = need(p + "feed_forward.w2.weight"),
-                   *an = need(p + "attention_norm.weight"), *fn = need(p + "ffn_norm.weight");
+        const void *qkv = tm.need(p + "attention.wqkv.weight"), *wo = tm.need(p + "attention.wo.weight"),
+                   *w13 = tm.need(p + "feed_forward.w13.weight"), *w2 = tm.need(p + "feed_forward.w2.weight"),
+                   *an = tm.need(p + "attention_norm.weight"), *fn = tm.need(p + "ffn_norm.weight");
         const void *qw = nullptr, *qb = nullptr, *kw = nullptr, *kb = nullptr;
         if (cfg->qk_normalization) {
-            qw = need(p + "attention.q_normalization.weight"); qb = need(p + "attention.q_normalization.bias");
-            kw = need(p + "attention.k_normalization.weight"); kb = need(p + "attention.k_normalization.bias");
+            qw = tm.need(p + "attention.q_normalization.weight"); qb = tm.need(p + "attention.q_normalization.bias");
+            kw = tm.need(p + "attention.k_normalization.weight"); kb = tm.need(p + "attention.k_normalization.bias");
         }
         if (rc != WMAR_OK) break;
-        TRY(g->mem.alloc(&w.wqkv, (size_t)Nqkv * D / 8)); TRY(bpack(qkv, an, w.wqkv, Nqkv, D, 0, 0, bf, st));
-        TRY(g->mem.alloc(&w.wo, (size_t)D * D / 8)); TRY(bpack(wo, nullptr, w.wo, D, D, 0, 0, bf, st));
-        TRY(g->mem.alloc(&w.w13, (size_t)2 * F * D / 8)); TRY(bpack(w13, fn, w.w13, 2 * F, D, 1, F, bf, st));
-        TRY(g->mem.alloc(&w.w2, (size_t)D * F / 8)); TRY(bpack(w2, nullptr, w.w2, D, F, 0, 0, bf, st));
+        WMAR_TRY(g->mem.alloc(&w.wqkv, (size_t)Nqkv * D / 8)); WMAR_TRY(bpack(qkv, an, w.wqkv, Nqkv, D, 0, 0, bf, st));
+        WMAR_TRY(g->mem.alloc(&w.wo, (size_t)D * D / 8)); WMAR_TRY(bpack(wo, nullptr, w.wo, D, D, 0, 0, bf, st));
+        WMAR_TRY(g->mem.alloc(&w.w13, (size_t)2 * F * D / 8)); WMAR_TRY(bpack(w13, fn, w.w13, 2 * F, D, 1, F, bf, st));
+        WMAR_TRY(g->mem.alloc(&w.w2, (size_t)D * F / 8)); WMAR_TRY(bpack(w2, nullptr, w.w2, D, F, 0, 0, bf, st));
         w.qnw = w.qnb = w.knw = w.knb = nullptr;
         if (cfg->qk_normalization) {
-            TRY(vec_f32(&w.qnw, qw, (size_t)hd)); TRY(vec_f32(&w.qnb, qb, (size_t)hd));
-            TRY(vec_f32(&w.knw, kw, (size_t)hd)); TRY(vec_f32(&w.knb, kb, (size_t)hd));
+            WMAR_TRY(vec_f32(&w.qnw, qw, (size_t)hd)); WMAR_TRY(vec_f32(&w.qnb, qb, (size_t)hd));
+            WMAR_TRY(vec_f32(&w.knw, kw, (size_t)hd)); WMAR_TRY(vec_f32(&w.knb, kb, (size_t)hd));
         }
     }
     const size_t Mpad = (size_t)g->MT * 32;
-    TRY(g->mem.alloc(&g->x, Mpad * D / 8));
-    TRY(g->mem.alloc(&g->y, Mpad * D / 8));
-    TRY(g->mem.alloc(&g->hbuf, Mpad * F / 8));
-    TRY(g->mem.alloc(&g->slabs, (size_t)BG_MAXP * Mpad * D));
-    TRY(g->mem.alloc(&g->big_slabs, (size_t)BG_MAXP * Mpad * (size_t)std::max(Nqkv, 2 * F)));
-    TRY(g->mem.alloc(&g->ssq, (size_t)((D / 16 + CHAM_STAT_KB - 1) / CHAM_STAT_KB) * Mpad));
+    WMAR_TRY(g->mem.alloc_zero(&g->x, Mpad * D / 8, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->y, Mpad * D / 8, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->hbuf, Mpad * F / 8, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->slabs, (size_t)BG_MAXP * Mpad * D, st));                       // padding rows are never written
+    WMAR_TRY(g->mem.alloc_zero(&g->big_slabs, (size_t)BG_MAXP * Mpad * (size_t)std::max(Nqkv, 2 * F), st));
+    WMAR_TRY(g->mem.alloc(&g->ssq, (size_t)((D / 16 + CHAM_STAT_KB - 1) / CHAM_STAT_KB) * Mpad));
     const size_t kv = (size_t)L * g->Mmax * Hkv * g->T * hd;
-    TRY(g->mem.alloc(&g->kcache, kv));
-    TRY(g->mem.alloc(&g->vcache, kv));
-    TRY(g->mem.alloc(&g->logits, (size_t)g->Mmax * V));
-    TRY(g->mem.alloc(&g->scratch, (size_t)g->Mmax * V));
-    TRY(g->mem.alloc(&g->tok, Mpad));
-    TRY(g->mem.alloc(&g->pos, Mpad));
-    TRY(g->mem.alloc(&g->ids, (size_t)g->Mmax * (size_t)(g->T + 4)));
-    TRY(g->mem.alloc(&g->ctr, 4));
-    TRY(g->mem.alloc(&g->rope, (size_t)g->T * (hd / 2)));
+    WMAR_TRY(g->mem.alloc_zero(&g->kcache, kv, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->vcache, kv, st));
+    WMAR_TRY(g->mem.alloc(&g->logits, (size_t)g->Mmax * V));
+    WMAR_TRY(g->mem.alloc(&g->scratch, (size_t)g->Mmax * V));
+    WMAR_TRY(g->mem.alloc_zero(&g->tok, Mpad, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->pos, Mpad, st));
+    WMAR_TRY(g->mem.alloc(&g->ids, (size_t)g->Mmax * (size_t)(g->T + 4)));
+    WMAR_TRY(g->mem.alloc_zero(&g->ctr, 4, st));
+    WMAR_TRY(g->mem.alloc(&g->rope, (size_t)g->T * (hd / 2)));
     if (rc == WMAR_OK) {
         const long long n = (long long)g->T * (hd / 2);
         hipLaunchKernelGGL(k_rope_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->rope, g->T, hd / 2, cfg->rope_theta);
         rc = launch_status("k_rope_table");
     }
+    WMAR_TRY(g->gr.init());
     if (rc == WMAR_OK) {
-        hipError_t er = hipMemsetAsync(g->x, 0, Mpad * D * 2, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->y, 0, Mpad * D * 2, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->slabs, 0, (size_t)BG_MAXP * Mpad * D * 4, st);                       // padding rows are never written
-        if (er == hipSuccess) er = hipMemsetAsync(g->big_slabs, 0, (size_t)BG_MAXP * Mpad * (size_t)std::max(Nqkv, 2 * F) * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->hbuf, 0, Mpad * F * 2, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->kcache, 0, kv * 2, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->vcache, 0, kv * 2, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->tok, 0, Mpad * 8, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->pos, 0, Mpad * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->ctr, 0, 16, st);
-        if (er == hipSuccess) er = hipStreamCreateWithFlags(&g->cap_stream, hipStreamNonBlocking);
-        if (er == hipSuccess) er = hipEventCreate(&g->ev);
-        if (er == hipSuccess) er = hipStreamSynchronize(st);
+        const hipError_t er = hipStreamSynchronize(st);
         if (er != hipSuccess) { set_error("cham_create: %s", hipGetErrorString(er)); rc = WMAR_EHIP; }
     }
-#undef TRY
     if (rc != WMAR_OK) { delete g; return rc; }
     *out = g;
     return WMAR_OK;
@@ -342,7 +305,6 @@ int wmar_cham_forward_tokens(wmar_cham* g, const int64_t* tok_dev, const int32_t
     WMAR_REQUIRE(g && tok_dev && pos_dev, "cham_forward_tokens: null argument");
     WMAR_REQUIRE(M >= 1 && M <= g->Mmax, "cham_forward_tokens: rows %lld outside 1..%d", (long long)M, g->Mmax);
     hipStream_t st = (hipStream_t)stream;
-    if (g->pending) { (void)hipEventSynchronize(g->ev); g->pending = false; }
     WMAR_HIP_CHECK(hipMemcpyAsync(g->tok, tok_dev, (size_t)M * 8, hipMemcpyDeviceToDevice, st));
     WMAR_HIP_CHECK(hipMemcpyAsync(g->pos, pos_dev, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
     ChamPlan p(g, (int)M, st);
@@ -370,7 +332,7 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
     }
     WMAR_REQUIRE(maxlen + n_tokens <= g->T, "cham_generate_image: %d prompt + %d image tokens exceed max_seq_len %d", maxlen,
                  n_tokens, g->T);
-    g->drop_graph();
+    g->gr.drop();
     // right-aligned prompt tables (alignment.py:27-52): row m idles (token 0 at position 0) until its prompt starts
     // the watermark sees the whole padded row: keep its last CTX entries (prompt tokens, pad_id where the row is still padding)
     const int CTX = maxlen < 3 ? maxlen : 3;
@@ -453,15 +415,13 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
             const int gs = 4, lead = (n_tokens - 1) % gs;
             for (int n = 0; n < lead && rc == WMAR_OK; ++n) rc = one_step(st);
             if (rc == WMAR_OK && n_tokens - 1 - lead > 0) {
-                e = hipStreamBeginCapture(g->cap_stream, hipStreamCaptureModeThreadLocal);
-                if (e == hipSuccess) {
-                    for (int k = 0; k < gs && rc == WMAR_OK; ++k) rc = one_step(g->cap_stream);
-                    e = hipStreamEndCapture(g->cap_stream, &g->graph);
-                }
-                if (rc == WMAR_OK && e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-                for (int n = 1 + lead; n < n_tokens && rc == WMAR_OK && e == hipSuccess; n += gs) e = hipGraphLaunch(g->exec, st);
+                rc = g->gr.capture(0, [&](hipStream_t s) {
+                    int r = WMAR_OK;
+                    for (int k = 0; k < gs && r == WMAR_OK; ++k) r = one_step(s);
+                    return r;
+                });
+                for (int n = 1 + lead; n < n_tokens && rc == WMAR_OK; n += gs) rc = g->gr.replay(0, st);
             }
-            if (rc == WMAR_OK && e != hipSuccess) { set_error("cham_generate_image graph: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
         } else {
             for (int n = 1; n < n_tokens && rc == WMAR_OK; ++n) rc = one_step(st);
         }
@@ -471,7 +431,7 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
     (void)hipFree(tab_tok);
     (void)hipFree(tab_pos);
     if (rc == WMAR_OK && e2 != hipSuccess) { set_error("cham_generate_image: %s", hipGetErrorString(e2)); rc = WMAR_EHIP; }
-    if (rc != WMAR_OK) g->drop_graph();
+    if (rc != WMAR_OK) g->gr.drop();
     return rc;
 }
 

@@ -6,7 +6,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
+#include <vector>
 
 #include "../../include/wmar_hip.h"
 
@@ -106,6 +108,63 @@ inline int launch_status(const char* what) {
     }
     return WMAR_OK;
 }
+
+// Sticky status of the *_create functions: the first error wins, nothing is enqueued behind it.  Needs an `int rc` in scope.
+#define WMAR_TRY(x) do { if (rc == WMAR_OK) rc = (x); } while (0)
+
+// Device allocations of one engine (freed together).
+struct DeviceArena {
+    std::vector<void*> allocs;
+    int64_t bytes = 0;
+    template <typename T>
+    int alloc(T** p, size_t n) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, (n ? n : 1) * sizeof(T));
+        if (e != hipSuccess) {
+            set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
+            return WMAR_ENOMEM;
+        }
+        allocs.push_back(q);
+        bytes += (int64_t)(n * sizeof(T));
+        *p = (T*)q;
+        return WMAR_OK;
+    }
+    // ... zero-filled on `st` (buffers whose padding rows or flags are read before anything writes them)
+    template <typename T>
+    int alloc_zero(T** p, size_t n, hipStream_t st) {
+        if (int rc = alloc(p, n)) return rc;
+        WMAR_HIP_CHECK(hipMemsetAsync(*p, 0, n * sizeof(T), st));
+        return WMAR_OK;
+    }
+    DeviceArena() = default;
+    DeviceArena(const DeviceArena&) = delete;
+    DeviceArena& operator=(const DeviceArena&) = delete;
+    ~DeviceArena() { for (void* p : allocs) (void)hipFree(p); }
+};
+
+// The checkpoint as handed to a *_create function: name -> device pointer (fp32, or bf16 for Chameleon).  need() converts to the
+// pointer type its caller declares; the first missing name sets the error text and `rc`, which the caller's WMAR_TRY chain shares.
+struct TensorMap {
+    std::map<std::string, const void*> m;
+    int rc = WMAR_OK;
+    TensorMap(const char* const* names, const void* const* tensors_dev, int n) {
+        for (int i = 0; i < n; ++i) m[names[i]] = tensors_dev[i];
+    }
+    struct Ptr {
+        const void* p;
+        template <typename T> operator const T*() const { return (const T*)p; }
+    };
+    const float* get(const std::string& k) const {
+        auto it = m.find(k);
+        return it == m.end() ? nullptr : (const float*)it->second;
+    }
+    Ptr need(const std::string& k) {
+        auto it = m.find(k);
+        if (it != m.end()) return Ptr{it->second};
+        if (rc == WMAR_OK) { set_error("checkpoint tensor '%s' is missing", k.c_str()); rc = WMAR_EMISSING; }
+        return Ptr{nullptr};
+    }
+};
 
 // Context-row selection shared by the logit processor, the fused sampler and the
 // generation graph (gentime_watermark.py:233-263).  Returns -1 when the row must be skipped.

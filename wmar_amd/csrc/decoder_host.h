@@ -1,4 +1,7 @@
-// Host-side helpers shared by the decode engines (gpt.hip, rar.hip).
+// Host-side scaffold shared by the decode engines (gpt.hip, rar.hip, cham.hip): weight packing and GEMM dispatch, and the
+// mechanisms every engine drives its kernels with -- captured-graph lifetime (GraphSlots), the "whole grid resident" check, the
+// block -> XCD grouping probe and the re-run behind a failed in-launch barrier.  (The allocation list and the checkpoint lookup
+// are in common.h: vqgan.hip uses them without these kernels.)
 #pragma once
 #include <map>
 #include <string>
@@ -10,20 +13,19 @@ namespace wmar {
 
 inline int mt_for(int64_t B) { return B <= 32 ? 1 : (B <= 64 ? 2 : 4); }
 
-struct TensorMap {
-    std::map<std::string, const void*> m;
-    const float* get(const std::string& k) const {
-        auto it = m.find(k);
-        return it == m.end() ? nullptr : (const float*)it->second;
-    }
-};
-
 inline int pack(const float* W, float4* Wp, int N, int K, int nt_off, hipStream_t st,
          const float* gamma = nullptr) {
     long long total = (long long)(N / 32) * (K / 8) * 64;
     hipLaunchKernelGGL(k_pack_linear, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, Wp, N, K, nt_off, K / 8,
                        gamma);
     return launch_status("k_pack_linear");
+}
+
+// W[N][K] (columns scaled by gamma when given) -> Wq in k_pack_bx order, N / 32 column tiles from tile `tile_off` on
+inline int pack_bx(const float* W, const float* gamma, float4* Wq, int N, int K, int tile_off, hipStream_t st) {
+    const long long total = (long long)(N / 32) * (K / 16) * 128;
+    hipLaunchKernelGGL(k_pack_bx, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, gamma, Wq, N, K, tile_off);
+    return launch_status("k_pack_bx");
 }
 
 // dst[0..N) = bias + W beta
@@ -34,7 +36,7 @@ inline int fold_bias(const float* W, const float* bias, const float* beta, float
 
 template <typename Engine>
 int copy_vec(Engine* g, float** dst, const float* src, size_t n, hipStream_t st) {
-    if (int rc = g->alloc(dst, n)) return rc;
+    if (int rc = g->mem.alloc(dst, n)) return rc;
     WMAR_HIP_CHECK(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     return WMAR_OK;
 }
@@ -106,27 +108,113 @@ inline int gemm_split(GemmArgs a, int* S_out, hipStream_t st, int force_S = 0) {
 inline int stat_chunks(int KB) { const int n = (KB + WMAR_STAT_CHUNK - 1) / WMAR_STAT_CHUNK; return n <= STAT_CHUNKS_MAX ? n : (KB + 15) / 16; }
 
 
-// Device allocations of one engine (freed together).
-struct DeviceArena {
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
-    template <typename T>
-    int alloc(T** p, size_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) {
-            set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            return WMAR_ENOMEM;
-        }
-        allocs.push_back(q);
-        bytes += (int64_t)(n * sizeof(T));
-        *p = (T*)q;
+// Captured graphs of one engine: N graph / exec slots on one capture stream, and the rule for their lifetime -- an exec that may
+// still be replaying (`pending`, until the `done` event recorded behind the last replays has passed) is waited for before it is
+// destroyed, and a capture that fails leaves no graph behind.  Which slot is captured when, and when graphs are reused, is the
+// engine's policy.  Declared BEHIND the engine's DeviceArena, so that the graphs are dropped before the memory they use is freed.
+template <int N>
+struct GraphSlots {
+    hipStream_t cap = nullptr;
+    hipEvent_t done = nullptr;
+    hipGraph_t graph[N] = {};
+    hipGraphExec_t exec[N] = {};
+    bool pending = false;
+    int init() {
+        WMAR_HIP_CHECK(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
+        WMAR_HIP_CHECK(hipEventCreate(&done));
         return WMAR_OK;
     }
-    void release() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear();
+    void drop() {
+        if (pending && done) (void)hipEventSynchronize(done);
+        pending = false;
+        for (int i = 0; i < N; ++i) {
+            if (exec[i]) (void)hipGraphExecDestroy(exec[i]);
+            if (graph[i]) (void)hipGraphDestroy(graph[i]);
+            exec[i] = nullptr; graph[i] = nullptr;
+        }
+    }
+    // slot <- the launches `enqueue(cap)` puts on the capture stream, instantiated.  On any failure every slot is dropped.
+    template <typename F>
+    int capture(int slot, F&& enqueue) {
+        int rc = WMAR_OK;
+        hipError_t e = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
+        if (e != hipSuccess) { set_error("hipStreamBeginCapture: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
+        else {
+            rc = enqueue(cap);
+            e = hipStreamEndCapture(cap, &graph[slot]);      // ends the capture whatever `enqueue` returned
+            if (rc == WMAR_OK && e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
+        }
+        if (rc == WMAR_OK && (e = hipGraphInstantiate(&exec[slot], graph[slot], nullptr, nullptr, 0)) != hipSuccess) {
+            set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); rc = WMAR_EHIP;
+        }
+        if (rc != WMAR_OK) drop();
+        return rc;
+    }
+    int replay(int slot, hipStream_t st) {
+        const hipError_t e = hipGraphLaunch(exec[slot], st);
+        if (e != hipSuccess) { set_error("graph replay failed: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+        return WMAR_OK;
+    }
+    // behind the last replay of a call: from here on drop() waits for them
+    int replayed(hipStream_t st) {
+        const hipError_t e = hipEventRecord(done, st);
+        if (e != hipSuccess) { set_error("graph replay failed: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+        pending = true;
+        return WMAR_OK;
+    }
+    GraphSlots() = default;
+    GraphSlots(const GraphSlots&) = delete;
+    GraphSlots& operator=(const GraphSlots&) = delete;
+    ~GraphSlots() {
+        drop();
+        if (cap) (void)hipStreamDestroy(cap);
+        if (done) (void)hipEventDestroy(done);
     }
 };
+
+// Can every workgroup of a `blocks`-wide grid be resident at once?  (What the device holds: workgroups per compute unit x the
+// compute units the runtime exposes -- a CU mask or a partition mode shrinks it.)  Kernels whose workgroups wait for each other
+// inside one launch need it; a query that fails counts as "no".
+inline bool grid_resident(int blocks_per_cu, long long blocks) {
+    int dev = 0, cus = 0;
+    return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+           (long long)blocks_per_cu * cus >= blocks;
+}
+template <typename Kernel>
+bool grid_resident(Kernel kernel, int threads, long long blocks) {
+    int nb = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, 0) == hipSuccess && grid_resident(nb, blocks);
+}
+
+// Do the blocks of a `blocks`-wide grid with equal blockIdx % 8 share an XCD, the eight groups on eight different ones?  Three
+// launches of k_xcc_probe: the id a group gets rotates with the launches before it, the grouping must not.
+inline bool xcd_grouping_ok(int blocks, int threads, hipStream_t st) {
+    unsigned* tmp = nullptr;
+    std::vector<unsigned> h((size_t)blocks);
+    bool ok = hipMalloc(&tmp, (size_t)blocks * 4) == hipSuccess;
+    for (int rep = 0; rep < 3 && ok; ++rep) {
+        hipLaunchKernelGGL(k_xcc_probe, dim3((unsigned)blocks), dim3((unsigned)threads), 0, st, tmp);
+        ok = hipMemcpyAsync(h.data(), tmp, (size_t)blocks * 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+        unsigned seen = 0;
+        for (int b = 0; b < blocks && ok; ++b) ok = h[b] == h[b & 7] && h[b] < 16;
+        for (int x = 0; x < 8 && ok; ++x) { ok = !(seen & (1u << h[x])); seen |= 1u << h[x]; }
+    }
+    if (tmp) (void)hipFree(tmp);
+    return ok;
+}
+
+// Work that may run a launch with an in-launch barrier: `run()` enqueues it, `failed()` then reads the barrier's flag (the engine's
+// *_sync_failed: 1 = the flag was up and the engine has switched to its fallback path, < 0 = error).  A failed run is repeated
+// once -- on the fallback path, where the flag cannot come up; `still_up` is the error text if it does.
+template <typename Run, typename Failed>
+int run_with_fallback(const char* still_up, Run&& run, Failed&& failed) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (int rc = run()) return rc;
+        const int f = failed();
+        if (f <= 0) return f;
+    }
+    set_error("%s", still_up);
+    return WMAR_EHIP;
+}
 
 }  // namespace wmar

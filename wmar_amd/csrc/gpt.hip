@@ -47,8 +47,7 @@ struct SmallW {
 struct wmar_gpt {
     wmar_gpt_config cfg{};
     int D = 0, H = 0, hd = 0, V = 0, L = 0, Tmax = 0, Bmax = 0, MTmax = 0;
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
+    DeviceArena mem;
     std::vector<LayerW> layers;
     // small-batch path (1..12 rows, n_embd 1536, head_dim 64): streaming kernels on row-major weights, five launches per layer
     std::vector<SmallW> sw;
@@ -74,25 +73,13 @@ struct wmar_gpt {
     float *logits = nullptr, *scratch = nullptr;
     long long* past = nullptr;  // [Bmax][Tmax+1]
     int *pos_dev = nullptr, *step_dev = nullptr;
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev0 = nullptr;      // start of a timed span (its end is gr.done)
     // One captured step per attention phase: the decode attention runs 1 / 2 / 4 waves per (sequence, head) while the
     // cache is short / medium / long (att_phase(): fixed cost 7.0 / 9.8 / 13.5 us against loads in flight).
     static constexpr int N_PHASE = 3;
-    hipGraph_t graph[N_PHASE] = {nullptr, nullptr, nullptr};
-    hipGraphExec_t exec[N_PHASE] = {nullptr, nullptr, nullptr};
+    GraphSlots<N_PHASE> gr;
     int att_nw = 2;                // waves per attention workgroup of the step being enqueued
     unsigned long long graph_key[12] = {0};
-    bool pending = false;          // replays of `exec` may still be running (ev1 marks their end)
-    void drop_graph() {
-        if (pending && ev1) (void)hipEventSynchronize(ev1);
-        pending = false;
-        for (int i = 0; i < N_PHASE; ++i) {
-            if (exec[i]) (void)hipGraphExecDestroy(exec[i]);
-            if (graph[i]) (void)hipGraphDestroy(graph[i]);
-            exec[i] = nullptr; graph[i] = nullptr;
-        }
-    }
     // phase of the step that attends to `kv` cached rows (including the new one)
     // Measured at batch 64 with the QKV projection arriving in 7 split-K pieces (round 2): one wave per (sequence, head) is the
     // fastest variant at every cache length up to 256 (the prologue that sums the pieces runs in wave 0 while the others
@@ -158,25 +145,8 @@ struct wmar_gpt {
         ev_used = 0;
     }
 
-    template <typename T>
-    int alloc(T** p, size_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, n * sizeof(T));
-        if (e != hipSuccess) {
-            set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            return WMAR_ENOMEM;
-        }
-        allocs.push_back(q);
-        bytes += (int64_t)(n * sizeof(T));
-        *p = (T*)q;
-        return WMAR_OK;
-    }
     ~wmar_gpt() {
-        drop_graph();
-        for (void* p : allocs) (void)hipFree(p);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
         if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
     }
 };
@@ -611,8 +581,7 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
     WMAR_REQUIRE(hd == 32 || hd == 64 || hd == 128, "head_dim %d unsupported (32, 64, 128)", hd);
     WMAR_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= 128, "max_batch must be in 1..128");
     WMAR_REQUIRE(cfg->block_size >= 1 && L >= 1, "bad block_size / n_layer");
-    TensorMap tm;
-    for (int i = 0; i < n_tensors; ++i) tm.m[names[i]] = tensors_dev[i];
+    TensorMap tm(names, tensors_dev, n_tensors);
     hipStream_t st = (hipStream_t)stream;
     auto* g = new wmar_gpt();
     g->cfg = *cfg; g->D = D; g->H = H; g->hd = hd; g->V = V; g->L = L; g->Tmax = cfg->block_size; g->Bmax = cfg->max_batch;
@@ -639,92 +608,77 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
     if (getenv("WMAR_DBG_SUMS")) { if (hipMalloc(&g->dbg_sums, 4096 * 8) != hipSuccess) g->dbg_sums = nullptr; }
     g->no_bx_qkv = getenv("WMAR_NO_BX_QKV") != nullptr; g->no_bx_proj = getenv("WMAR_NO_BX_PROJ") != nullptr;   // one role at a time (bisecting)
 #endif
-    int rc = WMAR_OK;
-    auto need = [&](const std::string& k) -> const float* {
-        const float* p = tm.get(k);
-        if (!p && rc == WMAR_OK) { set_error("checkpoint tensor '%s' is missing", k.c_str()); rc = WMAR_EMISSING; }
-        return p;
-    };
-#define TRY(x) do { if (rc == WMAR_OK) rc = (x); } while (0)
-    const float* te = need("tok_emb.weight");
-    const float* pe = need("pos_emb");
-    const float* hw = need("head.weight");
-    const float *lfw = need("ln_f.weight"), *lfb = need("ln_f.bias");
+    int& rc = tm.rc;
+    const float* te = tm.need("tok_emb.weight");
+    const float* pe = tm.need("pos_emb");
+    const float* hw = tm.need("head.weight");
+    const float *lfw = tm.need("ln_f.weight"), *lfb = tm.need("ln_f.bias");
     if (rc == WMAR_OK) {
-        TRY(copy_vec(g, &g->tok_emb, te, (size_t)V * D, st));
-        TRY(copy_vec(g, &g->pos_emb, pe, (size_t)cfg->block_size * D, st));
-        TRY(g->alloc(&g->whead, (size_t)V * D / 4));
-        TRY(pack(hw, g->whead, V, D, 0, st, lfw));
-        TRY(g->alloc(&g->bhead, (size_t)V));
-        TRY(fold_bias(hw, nullptr, lfb, g->bhead, V, D, st));
-        TRY(g->alloc(&g->chead, (size_t)V));
-        TRY(fold_bias(hw, nullptr, lfw, g->chead, V, D, st));
+        WMAR_TRY(copy_vec(g, &g->tok_emb, te, (size_t)V * D, st));
+        WMAR_TRY(copy_vec(g, &g->pos_emb, pe, (size_t)cfg->block_size * D, st));
+        WMAR_TRY(g->mem.alloc(&g->whead, (size_t)V * D / 4));
+        WMAR_TRY(pack(hw, g->whead, V, D, 0, st, lfw));
+        WMAR_TRY(g->mem.alloc(&g->bhead, (size_t)V));
+        WMAR_TRY(fold_bias(hw, nullptr, lfb, g->bhead, V, D, st));
+        WMAR_TRY(g->mem.alloc(&g->chead, (size_t)V));
+        WMAR_TRY(fold_bias(hw, nullptr, lfw, g->chead, V, D, st));
     }
     g->layers.resize(L);
     for (int l = 0; l < L && rc == WMAR_OK; ++l) {
         std::string p = "blocks." + std::to_string(l) + ".";
         LayerW& w = g->layers[l];
-        const float *qw = need(p + "attn.query.weight"), *kw = need(p + "attn.key.weight"), *vw = need(p + "attn.value.weight");
-        const float *qb = need(p + "attn.query.bias"), *kb = need(p + "attn.key.bias"), *vb = need(p + "attn.value.bias");
-        const float *pw = need(p + "attn.proj.weight"), *pb = need(p + "attn.proj.bias");
-        const float *f1w = need(p + "mlp.0.weight"), *f1b = need(p + "mlp.0.bias");
-        const float *f2w = need(p + "mlp.2.weight"), *f2b = need(p + "mlp.2.bias");
-        const float *l1w = need(p + "ln1.weight"), *l1b = need(p + "ln1.bias"), *l2w = need(p + "ln2.weight"), *l2b = need(p + "ln2.bias");
+        const float *qw = tm.need(p + "attn.query.weight"), *kw = tm.need(p + "attn.key.weight"), *vw = tm.need(p + "attn.value.weight");
+        const float *qb = tm.need(p + "attn.query.bias"), *kb = tm.need(p + "attn.key.bias"), *vb = tm.need(p + "attn.value.bias");
+        const float *pw = tm.need(p + "attn.proj.weight"), *pb = tm.need(p + "attn.proj.bias");
+        const float *f1w = tm.need(p + "mlp.0.weight"), *f1b = tm.need(p + "mlp.0.bias");
+        const float *f2w = tm.need(p + "mlp.2.weight"), *f2b = tm.need(p + "mlp.2.bias");
+        const float *l1w = tm.need(p + "ln1.weight"), *l1b = tm.need(p + "ln1.bias"), *l2w = tm.need(p + "ln2.weight"), *l2b = tm.need(p + "ln2.bias");
         if (rc != WMAR_OK) break;
-        TRY(g->alloc(&w.wqkv, (size_t)3 * D * D / 4));
-        TRY(pack(qw, w.wqkv, D, D, 0, st, l1w));
-        TRY(pack(kw, w.wqkv, D, D, D / 32, st, l1w));
-        TRY(pack(vw, w.wqkv, D, D, 2 * D / 32, st, l1w));
+        WMAR_TRY(g->mem.alloc(&w.wqkv, (size_t)3 * D * D / 4));
+        WMAR_TRY(pack(qw, w.wqkv, D, D, 0, st, l1w));
+        WMAR_TRY(pack(kw, w.wqkv, D, D, D / 32, st, l1w));
+        WMAR_TRY(pack(vw, w.wqkv, D, D, 2 * D / 32, st, l1w));
         if (g->MTmax >= 2 && D % 16 == 0 && (3 * D / 32) % 4 == 0) {
-            auto pack_bx = [&](const float* W, int tile_off) -> int {
-                const long long total = (long long)(D / 32) * (D / 16) * 128;
-                hipLaunchKernelGGL(k_pack_bx, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, l1w, w.wqkvx_bx, D, D, tile_off);
-                return launch_status("k_pack_bx");
-            };
-            TRY(g->alloc(&w.wqkvx_bx, (size_t)3 * D * D / 4));
-            TRY(pack_bx(qw, 0));
-            TRY(pack_bx(kw, D / 32));
-            TRY(pack_bx(vw, 2 * D / 32));
+            WMAR_TRY(g->mem.alloc(&w.wqkvx_bx, (size_t)3 * D * D / 4));
+            WMAR_TRY(pack_bx(qw, l1w, w.wqkvx_bx, D, D, 0, st));
+            WMAR_TRY(pack_bx(kw, l1w, w.wqkvx_bx, D, D, D / 32, st));
+            WMAR_TRY(pack_bx(vw, l1w, w.wqkvx_bx, D, D, 2 * D / 32, st));
         }
-        TRY(g->alloc(&w.bqkv, (size_t)3 * D));
-        TRY(fold_bias(qw, qb, l1b, w.bqkv, D, D, st));
-        TRY(fold_bias(kw, kb, l1b, w.bqkv + D, D, D, st));
-        TRY(fold_bias(vw, vb, l1b, w.bqkv + 2 * D, D, D, st));
-        TRY(g->alloc(&w.cqkv, (size_t)3 * D));
-        TRY(fold_bias(qw, nullptr, l1w, w.cqkv, D, D, st));
-        TRY(fold_bias(kw, nullptr, l1w, w.cqkv + D, D, D, st));
-        TRY(fold_bias(vw, nullptr, l1w, w.cqkv + 2 * D, D, D, st));
-        TRY(g->alloc(&w.wproj, (size_t)D * D / 4));
-        TRY(pack(pw, w.wproj, D, D, 0, st));
-        TRY(copy_vec(g, &w.bproj, pb, D, st));
+        WMAR_TRY(g->mem.alloc(&w.bqkv, (size_t)3 * D));
+        WMAR_TRY(fold_bias(qw, qb, l1b, w.bqkv, D, D, st));
+        WMAR_TRY(fold_bias(kw, kb, l1b, w.bqkv + D, D, D, st));
+        WMAR_TRY(fold_bias(vw, vb, l1b, w.bqkv + 2 * D, D, D, st));
+        WMAR_TRY(g->mem.alloc(&w.cqkv, (size_t)3 * D));
+        WMAR_TRY(fold_bias(qw, nullptr, l1w, w.cqkv, D, D, st));
+        WMAR_TRY(fold_bias(kw, nullptr, l1w, w.cqkv + D, D, D, st));
+        WMAR_TRY(fold_bias(vw, nullptr, l1w, w.cqkv + 2 * D, D, D, st));
+        WMAR_TRY(g->mem.alloc(&w.wproj, (size_t)D * D / 4));
+        WMAR_TRY(pack(pw, w.wproj, D, D, 0, st));
+        WMAR_TRY(copy_vec(g, &w.bproj, pb, D, st));
         if (g->MTmax >= 2 && D % BX_KSLICE == 0 && D / BX_KSLICE <= MAX_SLABS) {
-            const long long total = (long long)(D / 32) * (D / 16) * 128;
-            TRY(g->alloc(&w.wproj_bx, (size_t)D * D / 4));
-            if (rc == WMAR_OK) {
-                hipLaunchKernelGGL(k_pack_bx, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pw, (const float*)nullptr, w.wproj_bx, D, D, 0);
-                rc = launch_status("k_pack_bx");
-            }
+            WMAR_TRY(g->mem.alloc(&w.wproj_bx, (size_t)D * D / 4));
+            WMAR_TRY(pack_bx(pw, nullptr, w.wproj_bx, D, D, 0, st));
         }
-        TRY(g->alloc(&w.wfc1, (size_t)4 * D * D / 4));
-        TRY(pack(f1w, w.wfc1, 4 * D, D, 0, st, l2w));
+        WMAR_TRY(g->mem.alloc(&w.wfc1, (size_t)4 * D * D / 4));
+        WMAR_TRY(pack(f1w, w.wfc1, 4 * D, D, 0, st, l2w));
         if ((4 * D) % 24 == 0 && (D / 16) % 16 == 0 && g->MTmax >= 2) {
             // batches of 33..64 rows run FC1 on 24-column tiles (k_fc1x: one workgroup per CU at n_embd 1536); the 32-column
             // packing above serves the other batch sizes
             const size_t units = (size_t)(4 * D / 24) * (D / 16) * 64;
-            TRY(g->alloc(&w.wfc1x16, units));
-            TRY(g->alloc(&w.wfc1x8, units));
+            WMAR_TRY(g->mem.alloc(&w.wfc1x16, units));
+            WMAR_TRY(g->mem.alloc(&w.wfc1x8, units));
             if (rc == WMAR_OK) {
                 hipLaunchKernelGGL(k_pack_fc1x, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, f1w, l2w, w.wfc1x16, w.wfc1x8, 4 * D, D);
                 rc = launch_status("k_pack_fc1x");
             }
         }
-        TRY(g->alloc(&w.bfc1, (size_t)4 * D));
-        TRY(fold_bias(f1w, f1b, l2b, w.bfc1, 4 * D, D, st));
-        TRY(g->alloc(&w.cfc1, (size_t)4 * D));
-        TRY(fold_bias(f1w, nullptr, l2w, w.cfc1, 4 * D, D, st));
-        TRY(g->alloc(&w.wfc2, (size_t)4 * D * D / 4));
-        TRY(pack(f2w, w.wfc2, D, 4 * D, 0, st));
-        TRY(copy_vec(g, &w.bfc2, f2b, D, st));
+        WMAR_TRY(g->mem.alloc(&w.bfc1, (size_t)4 * D));
+        WMAR_TRY(fold_bias(f1w, f1b, l2b, w.bfc1, 4 * D, D, st));
+        WMAR_TRY(g->mem.alloc(&w.cfc1, (size_t)4 * D));
+        WMAR_TRY(fold_bias(f1w, nullptr, l2w, w.cfc1, 4 * D, D, st));
+        WMAR_TRY(g->mem.alloc(&w.wfc2, (size_t)4 * D * D / 4));
+        WMAR_TRY(pack(f2w, w.wfc2, D, 4 * D, 0, st));
+        WMAR_TRY(copy_vec(g, &w.bfc2, f2b, D, st));
     }
     // small-batch path (decode_small.h): the weights once more in the checkpoint's row-major layout (LayerNorm not folded), 5.5 GB at
     // 48 layers x 1536.  Shapes: n_embd = two K segments of 768, head_dim 64.  WMAR_NO_SMALL=1 at creation keeps 1..12 rows on the
@@ -733,7 +687,7 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
         g->sw.resize(L);
         const size_t DD = (size_t)D * D;
         // ONE allocation, fixed per-layer stride (decode_persist.h forms every address from this base)
-        TRY(g->alloc(&g->sw_arena, (size_t)L * SS_LAYER_FLOATS));
+        WMAR_TRY(g->mem.alloc(&g->sw_arena, (size_t)L * SS_LAYER_FLOATS));
         for (int l = 0; l < L && rc == WMAR_OK; ++l) {
             std::string p = "blocks." + std::to_string(l) + ".";
             SmallW& w = g->sw[l];
@@ -753,13 +707,13 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
             cp(w.ln1w, "ln1.weight", D); cp(w.ln1b, "ln1.bias", D); cp(w.ln2w, "ln2.weight", D); cp(w.ln2b, "ln2.bias", D);
             if (e != hipSuccess) { set_error("gpt_create: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
         }
-        TRY(copy_vec(g, &g->whead_rm, hw, (size_t)V * D, st));
-        TRY(copy_vec(g, &g->lnfw, lfw, D, st));
-        TRY(copy_vec(g, &g->lnfb, lfb, D, st));
-        TRY(g->alloc(&g->xs, (size_t)SG_MAX_ROWS * D));
-        TRY(g->alloc(&g->ys, (size_t)SG_MAX_ROWS * D));
-        TRY(g->alloc(&g->hs, (size_t)SG_MAX_ROWS * 4 * D));
-        TRY(g->alloc(&g->qs, (size_t)SG_MAX_ROWS * D));
+        WMAR_TRY(copy_vec(g, &g->whead_rm, hw, (size_t)V * D, st));
+        WMAR_TRY(copy_vec(g, &g->lnfw, lfw, D, st));
+        WMAR_TRY(copy_vec(g, &g->lnfb, lfb, D, st));
+        WMAR_TRY(g->mem.alloc(&g->xs, (size_t)SG_MAX_ROWS * D));
+        WMAR_TRY(g->mem.alloc(&g->ys, (size_t)SG_MAX_ROWS * D));
+        WMAR_TRY(g->mem.alloc(&g->hs, (size_t)SG_MAX_ROWS * 4 * D));
+        WMAR_TRY(g->mem.alloc(&g->qs, (size_t)SG_MAX_ROWS * D));
         g->small_ok = rc == WMAR_OK;
         // the persistent step: per-layer pointer table, barrier words; all 256 workgroups of 320 threads must be resident at once and
         // workgroups with equal blockIdx % 8 must share an XCD (probed below with the kernel's own grid).  WMAR_NO_PERSIST=1: off.
@@ -768,92 +722,49 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
         // 1.63 ms per step at batch 1, 2.85 against 1.89 at batch 5) -- the barrier's atomics and polls travel through the same in-order
         // per-CU memory pipeline as the weight prefetch they are meant to overlap with; kept as a tested experiment, not the default plan.
         if (g->small_ok && getenv("WMAR_PERSIST") && !getenv("WMAR_NO_PERSIST")) {
-            TRY(g->alloc(&g->ss_bar, (size_t)SS_BAR_WORDS));
-            if (rc == WMAR_OK && hipMemsetAsync(g->ss_bar, 0, SS_BAR_WORDS * 4, st) != hipSuccess) { set_error("gpt_create: memset failed"); rc = WMAR_EHIP; }
-            if (rc == WMAR_OK) {
-                int dev = 0, cus = 0;
-                bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
-                ok = ok && (long long)sstep_blocks_per_cu() * cus >= SS_WGS;
-                unsigned* tmp = nullptr;
-                ok = ok && hipMalloc(&tmp, SS_WGS * 4) == hipSuccess;
-                for (int rep = 0; rep < 3 && ok; ++rep) {
-                    unsigned h[SS_WGS];
-                    hipLaunchKernelGGL(k_xcc_probe, dim3(SS_WGS), dim3(SS_THREADS), 0, st, tmp);
-                    ok = hipMemcpyAsync(h, tmp, sizeof h, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-                    unsigned seen = 0;
-                    for (int b = 0; b < SS_WGS && ok; ++b) ok = h[b] == h[b & 7] && h[b] < 16;
-                    for (int x = 0; x < 8 && ok; ++x) { ok = !(seen & (1u << h[x])); seen |= 1u << h[x]; }
-                }
-                if (tmp) (void)hipFree(tmp);
-                g->persist_ok = ok;
-            }
+            WMAR_TRY(g->mem.alloc_zero(&g->ss_bar, (size_t)SS_BAR_WORDS, st));
+            if (rc == WMAR_OK) g->persist_ok = grid_resident(sstep_blocks_per_cu(), SS_WGS) && xcd_grouping_ok(SS_WGS, SS_THREADS, st);
         }
     }
     const size_t Mpad = (size_t)g->MTmax * 32;
-    TRY(g->alloc(&g->x, Mpad * D / 4));
-    TRY(g->alloc(&g->x2, Mpad * D / 4));
-    TRY(g->alloc(&g->y, Mpad * D / 4));
-    TRY(g->alloc(&g->hbuf, Mpad * 4 * D / 4));
-    TRY(g->alloc(&g->slabs, (size_t)MAX_SLABS * Mpad * D / 4));
-    TRY(g->alloc(&g->qkv_slabs, (size_t)MAX_SLABS * Mpad * 3 * D / 4));
-    if (g->MTmax >= 2 && D % BX_KSLICE == 0) TRY(g->alloc(&g->yq, (size_t)D / 16 * 2 * 3 * 64));
-    TRY(g->alloc(&g->qbuf, Mpad * D));
-    TRY(g->alloc(&g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2));
-    TRY(g->alloc(&g->stats_q, (size_t)QKV_SLABS_MAX * 4 * Mpad * 2));      // x 4: k_qkvx_bx's keeper groups per K slice
+    // (zero-filled: padded rows of the packed buffers must hold finite numbers)
+    WMAR_TRY(g->mem.alloc_zero(&g->x, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->x2, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->y, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->hbuf, Mpad * 4 * D / 4, st));
+    WMAR_TRY(g->mem.alloc(&g->slabs, (size_t)MAX_SLABS * Mpad * D / 4));
+    WMAR_TRY(g->mem.alloc(&g->qkv_slabs, (size_t)MAX_SLABS * Mpad * 3 * D / 4));
+    if (g->MTmax >= 2 && D % BX_KSLICE == 0) WMAR_TRY(g->mem.alloc_zero(&g->yq, (size_t)D / 16 * 2 * 3 * 64, st));   // rows past the batch are never written
+    WMAR_TRY(g->mem.alloc_zero(&g->qbuf, Mpad * D, st));
+    WMAR_TRY(g->mem.alloc(&g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2));
+    WMAR_TRY(g->mem.alloc(&g->stats_q, (size_t)QKV_SLABS_MAX * 4 * Mpad * 2));      // x 4: k_qkvx_bx's keeper groups per K slice
     const size_t kv = (size_t)L * g->Bmax * H * g->Tmax * hd;
-    TRY(g->alloc(&g->kcache, kv));
-    TRY(g->alloc(&g->vcache, kv));
-    TRY(g->alloc(&g->logits, (size_t)g->Bmax * V));
-    TRY(g->alloc(&g->scratch, (size_t)g->Bmax * V));
-    TRY(g->alloc(&g->past, (size_t)g->Bmax * (g->Tmax + 1)));
-    TRY(g->alloc(&g->pos_dev, 4));
-    TRY(g->alloc(&g->xsync, 8 * 64 + 64));
+    WMAR_TRY(g->mem.alloc_zero(&g->kcache, kv, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->vcache, kv, st));
+    WMAR_TRY(g->mem.alloc(&g->logits, (size_t)g->Bmax * V));
+    WMAR_TRY(g->mem.alloc(&g->scratch, (size_t)g->Bmax * V));
+    WMAR_TRY(g->mem.alloc_zero(&g->past, (size_t)g->Bmax * (g->Tmax + 1), st));
+    WMAR_TRY(g->mem.alloc(&g->pos_dev, 4));
+    WMAR_TRY(g->mem.alloc_zero(&g->xsync, 8 * 64 + 64, st));
     g->step_dev = g->pos_dev + 1;
+    WMAR_TRY(g->gr.init());
     if (rc == WMAR_OK) {
-        // padded rows of the packed buffers must hold finite numbers
-        hipError_t e = hipMemsetAsync(g->x, 0, Mpad * D * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->x2, 0, Mpad * D * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->kcache, 0, kv * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->vcache, 0, kv * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->hbuf, 0, Mpad * 4 * D * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->past, 0, (size_t)g->Bmax * (g->Tmax + 1) * 8, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->y, 0, Mpad * D * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->qbuf, 0, Mpad * D * 4, st);
-        if (e == hipSuccess && g->yq) e = hipMemsetAsync(g->yq, 0, (size_t)D / 16 * 2 * 3 * 64 * 16, st);   // rows past the batch are never written
-        if (e == hipSuccess) e = hipMemsetAsync(g->xsync, 0, (8 * 64 + 64) * 4, st);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->cap_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreate(&g->ev0);
-        if (e == hipSuccess) e = hipEventCreate(&g->ev1);
+        hipError_t e = hipEventCreate(&g->ev0);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { set_error("gpt_create: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
     }
-#undef TRY
     if (rc == WMAR_OK && g->MTmax >= 2 && g->yq) {
         // k_bx_xr keeps a split-K reduction inside an XCD: probe that the 24 blocks of a 192-block grid with equal blockIdx % 8
         // share an XCC id and that the eight groups land on eight different XCDs (three launches: the id a group gets rotates with
         // the launches before it, the grouping must not).  Anything else keeps the two-launch path.
         g->no_xr = getenv("WMAR_NO_XR") != nullptr;
-        unsigned* tmp = nullptr;
-        bool ok = hipMalloc(&tmp, 192 * 4) == hipSuccess;
-        for (int rep = 0; rep < 3 && ok; ++rep) {
-            unsigned h[192];
-            hipLaunchKernelGGL(k_xcc_probe, dim3(192), dim3(256), 0, st, tmp);
-            ok = hipMemcpyAsync(h, tmp, sizeof h, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-            unsigned seen = 0;
-            for (int b = 0; b < 192 && ok; ++b) ok = h[b] == h[b & 7] && h[b] < 16;
-            for (int x = 0; x < 8 && ok; ++x) { ok = !(seen & (1u << h[x])); seen |= 1u << h[x]; }
-        }
-        if (tmp) (void)hipFree(tmp);
         // ... and every workgroup of its grid must be resident at once: one per CU at least (a CU mask or a partition mode shrinks
         // what the runtime reports)
         // (the instantiation that will run: WMAR_XR_NW4=1 selects the four-wave variant, another register / LDS footprint)
-        int nb = 0, dev = 0, cus = 0;
         const bool xr4 = getenv("WMAR_XR_NW4") != nullptr;
-        if (ok) ok = (xr4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bx_xr<BX_PER, 4>, 256, 0)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bx_xr<BX_PER / 2, 4, 8>, 512, 0)) == hipSuccess && hipGetDevice(&dev) == hipSuccess &&
-                     hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                     (long long)nb * cus >= (long long)(D / 32) * 4;
-        g->xcd_ok = ok;
+        const long long blocks = (long long)(D / 32) * 4;
+        g->xcd_ok = xcd_grouping_ok(192, 256, st) &&
+                    (xr4 ? grid_resident(k_bx_xr<BX_PER, 4>, 256, blocks) : grid_resident(k_bx_xr<BX_PER / 2, 4, 8>, 512, blocks));
         { const char* e = getenv("WMAR_INJECT_SYNC_FAIL"); g->inject_fail = (e && atoi(e) > 0) ? 1 : 0; }
     }
     if (rc != WMAR_OK) { delete g; return rc; }
@@ -873,7 +784,7 @@ static int gpt_persist_failed(wmar_gpt* g, hipStream_t st) {
     WMAR_HIP_CHECK(hipMemcpyAsync(&f, g->ss_bar + 8 * 64 + 64, 4, hipMemcpyDeviceToHost, st));
     WMAR_HIP_CHECK(hipStreamSynchronize(st));
     if (!f) return 0;
-    g->drop_graph();
+    g->gr.drop();
     WMAR_HIP_CHECK(hipMemsetAsync(g->ss_bar, 0, SS_BAR_WORDS * 4, st));
     g->persist_ok = false;
     g->fallbacks += 1;
@@ -891,7 +802,7 @@ static int gpt_sync_failed(wmar_gpt* g, hipStream_t st) {
     WMAR_HIP_CHECK(hipMemcpyAsync(f, g->xsync + 8 * 64, 8, hipMemcpyDeviceToHost, st));
     WMAR_HIP_CHECK(hipStreamSynchronize(st));
     if (!f[0] && !f[1]) return 0;
-    g->drop_graph();
+    g->gr.drop();
     WMAR_HIP_CHECK(hipMemsetAsync(g->xsync, 0, (8 * 64 + 64) * 4, st));
     g->xcd_ok = false;                  // the two-launch path from here on
     g->fallbacks += 1;
@@ -921,7 +832,7 @@ int wmar_gpt_check(wmar_gpt* g, void* stream) {
 }
 
 void wmar_gpt_destroy(wmar_gpt* g) { delete g; }
-int64_t wmar_gpt_device_bytes(const wmar_gpt* g) { return g ? g->bytes : 0; }
+int64_t wmar_gpt_device_bytes(const wmar_gpt* g) { return g ? g->mem.bytes : 0; }
 
 int wmar_gpt_decode_step(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t pos, float* logits_dev, void* stream) {
     WMAR_REQUIRE(g && tok_dev && logits_dev, "decode_step: null argument");
@@ -930,18 +841,13 @@ int wmar_gpt_decode_step(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t
     hipStream_t st = (hipStream_t)stream;
     StepIO io{(const long long*)tok_dev, 1, 0, logits_dev};
     g->att_nw = wmar_gpt::phase_waves(g->att_phase(pos + 1, B));
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    // on the fused path the call waits for the step and checks the in-launch barrier; a failed step is re-run on the two-launch
+    // path (the step is a pure function of the token, the position and the cache rows below it)
+    return run_with_fallback("decode_step: the in-launch barrier flag is up on the two-launch path", [&]() -> int {
         if (int rc = gpt_inject(g, st)) return rc;
         hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, g->pos_dev, (int)pos);
-        if (int rc = enqueue_step(g, B, io, st)) return rc;
-        // on the fused path the call waits for the step and checks the in-launch barrier; a failed step is re-run on the two-launch
-        // path (the step is a pure function of the token, the position and the cache rows below it)
-        const int f = gpt_sync_failed(g, st);
-        if (f < 0) return f;
-        if (f == 0) return WMAR_OK;
-    }
-    set_error("decode_step: the in-launch barrier flag is up on the two-launch path");
-    return WMAR_EHIP;
+        return enqueue_step(g, B, io, st);
+    }, [&] { return gpt_sync_failed(g, st); });
 }
 
 int wmar_gpt_profile_role(wmar_gpt* g, int32_t role, int64_t B, int32_t kv_len, int32_t iters, void* stream,
@@ -979,12 +885,12 @@ int wmar_gpt_profile_role(wmar_gpt* g, int32_t role, int64_t B, int32_t kv_len, 
     for (int i = 0; i < 3 && rc == WMAR_OK; ++i) rc = one(i);           // warm-up
     if (rc == WMAR_OK && hipEventRecord(g->ev0, st) != hipSuccess) rc = WMAR_EHIP;
     for (int i = 0; i < iters && rc == WMAR_OK; ++i) rc = one(i + 3);
-    if (rc == WMAR_OK && hipEventRecord(g->ev1, st) != hipSuccess) rc = WMAR_EHIP;
+    if (rc == WMAR_OK && hipEventRecord(g->gr.done, st) != hipSuccess) rc = WMAR_EHIP;
     g->span_on = was;
     if (rc) return rc;
-    WMAR_HIP_CHECK(hipEventSynchronize(g->ev1));
+    WMAR_HIP_CHECK(hipEventSynchronize(g->gr.done));
     float ms = 0.f;
-    WMAR_HIP_CHECK(hipEventElapsedTime(&ms, g->ev0, g->ev1));
+    WMAR_HIP_CHECK(hipEventElapsedTime(&ms, g->ev0, g->gr.done));
     *avg_us = (double)ms * 1000.0 / iters;
     return WMAR_OK;
 }
@@ -1012,10 +918,8 @@ int wmar_gpt_plan_info(wmar_gpt* g, int64_t B, char* buf, int64_t buf_len) {
         WMAR_REQUIRE(n > 0 && n < buf_len, "plan_info: buffer of %lld bytes too small", (long long)buf_len);
         return WMAR_OK;
     }
-    const LayerW& w = g->layers[0];
     char qkv[96], proj[160], fc1[96], fc2[96];
     const int S_in = p.S_fc2 + (p.fc2_hi > 0 ? 1 : 0);
-    (void)w;
     if (p.qkv_bx()) snprintf(qkv, sizeof qkv, "k_qkvx_bx<%d> (bf16 pipe, %d K slices)", S_in, p.S_qx);
     else if (p.S_qx > 0) snprintf(qkv, sizeof qkv, "k_qkvx<%d,%d> (fp32 MFMA, %d K slices)", p.MT, S_in, p.S_qx);
     else snprintf(qkv, sizeof qkv, "k_gemm<EPI_PACKED> (fp32 MFMA, %d K slices) after k_resid_stats", p.S_qkv);
@@ -1087,12 +991,12 @@ int wmar_gpt_debug_kv_row(wmar_gpt* g, int which, int pos, float* out) {
 int wmar_gpt_set_attention_phases(wmar_gpt* g, int32_t one_wave_upto, int32_t two_waves_upto) {
     WMAR_REQUIRE(g, "set_attention_phases: null argument");
     if (one_wave_upto < 0 && two_waves_upto < 0) {          // (-1, -1): back to the automatic schedule (batch-dependent, att_phase)
-        if (g->att_user) g->drop_graph();
+        if (g->att_user) g->gr.drop();
         g->att_t1 = 1 << 30; g->att_t2 = 1 << 30; g->att_user = false;
         return WMAR_OK;
     }
     WMAR_REQUIRE(one_wave_upto >= 0 && two_waves_upto >= one_wave_upto, "set_attention_phases: bad thresholds");
-    if (!g->att_user || g->att_t1 != one_wave_upto || g->att_t2 != two_waves_upto) g->drop_graph();
+    if (!g->att_user || g->att_t1 != one_wave_upto || g->att_t2 != two_waves_upto) g->gr.drop();
     g->att_t1 = one_wave_upto; g->att_t2 = two_waves_upto; g->att_user = true;
     return WMAR_OK;
 }
@@ -1132,11 +1036,7 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
     WMAR_HIP_CHECK(hipMemsetAsync(g->pos_dev, 0, 8, st));
 
     SampArgs a{};
-    if (wm) {
-        a.wm.table = wm->table_dev; a.wm.n_rows = wm->n_rows; a.wm.row_words = (wm->vocab_size + 31) / 32;
-        a.wm.seed_mode = wm->seed_strategy; a.wm.h = wm->context_size; a.wm.S = wm->spatial_dim;
-        a.wm.delta = wm->delta; a.wm.enabled = 1;
-    }
+    a.wm = make_wm(wm);
     a.logits = g->logits; a.V = g->V; a.past = g->past; a.past_stride = pstride;
     a.t_dev = g->step_dev;      // filled below: current length = step + 1
     a.temperature = sp->temperature; a.top_k = sp->top_k; a.use_top_p = sp->top_p >= 0;
@@ -1189,32 +1089,28 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
             if (n_need == 1 && want > 1 && steps % want == 0) gs = want;
         }
         key[1] |= (unsigned long long)gs << 32;
-        if (memcmp(key, g->graph_key, sizeof(key)) != 0) g->drop_graph();
+        if (memcmp(key, g->graph_key, sizeof(key)) != 0) g->gr.drop();
         bool have = true;
-        for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) have = have && (!need[ph] || g->exec[ph]);
+        for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) have = have && (!need[ph] || g->gr.exec[ph]);
         if (!have) {
-            g->drop_graph();
+            g->gr.drop();
             for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) {
                 if (!need[ph]) continue;          // only the phases this run passes through are captured
-                WMAR_HIP_CHECK(hipStreamBeginCapture(g->cap_stream, hipStreamCaptureModeThreadLocal));
-                int rc = WMAR_OK;
-                for (int k = 0; k < gs && rc == WMAR_OK; ++k) rc = one_step(g->cap_stream, ph);
-                hipError_t e = hipStreamEndCapture(g->cap_stream, &g->graph[ph]);
-                if (rc) { g->drop_graph(); return rc; }
-                if (e != hipSuccess) { g->drop_graph(); set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-                e = hipGraphInstantiate(&g->exec[ph], g->graph[ph], nullptr, nullptr, 0);
-                if (e != hipSuccess) { g->drop_graph(); set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+                const int rc = g->gr.capture(ph, [&](hipStream_t s) {
+                    int r = WMAR_OK;
+                    for (int k = 0; k < gs && r == WMAR_OK; ++k) r = one_step(s, ph);
+                    return r;
+                });
+                if (rc) return rc;
             }
             memcpy(g->graph_key, key, sizeof(key));
         }
-        hipError_t e = hipSuccess;
-        for (int n = 0; n < steps && e == hipSuccess; n += gs) e = hipGraphLaunch(g->exec[g->att_phase(n + 1, B)], st);
-        if (e == hipSuccess) e = hipEventRecord(g->ev1, st);   // also marks "replays finished" for drop_graph()
-        if (e == hipSuccess) { g->pending = true; }
-        if (e != hipSuccess) { set_error("graph replay failed: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+        for (int n = 0; n < steps; n += gs)
+            if (int rc = g->gr.replay(g->att_phase(n + 1, B), st)) return rc;
+        if (int rc = g->gr.replayed(st)) return rc;      // (gr.done also ends the timed span)
         { StepPlan pl(g, B, io, nullptr); if (!pl.small && pl.proj_xr) g->xr_enqueued = true; if (pl.persist) g->ps_enqueued = true; }   // a replay runs the launches of its capture
         // asynchronous: the caller's stream orders everything after the replays
-        if (g->timing) WMAR_HIP_CHECK(hipEventSynchronize(g->ev1));
+        if (g->timing) WMAR_HIP_CHECK(hipEventSynchronize(g->gr.done));
     } else {
         g->span_on = g->timing != 0;
         int rc = WMAR_OK;
@@ -1222,14 +1118,14 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
         g->span_on = false;
         if (rc) return rc;
         if (g->timing) {
-            WMAR_HIP_CHECK(hipEventRecord(g->ev1, st));
+            WMAR_HIP_CHECK(hipEventRecord(g->gr.done, st));
             WMAR_HIP_CHECK(hipStreamSynchronize(st));
             g->span_collect();
         }
     }
     if (g->timing) {
         float ms = 0;
-        WMAR_HIP_CHECK(hipEventElapsedTime(&ms, g->ev0, g->ev1));
+        WMAR_HIP_CHECK(hipEventElapsedTime(&ms, g->ev0, g->gr.done));
         g->step_ms = ms / steps;
     }
     return WMAR_OK;
@@ -1239,17 +1135,12 @@ int wmar_gpt_generate(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_sample_para
                       int64_t B, int32_t steps, const float* q_dev, int64_t* tokens_out_dev,
                       float* logits_trace_dev, void* stream) {
     WMAR_REQUIRE(g, "generate: null argument");
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (int rc = gpt_generate_once(g, wm, sp, cond_dev, B, steps, q_dev, tokens_out_dev, logits_trace_dev, stream)) return rc;
-        // While the engine runs the fused projection launch the call waits for its replays and reads the barrier flags; a run that
-        // raised one is repeated on the two-launch path (same inputs, same noise: the same tokens).  On the two-launch path the call
-        // stays asynchronous.
-        const int f = gpt_sync_failed(g, (hipStream_t)stream);
-        if (f < 0) return f;
-        if (f == 0) return WMAR_OK;
-    }
-    set_error("generate: the in-launch barrier flag is up on the two-launch path");
-    return WMAR_EHIP;
+    // While the engine runs the fused projection launch the call waits for its replays and reads the barrier flags; a run that
+    // raised one is repeated on the two-launch path (same inputs, same noise: the same tokens).  On the two-launch path the call
+    // stays asynchronous.
+    return run_with_fallback("generate: the in-launch barrier flag is up on the two-launch path",
+                             [&] { return gpt_generate_once(g, wm, sp, cond_dev, B, steps, q_dev, tokens_out_dev, logits_trace_dev, stream); },
+                             [&] { return gpt_sync_failed(g, (hipStream_t)stream); });
 }
 
 }  // extern "C"

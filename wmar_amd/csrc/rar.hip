@@ -433,26 +433,7 @@ struct wmar_rar {
                                    // wait that gave up): the two-launch pair
     int inject_fail = 0;           // WMAR_INJECT_SYNC_FAIL=1 at creation (tests): the next fused call finds the flag raised
     int fallbacks = 0;
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool pending = false;
-    void drop_graph() {
-        if (pending && ev) (void)hipEventSynchronize(ev);
-        pending = false;
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        exec = nullptr; graph = nullptr;
-    }
-    template <typename Tp>
-    int alloc(Tp** p, size_t n) { return mem.alloc(p, n); }
-    ~wmar_rar() {
-        drop_graph();
-        mem.release();
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        if (ev) (void)hipEventDestroy(ev);
-    }
+    GraphSlots<1> gr;
 };
 
 namespace {
@@ -691,39 +672,32 @@ int wmar_rar_create(const wmar_rar_config* cfg, const char* const* names, const 
     WMAR_REQUIRE(D % 32 == 0 && F % 32 == 0 && V % 32 == 0 && D <= 8192, "hidden (<=8192), intermediate and codebook sizes must be multiples of 32");
     WMAR_REQUIRE(hd == 32 || hd == 48 || hd == 64 || hd == 80 || hd == 88 || hd == 128, "head_dim %d unsupported", hd);
     WMAR_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= 64, "max_batch must be in 1..64 (rows double under guidance)");
-    TensorMap tm;
-    for (int i = 0; i < n_tensors; ++i) tm.m[names[i]] = tensors_dev[i];
+    TensorMap tm(names, tensors_dev, n_tensors);
     hipStream_t st = (hipStream_t)stream;
     auto* g = new wmar_rar();
     g->cfg = *cfg; g->D = D; g->H = H; g->hd = hd; g->V = V; g->L = L; g->F = F;
     g->T = cfg->image_seq_len + 2; g->Bmax = cfg->max_batch; g->Mmax = 2 * cfg->max_batch; g->MTmax = mt_for(g->Mmax);
     g->Ntot = (long long)6 * D * L + 2 * D;
-    int rc = WMAR_OK;
-    auto need = [&](const std::string& k) -> const float* {
-        const float* p = tm.get(k);
-        if (!p && rc == WMAR_OK) { set_error("checkpoint tensor '%s' is missing", k.c_str()); rc = WMAR_EMISSING; }
-        return p;
-    };
-#define TRY(x) do { if (rc == WMAR_OK) rc = (x); } while (0)
+    int& rc = tm.rc;
     const int nemb = V + 1 + cfg->condition_num_classes + 1;
-    const float *e = need("embeddings.weight"), *cl = need("cls_token"), *pe = need("pos_embed"),
-                *ta = need("target_aware_pos_embed"), *ts = need("timesteps_embeddings"), *hw = need("lm_head.weight"),
-                *hb = need("lm_head.bias"), *fw = need("adaln_before_head.adaLN_modulation.1.weight"),
-                *fb = need("adaln_before_head.adaLN_modulation.1.bias");
+    const float *e = tm.need("embeddings.weight"), *cl = tm.need("cls_token"), *pe = tm.need("pos_embed"),
+                *ta = tm.need("target_aware_pos_embed"), *ts = tm.need("timesteps_embeddings"), *hw = tm.need("lm_head.weight"),
+                *hb = tm.need("lm_head.bias"), *fw = tm.need("adaln_before_head.adaLN_modulation.1.weight"),
+                *fb = tm.need("adaln_before_head.adaLN_modulation.1.bias");
     if (rc == WMAR_OK) {
-        TRY(copy_vec(g, &g->emb, e, (size_t)nemb * D, st));
-        TRY(copy_vec(g, &g->cls, cl, (size_t)D, st));
-        TRY(copy_vec(g, &g->pos, pe, (size_t)(cfg->image_seq_len + 1024) * D, st));
-        TRY(copy_vec(g, &g->tape, ta, (size_t)(cfg->image_seq_len + 1024) * D, st));
-        TRY(copy_vec(g, &g->tstep, ts, (size_t)(cfg->image_seq_len + 100) * D, st));
-        TRY(g->alloc(&g->whead, (size_t)V * D / 4));
-        TRY(pack(hw, g->whead, V, D, 0, st));
-        TRY(copy_vec(g, &g->bhead, hb, (size_t)V, st));
-        TRY(g->alloc(&g->wada, (size_t)g->Ntot * D / 4));
-        TRY(g->alloc(&g->bada, (size_t)g->Ntot));
+        WMAR_TRY(copy_vec(g, &g->emb, e, (size_t)nemb * D, st));
+        WMAR_TRY(copy_vec(g, &g->cls, cl, (size_t)D, st));
+        WMAR_TRY(copy_vec(g, &g->pos, pe, (size_t)(cfg->image_seq_len + 1024) * D, st));
+        WMAR_TRY(copy_vec(g, &g->tape, ta, (size_t)(cfg->image_seq_len + 1024) * D, st));
+        WMAR_TRY(copy_vec(g, &g->tstep, ts, (size_t)(cfg->image_seq_len + 100) * D, st));
+        WMAR_TRY(g->mem.alloc(&g->whead, (size_t)V * D / 4));
+        WMAR_TRY(pack(hw, g->whead, V, D, 0, st));
+        WMAR_TRY(copy_vec(g, &g->bhead, hb, (size_t)V, st));
+        WMAR_TRY(g->mem.alloc(&g->wada, (size_t)g->Ntot * D / 4));
+        WMAR_TRY(g->mem.alloc(&g->bada, (size_t)g->Ntot));
         // WMAR_RAR_ADA_FP32=1 (A/B) keeps the per-step adaLN GEMM on the fp32-input MFMA
         g->bx_ada = D == 1280 && g->Ntot % 128 == 0 && g->MTmax >= 2 && getenv("WMAR_NO_BX") == nullptr && getenv("WMAR_RAR_ADA_FP32") == nullptr;
-        if (g->bx_ada) { TRY(g->alloc(&g->wada_bx, (size_t)g->Ntot * D / 4)); TRY(g->alloc(&g->scq, (size_t)D / 16 * 2 * 3 * 64)); }
+        if (g->bx_ada) { WMAR_TRY(g->mem.alloc(&g->wada_bx, (size_t)g->Ntot * D / 4)); WMAR_TRY(g->mem.alloc_zero(&g->scq, (size_t)D / 16 * 2 * 3 * 64, st)); }      // rows past the batch are never written
     }
     if (g->MTmax >= 4 && D % 32 == 0 && F % 32 == 0) {
         g->bx_qkv = bx_shape(3 * D / 64, D / 16); g->bx_proj = bx_shape(D / 32, D / 16); g->bx_fc2 = bx_shape(D / 64, F / 16);
@@ -736,123 +710,90 @@ int wmar_rar_create(const wmar_rar_config* cfg, const char* const* names, const 
     for (int l = 0; l < L && rc == WMAR_OK; ++l) {
         const std::string p = "blocks." + std::to_string(l) + ".";
         RarLayer& w = g->layers[l];
-        const float *qw = need(p + "attn.qkv.weight"), *qb = need(p + "attn.qkv.bias"), *pw = need(p + "attn.proj.weight"),
-                    *pb = need(p + "attn.proj.bias"), *f1w = need(p + "mlp.fc1.weight"), *f1b = need(p + "mlp.fc1.bias"),
-                    *f2w = need(p + "mlp.fc2.weight"), *f2b = need(p + "mlp.fc2.bias"), *n1w = need(p + "norm1.weight"),
-                    *n1b = need(p + "norm1.bias"), *n2w = need(p + "norm2.weight"), *n2b = need(p + "norm2.bias"),
-                    *qnw = need(p + "attn.q_norm.weight"), *qnb = need(p + "attn.q_norm.bias"),
-                    *knw = need(p + "attn.k_norm.weight"), *knb = need(p + "attn.k_norm.bias"),
-                    *aw = need(p + "adaLN_modulation.1.weight"), *ab = need(p + "adaLN_modulation.1.bias");
+        const float *qw = tm.need(p + "attn.qkv.weight"), *qb = tm.need(p + "attn.qkv.bias"), *pw = tm.need(p + "attn.proj.weight"),
+                    *pb = tm.need(p + "attn.proj.bias"), *f1w = tm.need(p + "mlp.fc1.weight"), *f1b = tm.need(p + "mlp.fc1.bias"),
+                    *f2w = tm.need(p + "mlp.fc2.weight"), *f2b = tm.need(p + "mlp.fc2.bias"), *n1w = tm.need(p + "norm1.weight"),
+                    *n1b = tm.need(p + "norm1.bias"), *n2w = tm.need(p + "norm2.weight"), *n2b = tm.need(p + "norm2.bias"),
+                    *qnw = tm.need(p + "attn.q_norm.weight"), *qnb = tm.need(p + "attn.q_norm.bias"),
+                    *knw = tm.need(p + "attn.k_norm.weight"), *knb = tm.need(p + "attn.k_norm.bias"),
+                    *aw = tm.need(p + "adaLN_modulation.1.weight"), *ab = tm.need(p + "adaLN_modulation.1.bias");
         if (rc != WMAR_OK) break;
-        TRY(g->alloc(&w.wqkv, (size_t)3 * D * D / 4)); TRY(pack(qw, w.wqkv, 3 * D, D, 0, st));
-        TRY(copy_vec(g, &w.bqkv, qb, (size_t)3 * D, st));
-        TRY(g->alloc(&w.wproj, (size_t)D * D / 4)); TRY(pack(pw, w.wproj, D, D, 0, st));
-        TRY(copy_vec(g, &w.bproj, pb, (size_t)D, st));
-        TRY(g->alloc(&w.wfc1, (size_t)F * D / 4)); TRY(pack(f1w, w.wfc1, F, D, 0, st));
-        TRY(copy_vec(g, &w.bfc1, f1b, (size_t)F, st));
-        TRY(g->alloc(&w.wfc2, (size_t)F * D / 4)); TRY(pack(f2w, w.wfc2, D, F, 0, st));
-        TRY(copy_vec(g, &w.bfc2, f2b, (size_t)D, st));
+        WMAR_TRY(g->mem.alloc(&w.wqkv, (size_t)3 * D * D / 4)); WMAR_TRY(pack(qw, w.wqkv, 3 * D, D, 0, st));
+        WMAR_TRY(copy_vec(g, &w.bqkv, qb, (size_t)3 * D, st));
+        WMAR_TRY(g->mem.alloc(&w.wproj, (size_t)D * D / 4)); WMAR_TRY(pack(pw, w.wproj, D, D, 0, st));
+        WMAR_TRY(copy_vec(g, &w.bproj, pb, (size_t)D, st));
+        WMAR_TRY(g->mem.alloc(&w.wfc1, (size_t)F * D / 4)); WMAR_TRY(pack(f1w, w.wfc1, F, D, 0, st));
+        WMAR_TRY(copy_vec(g, &w.bfc1, f1b, (size_t)F, st));
+        WMAR_TRY(g->mem.alloc(&w.wfc2, (size_t)F * D / 4)); WMAR_TRY(pack(f2w, w.wfc2, D, F, 0, st));
+        WMAR_TRY(copy_vec(g, &w.bfc2, f2b, (size_t)D, st));
         if (g->bx_ok) {
-            auto pack_bx = [&](const float* W, float4* Wq, int N, int K) -> int {
-                const long long total = (long long)(N / 32) * (K / 16) * 128;
-                hipLaunchKernelGGL(k_pack_bx, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, (const float*)nullptr, Wq, N, K, 0);
-                return launch_status("k_pack_bx");
-            };
-            TRY(g->alloc(&w.wqkv_bx, (size_t)3 * D * D / 4)); TRY(pack_bx(qw, w.wqkv_bx, 3 * D, D));
-            TRY(g->alloc(&w.wproj_bx, (size_t)D * D / 4)); TRY(pack_bx(pw, w.wproj_bx, D, D));
-            TRY(g->alloc(&w.wfc2_bx, (size_t)F * D / 4)); TRY(pack_bx(f2w, w.wfc2_bx, D, F));
-            if (g->bx_fc1) { TRY(g->alloc(&w.wfc1_bx, (size_t)F * D / 4)); TRY(pack_bx(f1w, w.wfc1_bx, F, D)); }
+            WMAR_TRY(g->mem.alloc(&w.wqkv_bx, (size_t)3 * D * D / 4)); WMAR_TRY(pack_bx(qw, nullptr, w.wqkv_bx, 3 * D, D, 0, st));
+            WMAR_TRY(g->mem.alloc(&w.wproj_bx, (size_t)D * D / 4)); WMAR_TRY(pack_bx(pw, nullptr, w.wproj_bx, D, D, 0, st));
+            WMAR_TRY(g->mem.alloc(&w.wfc2_bx, (size_t)F * D / 4)); WMAR_TRY(pack_bx(f2w, nullptr, w.wfc2_bx, D, F, 0, st));
+            if (g->bx_fc1) { WMAR_TRY(g->mem.alloc(&w.wfc1_bx, (size_t)F * D / 4)); WMAR_TRY(pack_bx(f1w, nullptr, w.wfc1_bx, F, D, 0, st)); }
         }
-        TRY(copy_vec(g, &w.n1w, n1w, (size_t)D, st)); TRY(copy_vec(g, &w.n1b, n1b, (size_t)D, st));
-        TRY(copy_vec(g, &w.n2w, n2w, (size_t)D, st)); TRY(copy_vec(g, &w.n2b, n2b, (size_t)D, st));
-        TRY(copy_vec(g, &w.qnw, qnw, (size_t)hd, st)); TRY(copy_vec(g, &w.qnb, qnb, (size_t)hd, st));
-        TRY(copy_vec(g, &w.knw, knw, (size_t)hd, st)); TRY(copy_vec(g, &w.knb, knb, (size_t)hd, st));
+        WMAR_TRY(copy_vec(g, &w.n1w, n1w, (size_t)D, st)); WMAR_TRY(copy_vec(g, &w.n1b, n1b, (size_t)D, st));
+        WMAR_TRY(copy_vec(g, &w.n2w, n2w, (size_t)D, st)); WMAR_TRY(copy_vec(g, &w.n2b, n2b, (size_t)D, st));
+        WMAR_TRY(copy_vec(g, &w.qnw, qnw, (size_t)hd, st)); WMAR_TRY(copy_vec(g, &w.qnb, qnb, (size_t)hd, st));
+        WMAR_TRY(copy_vec(g, &w.knw, knw, (size_t)hd, st)); WMAR_TRY(copy_vec(g, &w.knb, knb, (size_t)hd, st));
         // this block's 6d adaLN rows go to their slice of the one big modulation GEMM
-        TRY(pack(aw, g->wada, 6 * D, D, l * (6 * D / 32), st));
-        if (g->bx_ada && rc == WMAR_OK) {
-            const long long total = (long long)(6 * D / 32) * (D / 16) * 128;
-            hipLaunchKernelGGL(k_pack_bx, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, aw, (const float*)nullptr, g->wada_bx, 6 * D, D, l * (6 * D / 32));
-            rc = launch_status("k_pack_bx");
-        }
+        WMAR_TRY(pack(aw, g->wada, 6 * D, D, l * (6 * D / 32), st));
+        if (g->bx_ada) WMAR_TRY(pack_bx(aw, nullptr, g->wada_bx, 6 * D, D, l * (6 * D / 32), st));
         if (rc == WMAR_OK && hipMemcpyAsync(g->bada + (size_t)l * 6 * D, ab, (size_t)6 * D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
             set_error("adaLN bias copy failed"); rc = WMAR_EHIP;
         }
     }
     if (rc == WMAR_OK) {
-        TRY(pack(fw, g->wada, 2 * D, D, L * (6 * D / 32), st));
-        if (g->bx_ada && rc == WMAR_OK) {
-            const long long total = (long long)(2 * D / 32) * (D / 16) * 128;
-            hipLaunchKernelGGL(k_pack_bx, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, fw, (const float*)nullptr, g->wada_bx, 2 * D, D, L * (6 * D / 32));
-            rc = launch_status("k_pack_bx");
-        }
+        WMAR_TRY(pack(fw, g->wada, 2 * D, D, L * (6 * D / 32), st));
+        if (g->bx_ada) WMAR_TRY(pack_bx(fw, nullptr, g->wada_bx, 2 * D, D, L * (6 * D / 32), st));
         if (rc == WMAR_OK && hipMemcpyAsync(g->bada + (size_t)L * 6 * D, fb, (size_t)2 * D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
             set_error("final adaLN bias copy failed"); rc = WMAR_EHIP;
         }
     }
     const size_t Mpad = (size_t)g->MTmax * 32;
-    TRY(g->alloc(&g->x, Mpad * D / 4));
-    TRY(g->alloc(&g->h, Mpad * D / 4));
-    TRY(g->alloc(&g->y, Mpad * D / 4));
-    TRY(g->alloc(&g->sc, Mpad * D / 4));
-    TRY(g->alloc(&g->hbuf, Mpad * F / 4));
-    TRY(g->alloc(&g->slabs, (size_t)MAX_SLABS * Mpad * D / 4));
-    TRY(g->alloc(&g->qkv_slabs, (size_t)(g->bx_ok ? g->bx_qkv.S : 1) * Mpad * 3 * D / 4));
+    WMAR_TRY(g->mem.alloc_zero(&g->x, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->h, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->y, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->sc, Mpad * D / 4, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->hbuf, Mpad * F / 4, st));
+    WMAR_TRY(g->mem.alloc(&g->slabs, (size_t)MAX_SLABS * Mpad * D / 4));
+    WMAR_TRY(g->mem.alloc(&g->qkv_slabs, (size_t)(g->bx_ok ? g->bx_qkv.S : 1) * Mpad * 3 * D / 4));
     if (g->bx_ok) {
-        TRY(g->alloc(&g->xq, (size_t)D / 16 * 4 * 3 * 64));
-        TRY(g->alloc(&g->yq, (size_t)D / 16 * 4 * 3 * 64));
-        TRY(g->alloc(&g->hq, (size_t)F / 16 * 4 * 3 * 64));
-        if (rc == WMAR_OK && hipMemsetAsync(g->yq, 0, (size_t)D / 16 * 4 * 3 * 64 * 16, st) != hipSuccess) { set_error("rar_create: memset failed"); rc = WMAR_EHIP; }
+        WMAR_TRY(g->mem.alloc(&g->xq, (size_t)D / 16 * 4 * 3 * 64));
+        WMAR_TRY(g->mem.alloc_zero(&g->yq, (size_t)D / 16 * 4 * 3 * 64, st));
+        WMAR_TRY(g->mem.alloc(&g->hq, (size_t)F / 16 * 4 * 3 * 64));
     }
-    TRY(g->alloc(&g->mod, Mpad * (size_t)g->Ntot));
-    TRY(g->alloc(&g->mod_u, (size_t)((g->T + 31) / 32) * 32 * (size_t)g->Ntot));
-    TRY(g->alloc(&g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2));
+    WMAR_TRY(g->mem.alloc_zero(&g->mod, Mpad * (size_t)g->Ntot, st));
+    WMAR_TRY(g->mem.alloc(&g->mod_u, (size_t)((g->T + 31) / 32) * 32 * (size_t)g->Ntot));
+    WMAR_TRY(g->mem.alloc(&g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2));
     const size_t kv = (size_t)L * g->Mmax * H * g->T * hd;
-    TRY(g->alloc(&g->kcache, kv));
-    TRY(g->alloc(&g->vcache, kv));
-    TRY(g->alloc(&g->logits, (size_t)g->Mmax * V));
-    TRY(g->alloc(&g->scratch, (size_t)g->Bmax * V));
-    TRY(g->alloc(&g->cfg_scale, (size_t)cfg->image_seq_len));
-    TRY(g->alloc(&g->ids, (size_t)g->Bmax * cfg->image_seq_len));
-    TRY(g->alloc(&g->cond_ids, (size_t)g->Mmax));
-    TRY(g->alloc(&g->ctr, 4));
+    WMAR_TRY(g->mem.alloc_zero(&g->kcache, kv, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->vcache, kv, st));
+    WMAR_TRY(g->mem.alloc(&g->logits, (size_t)g->Mmax * V));
+    WMAR_TRY(g->mem.alloc(&g->scratch, (size_t)g->Bmax * V));
+    WMAR_TRY(g->mem.alloc(&g->cfg_scale, (size_t)cfg->image_seq_len));
+    WMAR_TRY(g->mem.alloc_zero(&g->ids, (size_t)g->Bmax * cfg->image_seq_len, st));
+    WMAR_TRY(g->mem.alloc_zero(&g->cond_ids, (size_t)g->Mmax, st));
+    WMAR_TRY(g->mem.alloc(&g->ctr, 4));
     { const int kbd = D / 8, kpw = kbd <= 256 ? 1 : 4; g->part_site = (size_t)((kbd + 4 * kpw - 1) / (4 * kpw)) * g->MTmax * 32 * 2; }
-    TRY(g->alloc(&g->part, (size_t)2 * L * g->part_site));
-    TRY(g->alloc(&g->sync_fail, 4));
-    if (rc == WMAR_OK && hipMemsetAsync(g->sync_fail, 0, 16, st) != hipSuccess) { set_error("rar_create: memset failed"); rc = WMAR_EHIP; }
+    WMAR_TRY(g->mem.alloc(&g->part, (size_t)2 * L * g->part_site));
+    WMAR_TRY(g->mem.alloc_zero(&g->sync_fail, 4, st));
     if (rc == WMAR_OK) {
         // k_resid_mod's workgroups wait for each other's partial sums inside ONE launch: every workgroup of its grid (chunks x row
         // tiles, at most 64 x 4) must be resident at the same time.  Checked here against what the device can hold (the occupancy
         // the runtime reports for the widest instantiation x the compute units it exposes -- a CU mask or a partition mode shrinks
         // it); a device that cannot runs the two-launch pair (k_resid_mod<., ., 1> + <., ., 2>: same results) from the start.  A
         // wait that gives up at run time raises sync_fail: the call is then repeated on the two-launch pair (rar_sync_failed).
-        int nb = 0, dev = 0, cus = 0;
-        hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_resid_mod<8, 4, 0>, 256, 0);
-        if (e1 == hipSuccess) e1 = hipGetDevice(&dev);
-        if (e1 == hipSuccess) e1 = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         const int kbd = D / 8, kpw = kbd <= 256 ? 1 : 4;
         const long long need = (long long)((kbd + 4 * kpw - 1) / (4 * kpw)) * g->MTmax;
-        if (e1 != hipSuccess) { set_error("rar_create: occupancy query failed: %s", hipGetErrorString(e1)); rc = WMAR_EHIP; }
-        else g->rm_fused = (long long)nb * cus >= need && getenv("WMAR_NO_XR") == nullptr;
+        g->rm_fused = grid_resident(k_resid_mod<8, 4, 0>, 256, need) && getenv("WMAR_NO_XR") == nullptr;
         { const char* e = getenv("WMAR_INJECT_SYNC_FAIL"); g->inject_fail = (e && atoi(e) > 0) ? 1 : 0; }
     }
+    WMAR_TRY(g->gr.init());
     if (rc == WMAR_OK) {
-        hipError_t er = hipMemsetAsync(g->x, 0, Mpad * D * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->h, 0, Mpad * D * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->y, 0, Mpad * D * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->sc, 0, Mpad * D * 4, st);
-        if (er == hipSuccess && g->scq) er = hipMemsetAsync(g->scq, 0, (size_t)D / 16 * 2 * 3 * 64 * 16, st);      // rows past the batch are never written
-        if (er == hipSuccess) er = hipMemsetAsync(g->hbuf, 0, Mpad * F * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->mod, 0, Mpad * (size_t)g->Ntot * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->kcache, 0, kv * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->vcache, 0, kv * 4, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->ids, 0, (size_t)g->Bmax * cfg->image_seq_len * 8, st);
-        if (er == hipSuccess) er = hipMemsetAsync(g->cond_ids, 0, (size_t)g->Mmax * 8, st);
-        if (er == hipSuccess) er = hipStreamCreateWithFlags(&g->cap_stream, hipStreamNonBlocking);
-        if (er == hipSuccess) er = hipEventCreate(&g->ev);
-        if (er == hipSuccess) er = hipStreamSynchronize(st);
+        const hipError_t er = hipStreamSynchronize(st);
         if (er != hipSuccess) { set_error("rar_create: %s", hipGetErrorString(er)); rc = WMAR_EHIP; }
     }
-#undef TRY
     if (rc != WMAR_OK) { delete g; return rc; }
     *out = g;
     return WMAR_OK;
@@ -873,7 +814,7 @@ static int rar_sync_failed(wmar_rar* g, hipStream_t st, bool always = false) {
     WMAR_HIP_CHECK(hipStreamSynchronize(st));
     if (!f) return 0;
     if (!g->rm_fused) { WMAR_HIP_CHECK(hipMemsetAsync(g->sync_fail, 0, 4, st)); return 2; }
-    g->drop_graph();
+    g->gr.drop();
     WMAR_HIP_CHECK(hipMemsetAsync(g->sync_fail, 0, 4, st));
     g->rm_fused = false;
     g->fallbacks += 1;
@@ -916,20 +857,15 @@ int wmar_rar_forward_position(wmar_rar* g, const int64_t* tok_dev, const int64_t
     WMAR_REQUIRE(M >= 1 && M <= g->Mmax, "rar_forward_position: rows %lld outside 1..%d", (long long)M, g->Mmax);
     WMAR_REQUIRE(pos >= 0 && pos < g->T, "rar_forward_position: position %d outside 0..%d", pos, g->T - 1);
     hipStream_t st = (hipStream_t)stream;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    // on the fused path the call waits for the position and checks the in-launch waits; a failed position is repeated on the
+    // two-launch pair (a pure function of the tokens, the position and the cache rows below it)
+    return run_with_fallback("rar_forward_position: the in-launch wait flag is up on the two-launch pair", [&]() -> int {
         if (int rc = rar_inject(g, st)) return rc;
         WMAR_HIP_CHECK(hipMemcpyAsync(g->cond_ids, cond_ids_dev, (size_t)M * 8, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, (int)pos, 0, 0);
         RarPlan p(g, (int)M, (int)M, (const long long*)tok_dev, st);
-        if (int rc = p.position(true, logits_dev)) return rc;
-        // on the fused path the call waits for the position and checks the in-launch waits; a failed position is repeated on the
-        // two-launch pair (a pure function of the tokens, the position and the cache rows below it)
-        const int f = rar_sync_failed(g, st);
-        if (f < 0) return f;
-        if (f == 0) return WMAR_OK;
-    }
-    set_error("rar_forward_position: the in-launch wait flag is up on the two-launch pair");
-    return WMAR_EHIP;
+        return p.position(true, logits_dev);
+    }, [&] { return rar_sync_failed(g, st); });
 }
 
 static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,
@@ -943,7 +879,7 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
     hipStream_t st = (hipStream_t)stream;
     const int L = g->cfg.image_seq_len, V = g->V;
     const int M = use_guidance ? 2 * (int)B : (int)B;
-    g->drop_graph();
+    g->gr.drop();
     if (int rc = rar_inject(g, st)) return rc;
     // condition ids: class + codebook_size + 1, unconditional rows get the "none" id (rar.py:303-312)
     std::vector<long long> hc((size_t)B);
@@ -1007,20 +943,17 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
         return launch_status("k_advance3");
     };
     if (use_graph) {
-        WMAR_HIP_CHECK(hipStreamBeginCapture(g->cap_stream, hipStreamCaptureModeThreadLocal));
         // groups of four positions per captured graph (the seam between two replays is ~10 us, gpt.hip)
         const int gs = (L % 4 == 0) ? 4 : 1;
-        int rc = WMAR_OK;
-        for (int k = 0; k < gs && rc == WMAR_OK; ++k) rc = one_step(g->cap_stream);
-        hipError_t e = hipStreamEndCapture(g->cap_stream, &g->graph);
-        if (rc) { g->drop_graph(); return rc; }
-        if (e != hipSuccess) { g->drop_graph(); set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-        e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-        if (e != hipSuccess) { g->drop_graph(); set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-        for (int n = 0; n < L && e == hipSuccess; n += gs) e = hipGraphLaunch(g->exec, st);
-        if (e == hipSuccess) e = hipEventRecord(g->ev, st);
-        if (e != hipSuccess) { set_error("graph replay failed: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-        g->pending = true;
+        const int rc = g->gr.capture(0, [&](hipStream_t s) {
+            int r = WMAR_OK;
+            for (int k = 0; k < gs && r == WMAR_OK; ++k) r = one_step(s);
+            return r;
+        });
+        if (rc) return rc;
+        for (int n = 0; n < L; n += gs)
+            if (int r = g->gr.replay(0, st)) return r;
+        if (int r = g->gr.replayed(st)) return r;
     } else {
         for (int n = 0; n < L; ++n)
             if (int rc = one_step(st)) return rc;
@@ -1033,17 +966,12 @@ static int rar_generate_impl(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
                              const float* log_rs_dev, float top_p, int32_t top_k,
                              int64_t* tokens_out_dev, int32_t use_graph, void* stream) {
     WMAR_REQUIRE(g, "rar_generate: null argument");
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (int rc = rar_generate_once(g, wm, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, log_rs_dev, top_p, top_k,
-                                       tokens_out_dev, use_graph, stream)) return rc;
-        // on the fused path the call waits for its replays and reads the wait flag; a run that raised it is repeated on the
-        // two-launch pair (same inputs, same noise: the same tokens)
-        const int f = rar_sync_failed(g, (hipStream_t)stream);
-        if (f < 0) return f;
-        if (f == 0) return WMAR_OK;
-    }
-    set_error("rar_generate: the in-launch wait flag is up on the two-launch pair");
-    return WMAR_EHIP;
+    // on the fused path the call waits for its replays and reads the wait flag; a run that raised it is repeated on the
+    // two-launch pair (same inputs, same noise: the same tokens)
+    return run_with_fallback("rar_generate: the in-launch wait flag is up on the two-launch pair", [&] {
+        return rar_generate_once(g, wm, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, log_rs_dev, top_p, top_k,
+                                 tokens_out_dev, use_graph, stream);
+    }, [&] { return rar_sync_failed(g, (hipStream_t)stream); });
 }
 
 int wmar_rar_generate(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,

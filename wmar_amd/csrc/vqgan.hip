@@ -1017,8 +1017,7 @@ struct AttnW { NormW n; ConvW q, k, v, proj; };
 
 struct wmar_vq {
     wmar_vq_config cfg{};
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
+    DeviceArena mem;
     int Bmax = 0, S = 0;
     // decoder
     ConvW post_quant, d_conv_in, d_conv_out;
@@ -1046,21 +1045,6 @@ struct wmar_vq {
     double* gn_tiles = nullptr; long long gn_tiles_cap = 0;   // per-tile GroupNorm partial sums written by conv epilogues
     float* znorm = nullptr;
     unsigned long long* vqbest = nullptr;      // packed (distance, code) winners of k_vq_argmin_split
-
-    template <typename T>
-    int alloc(T** p, size_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) {
-            set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            return WMAR_ENOMEM;
-        }
-        allocs.push_back(q);
-        bytes += (int64_t)(n * sizeof(T));
-        *p = (T*)q;
-        return WMAR_OK;
-    }
-    ~wmar_vq() { for (void* p : allocs) (void)hipFree(p); }
 };
 
 namespace {
@@ -1069,41 +1053,17 @@ constexpr int GN_CHUNKS_MAX = 64;
 constexpr int GN_MR_DOUBLES = 32768;   // head of the GroupNorm scratch: (mean, rstd) float2 per [image][32 groups], up to 1024 images
 inline int pad8(int c) { return (c + 7) & ~7; }
 
-struct ArenaRef {   // the engine that owns the allocations
-    std::vector<void*>* allocs;
-    int64_t* bytes;
-    template <typename T>
-    int alloc(T** p, size_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) {
-            set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            return WMAR_ENOMEM;
-        }
-        allocs->push_back(q);
-        *bytes += (int64_t)(n * sizeof(T));
-        *p = (T*)q;
-        return WMAR_OK;
-    }
-};
-
-struct Loader {
-    std::map<std::string, const void*> m;
-    ArenaRef* v;
+// Loads convolutions and norms of a checkpoint into the owning engine's arena; shares the lookup's sticky `rc`.
+struct Loader : TensorMap {
+    DeviceArena* v;
     hipStream_t st;
-    int rc = WMAR_OK;
-    const float* need(const std::string& k) {
-        auto it = m.find(k);
-        if (it == m.end()) {
-            if (rc == WMAR_OK) { set_error("checkpoint tensor '%s' is missing", k.c_str()); rc = WMAR_EMISSING; }
-            return nullptr;
-        }
-        return (const float*)it->second;
-    }
+    Loader(const char* const* names, const void* const* tensors_dev, int n, DeviceArena* v_, hipStream_t st_)
+        : TensorMap(names, tensors_dev, n), v(v_), st(st_) {}
     // has_bias = false: bias-free conv (MaskGIT-VQGAN ResnetBlock / encoder conv_in) -> zero bias
     void conv(const std::string& p, int cin, int cout, int ks, ConvW& c, bool has_bias = true) {
         const float* W = need(p + ".weight");
-        const float* bsrc = has_bias ? need(p + ".bias") : nullptr;
+        const float* bsrc = nullptr;
+        if (has_bias) bsrc = need(p + ".bias");
         if (rc) return;
         c.cin = cin; c.cout = cout; c.ks = ks; c.cin_s = pad8(cin); c.cout_s = pad8(cout);
         c.CT = (cout + 31) / 32; c.KBc = c.cin_s / 8;
@@ -1384,10 +1344,7 @@ int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const vo
     WMAR_REQUIRE(S >= 8 && S % 8 == 0 && (S << (L - 1)) == cfg->resolution, "latent size %d must be a multiple of 8", S);
     auto* v = new wmar_vq();
     v->cfg = *cfg; v->Bmax = cfg->max_batch; v->S = S;
-    ArenaRef arena{&v->allocs, &v->bytes};
-    Loader ld;
-    ld.v = &arena; ld.st = (hipStream_t)stream;
-    for (int i = 0; i < n_tensors; ++i) ld.m[names[i]] = tensors_dev[i];
+    Loader ld(names, tensors_dev, n_tensors, &v->mem, (hipStream_t)stream);
     const int ch = cfg->ch, z = cfg->z_channels, E = cfg->embed_dim;
 
     // ---- decoder (model.py:437-505)
@@ -1450,17 +1407,15 @@ int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const vo
     ld.conv("quant_conv", z, E, 1, v->quant);
 
     // ---- quantizer
-    int rc = ld.rc;
     const float* emb = ld.need("quantize.embedding.weight");
-    rc = ld.rc;
+    int& rc = ld.rc;
     hipStream_t st = (hipStream_t)stream;
-#define TRY(x) do { if (rc == WMAR_OK) rc = (x); } while (0)
-    TRY(v->alloc(&v->emb, (size_t)cfg->n_embed * E));
+    WMAR_TRY(v->mem.alloc(&v->emb, (size_t)cfg->n_embed * E));
     if (rc == WMAR_OK && hipMemcpyAsync(v->emb, emb, (size_t)cfg->n_embed * E * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("embedding copy failed"); rc = WMAR_EHIP;
     }
-    TRY(v->alloc(&v->emb_p, (size_t)cfg->n_embed * E / 4));
-    TRY(v->alloc(&v->enorm, (size_t)cfg->n_embed));
+    WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)cfg->n_embed * E / 4));
+    WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)cfg->n_embed));
     if (rc == WMAR_OK) {
         // the codebook as a 1x1 "conv" weight [n_embed][E]: same fragment packing
         size_t n = (size_t)(cfg->n_embed / 32) * (E / 8) * 64;
@@ -1485,7 +1440,7 @@ int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const vo
         if (el0 > maxel) maxel = el0;
     }
     v->buf_elems = maxel * v->Bmax;
-    for (int i = 0; i < 4; ++i) TRY(v->alloc(&v->buf[i], v->buf_elems));
+    for (int i = 0; i < 4; ++i) WMAR_TRY(v->mem.alloc(&v->buf[i], v->buf_elems));
     const int cattn = ch * cfg->ch_mult[L - 1];
     // attention scratch sized for the largest attention resolution
     int amax = 0;
@@ -1495,32 +1450,30 @@ int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const vo
     int cam = 0;
     for (int lvl = 0; lvl < L; ++lvl) cam = ch * cfg->ch_mult[lvl] > cam ? ch * cfg->ch_mult[lvl] : cam;
     (void)cattn;
-    TRY(v->alloc(&v->aq, (size_t)v->Bmax * ntok * cam));
-    TRY(v->alloc(&v->ak, (size_t)v->Bmax * ntok * cam));
-    TRY(v->alloc(&v->av, (size_t)v->Bmax * ntok * cam));
-    TRY(v->alloc(&v->ao, (size_t)v->Bmax * ntok * cam));
-    TRY(v->alloc(&v->asc, (size_t)v->Bmax * ntok * ntok));
+    WMAR_TRY(v->mem.alloc(&v->aq, (size_t)v->Bmax * ntok * cam));
+    WMAR_TRY(v->mem.alloc(&v->ak, (size_t)v->Bmax * ntok * cam));
+    WMAR_TRY(v->mem.alloc(&v->av, (size_t)v->Bmax * ntok * cam));
+    WMAR_TRY(v->mem.alloc(&v->ao, (size_t)v->Bmax * ntok * cam));
+    WMAR_TRY(v->mem.alloc(&v->asc, (size_t)v->Bmax * ntok * ntok));
     if (ntok % 32 == 0 && cam % 32 == 0) {
-        TRY(v->alloc(&v->attk, (size_t)v->Bmax * ntok * cam * 3 / 8));     // 3 pieces x 2 bytes per element, in 16-byte units
-        TRY(v->alloc(&v->attv, (size_t)v->Bmax * ntok * cam * 3 / 8));
+        WMAR_TRY(v->mem.alloc(&v->attk, (size_t)v->Bmax * ntok * cam * 3 / 8));     // 3 pieces x 2 bytes per element, in 16-byte units
+        WMAR_TRY(v->mem.alloc(&v->attv, (size_t)v->Bmax * ntok * cam * 3 / 8));
         const size_t nz = ntok > (size_t)cam ? ntok : (size_t)cam;
-        TRY(v->alloc(&v->zbias, nz));
-        if (rc == WMAR_OK && hipMemsetAsync(v->zbias, 0, nz * 4, st) != hipSuccess) { set_error("vq_create: memset failed"); rc = WMAR_EHIP; }
+        WMAR_TRY(v->mem.alloc_zero(&v->zbias, nz, st));
     }
-    TRY(v->alloc(&v->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)v->Bmax * GN_CHUNKS_MAX * 32 * 2));
+    WMAR_TRY(v->mem.alloc(&v->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)v->Bmax * GN_CHUNKS_MAX * 32 * 2));
     v->gn_tiles_cap = (long long)v->Bmax * (cfg->resolution / 8) * (cfg->resolution / 8) * 64;
-    TRY(v->alloc(&v->gn_tiles, (size_t)v->gn_tiles_cap));
-    TRY(v->alloc(&v->znorm, (size_t)v->Bmax * S * S));
-    TRY(v->alloc(&v->vqbest, (size_t)v->Bmax * S * S));
+    WMAR_TRY(v->mem.alloc(&v->gn_tiles, (size_t)v->gn_tiles_cap));
+    WMAR_TRY(v->mem.alloc(&v->znorm, (size_t)v->Bmax * S * S));
+    WMAR_TRY(v->mem.alloc(&v->vqbest, (size_t)v->Bmax * S * S));
     if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("vq_create: sync failed"); rc = WMAR_EHIP; }
-#undef TRY
     if (rc != WMAR_OK) { delete v; return rc; }
     *out = v;
     return WMAR_OK;
 }
 
 void wmar_vq_destroy(wmar_vq* v) { delete v; }
-int64_t wmar_vq_device_bytes(const wmar_vq* v) { return v ? v->bytes : 0; }
+int64_t wmar_vq_device_bytes(const wmar_vq* v) { return v ? v->mem.bytes : 0; }
 
 int wmar_vq_decode(wmar_vq* v, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream) {
     WMAR_REQUIRE(v && codes_dev && images_dev, "vq_decode: null argument");
@@ -1667,8 +1620,7 @@ __global__ void k_nhwc_to_nchw_01(const float* __restrict__ src, float* __restri
 
 struct wmar_mvq {
     wmar_mvq_config cfg{};
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
+    DeviceArena mem;
     int Bmax = 0, S = 0;
     ConvW d_conv_in, d_conv_out, e_conv_in, e_conv_out;
     std::vector<ResW> d_mid, e_mid;
@@ -1681,7 +1633,6 @@ struct wmar_mvq {
     double* gn_tiles = nullptr; long long gn_tiles_cap = 0;   // per-tile GroupNorm partial sums written by conv epilogues
     float* znorm = nullptr;
     unsigned long long* vqbest = nullptr;      // packed (distance, code) winners of k_vq_argmin_split
-    ~wmar_mvq() { for (void* p : allocs) (void)hipFree(p); }
 };
 
 namespace {
@@ -1729,10 +1680,7 @@ int wmar_mvq_create(const wmar_mvq_config* cfg, const char* const* names, const 
     WMAR_REQUIRE(S >= 8 && S % 8 == 0 && (S << (R - 1)) == cfg->resolution, "latent size %d must be a multiple of 8", S);
     auto* v = new wmar_mvq();
     v->cfg = *cfg; v->Bmax = cfg->max_batch; v->S = S;
-    ArenaRef arena{&v->allocs, &v->bytes};
-    Loader ld;
-    ld.v = &arena; ld.st = (hipStream_t)stream;
-    for (int i = 0; i < n_tensors; ++i) ld.m[names[i]] = tensors_dev[i];
+    Loader ld(names, tensors_dev, n_tensors, &v->mem, (hipStream_t)stream);
     const int mid = hc * cfg->channel_mult[R - 1];
     // decoder (maskgit_vqgan.py:197-245)
     ld.conv("decoder.conv_in", z, mid, 3, v->d_conv_in);
@@ -1768,15 +1716,14 @@ int wmar_mvq_create(const wmar_mvq_config* cfg, const char* const* names, const 
     ld.norm("encoder.norm_out", mid, v->e_norm_out);
     ld.conv("encoder.conv_out", mid, z, 1, v->e_conv_out);
     const float* emb = ld.need("quantize.embedding.weight");
-    int rc = ld.rc;
+    int& rc = ld.rc;
     hipStream_t st = (hipStream_t)stream;
-#define TRY(x) do { if (rc == WMAR_OK) rc = (x); } while (0)
-    TRY(arena.alloc(&v->emb, (size_t)cfg->num_embeddings * z));
+    WMAR_TRY(v->mem.alloc(&v->emb, (size_t)cfg->num_embeddings * z));
     if (rc == WMAR_OK && hipMemcpyAsync(v->emb, emb, (size_t)cfg->num_embeddings * z * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("embedding copy failed"); rc = WMAR_EHIP;
     }
-    TRY(arena.alloc(&v->emb_p, (size_t)cfg->num_embeddings * z / 4));
-    TRY(arena.alloc(&v->enorm, (size_t)cfg->num_embeddings));
+    WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)cfg->num_embeddings * z / 4));
+    WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)cfg->num_embeddings));
     if (rc == WMAR_OK) {
         size_t n = (size_t)(cfg->num_embeddings / 32) * (z / 8) * 64;
         hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, emb, v->emb_p, cfg->num_embeddings, z, 1,
@@ -1797,21 +1744,20 @@ int wmar_mvq_create(const wmar_mvq_config* cfg, const char* const* names, const 
             r /= 2;
         }
     }
-    for (int i = 0; i < 4; ++i) TRY(arena.alloc(&v->buf[i], maxel * v->Bmax));
-    TRY(arena.alloc(&v->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)v->Bmax * GN_CHUNKS_MAX * 32 * 2));
+    for (int i = 0; i < 4; ++i) WMAR_TRY(v->mem.alloc(&v->buf[i], maxel * v->Bmax));
+    WMAR_TRY(v->mem.alloc(&v->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)v->Bmax * GN_CHUNKS_MAX * 32 * 2));
     v->gn_tiles_cap = (long long)v->Bmax * (cfg->resolution / 8) * (cfg->resolution / 8) * 64;
-    TRY(arena.alloc(&v->gn_tiles, (size_t)v->gn_tiles_cap));
-    TRY(arena.alloc(&v->znorm, (size_t)v->Bmax * S * S));
-    TRY(arena.alloc(&v->vqbest, (size_t)v->Bmax * S * S));
+    WMAR_TRY(v->mem.alloc(&v->gn_tiles, (size_t)v->gn_tiles_cap));
+    WMAR_TRY(v->mem.alloc(&v->znorm, (size_t)v->Bmax * S * S));
+    WMAR_TRY(v->mem.alloc(&v->vqbest, (size_t)v->Bmax * S * S));
     if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("mvq_create: sync failed"); rc = WMAR_EHIP; }
-#undef TRY
     if (rc != WMAR_OK) { delete v; return rc; }
     *out = v;
     return WMAR_OK;
 }
 
 void wmar_mvq_destroy(wmar_mvq* v) { delete v; }
-int64_t wmar_mvq_device_bytes(const wmar_mvq* v) { return v ? v->bytes : 0; }
+int64_t wmar_mvq_device_bytes(const wmar_mvq* v) { return v ? v->mem.bytes : 0; }
 
 int wmar_mvq_decode(wmar_mvq* v, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream) {
     WMAR_REQUIRE(v && codes_dev && images_dev, "mvq_decode: null argument");

@@ -16,39 +16,81 @@ def _require_cuda(t: torch.Tensor, what: str):
         raise RuntimeError(f"wmar_amd: {what} must live on the MI355X (no CPU implementation)")
 
 
-class GPTEngine:
-    """minGPT with a static KV cache; replaces GPT.forward_with_past + sample_with_past
-    (deps/taming/modules/transformer/mingpt.py:183-214, 326-368)."""
+class _Engine:
+    """Owner of one native engine handle: `<prefix>_create` / `_destroy` / `_device_bytes` of libwmar_hip.so."""
 
-    def __init__(self, cfg: GPTConfig, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda"):
-        self.cfg = cfg
+    _prefix = ""  # "wmar_gpt", ...
+
+    def _create(self, config, state: Dict[str, torch.Tensor], keep, device, max_batch: int, dtype=torch.float32):
+        """Creates the engine from the entries of `state` whose name `keep` accepts, moved to `device` as contiguous `dtype`
+        (the engine repacks them into its own HBM buffers: the copies made here are dropped on return)."""
         self.device = torch.device(device)
         self.max_batch = int(max_batch)
-        L = _lib.load()
-        tensors = {}
-        for k, v in state.items():
-            if k.endswith("attn.mask"):
-                continue
-            t = v.detach().to(device=self.device, dtype=torch.float32).contiguous()
-            tensors[k] = t
+        self._L = _lib.load()
+        tensors = {k: v.detach().to(device=self.device, dtype=dtype).contiguous() for k, v in state.items() if keep(k)}
         names, ptrs, n = _lib.tensor_table(tensors)
-        c = _lib.GptConfig(cfg.vocab_size, cfg.block_size, cfg.n_layer, cfg.n_head, cfg.n_embd, self.max_batch)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(L.wmar_gpt_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(self.device), C.byref(h)))
+            _lib.check(getattr(self._L, self._prefix + "_create")(C.byref(config), names, ptrs, n, _lib.stream_ptr(self.device),
+                                                                  C.byref(h)))
         self._h = h
-        self._L = L
-        del tensors  # weights were repacked into the engine's own HBM buffers
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            self._L.wmar_gpt_destroy(h)
+            getattr(self._L, self._prefix + "_destroy")(h)
             self._h = None
 
     @property
     def device_bytes(self) -> int:
-        return int(self._L.wmar_gpt_device_bytes(self._h))
+        return int(getattr(self._L, self._prefix + "_device_bytes")(self._h))
+
+
+class _TokenizerEngine(_Engine):
+    """Chunked (max_batch images per call) encode / decode of the two VQ tokenizers."""
+
+    _out_channels = 0  # image channels of decode()
+    _code_dim = 0      # width of the pre-quantization rows encode() can return
+
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        _require_cuda(codes, "codes")
+        codes = codes.to(torch.int64).contiguous()
+        B = codes.shape[0]
+        R = self.cfg.resolution
+        out = torch.empty(B, self._out_channels, R, R, dtype=torch.float32, device=self.device)
+        decode = getattr(self._L, self._prefix + "_decode")
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, self.max_batch):
+                b1 = min(B, b0 + self.max_batch)
+                _lib.check(decode(self._h, codes[b0:b1].data_ptr(), b1 - b0, out[b0:b1].data_ptr(), _lib.stream_ptr(self.device)))
+        return out
+
+    def encode(self, images: torch.Tensor, return_prequant: bool = False):
+        _require_cuda(images, "images")
+        images = images.to(torch.float32).contiguous()
+        B = images.shape[0]
+        S = self.cfg.codes_size
+        codes = torch.empty(B, S * S, dtype=torch.int64, device=self.device)
+        pre = torch.empty(B * S * S, self._code_dim, dtype=torch.float32, device=self.device) if return_prequant else None
+        encode = getattr(self._L, self._prefix + "_encode")
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, self.max_batch):
+                b1 = min(B, b0 + self.max_batch)
+                _lib.check(encode(self._h, images[b0:b1].data_ptr(), b1 - b0, codes[b0:b1].data_ptr(),
+                                  pre[b0 * S * S:b1 * S * S].data_ptr() if pre is not None else None, _lib.stream_ptr(self.device)))
+        return (codes, pre) if return_prequant else codes
+
+
+class GPTEngine(_Engine):
+    """minGPT with a static KV cache; replaces GPT.forward_with_past + sample_with_past
+    (deps/taming/modules/transformer/mingpt.py:183-214, 326-368)."""
+
+    _prefix = "wmar_gpt"
+
+    def __init__(self, cfg: GPTConfig, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda"):
+        self.cfg = cfg
+        c = _lib.GptConfig(cfg.vocab_size, cfg.block_size, cfg.n_layer, cfg.n_head, cfg.n_embd, int(max_batch))
+        self._create(c, state, lambda k: not k.endswith("attn.mask"), device, max_batch)
 
     def decode_step(self, tok: torch.Tensor, pos: int) -> torch.Tensor:
         """One token per sequence at position `pos` -> logits [B, V]."""
@@ -116,18 +158,15 @@ class GPTEngine:
         return {k: (us[i], calls[i]) for i, k in enumerate(self.T_CLASSES)}, step.value
 
 
-class VQGANEngine:
+class VQGANEngine(_TokenizerEngine):
     """Taming VQGAN encode / decode; replaces VQModel.encode/decode + VectorQuantizer2
     (deps/taming/models/vqgan.py:64-73, modules/vqvae/quantize.py:272-331)."""
 
+    _prefix = "wmar_vq"
+
     def __init__(self, cfg: VQConfig, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda"):
         self.cfg = cfg
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
-        L = _lib.load()
-        tensors = {k: v.detach().to(device=self.device, dtype=torch.float32).contiguous() for k, v in state.items()
-                   if not k.startswith("loss.")}
-        names, ptrs, n = _lib.tensor_table(tensors)
+        self._out_channels, self._code_dim = cfg.out_ch, cfg.embed_dim
         c = _lib.VqConfig()
         c.ch, c.num_res_blocks, c.resolution = cfg.ch, cfg.num_res_blocks, cfg.resolution
         c.in_channels, c.out_ch, c.z_channels = cfg.in_channels, cfg.out_ch, cfg.z_channels
@@ -137,81 +176,33 @@ class VQGANEngine:
         c.n_attn_res = len(cfg.attn_resolutions)
         for i, r in enumerate(cfg.attn_resolutions):
             c.attn_resolutions[i] = r
-        c.max_batch = self.max_batch
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.wmar_vq_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(self.device), C.byref(h)))
-        self._h = h
-        self._L = L
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.wmar_vq_destroy(h)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        return int(self._L.wmar_vq_device_bytes(self._h))
-
-    def decode(self, codes: torch.Tensor) -> torch.Tensor:
-        _require_cuda(codes, "codes")
-        codes = codes.to(torch.int64).contiguous()
-        B = codes.shape[0]
-        R = self.cfg.resolution
-        out = torch.empty(B, self.cfg.out_ch, R, R, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, self.max_batch):
-                b1 = min(B, b0 + self.max_batch)
-                _lib.check(self._L.wmar_vq_decode(self._h, codes[b0:b1].data_ptr(), b1 - b0, out[b0:b1].data_ptr(),
-                                                  _lib.stream_ptr(self.device)))
-        return out
-
-    def encode(self, images: torch.Tensor, return_prequant: bool = False):
-        _require_cuda(images, "images")
-        images = images.to(torch.float32).contiguous()
-        B = images.shape[0]
-        S = self.cfg.codes_size
-        codes = torch.empty(B, S * S, dtype=torch.int64, device=self.device)
-        pre = torch.empty(B * S * S, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if return_prequant else None
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, self.max_batch):
-                b1 = min(B, b0 + self.max_batch)
-                _lib.check(self._L.wmar_vq_encode(
-                    self._h, images[b0:b1].data_ptr(), b1 - b0, codes[b0:b1].data_ptr(),
-                    pre[b0 * S * S:b1 * S * S].data_ptr() if pre is not None else None, _lib.stream_ptr(self.device)))
-        return (codes, pre) if return_prequant else codes
+        c.max_batch = int(max_batch)
+        self._create(c, state, lambda k: not k.startswith("loss."), device, max_batch)
 
 
-class RAREngine:
+class RAREngine(_Engine):
     """RAR generator with KV cache, adaLN, qk-norm and classifier-free guidance; replaces
     RAR.forward_fn / RAR.generate (deps/rar/modeling/rar.py:319-459)."""
 
+    _prefix = "wmar_rar"
+
     def __init__(self, cfg, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda"):
         self.cfg = cfg
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
-        L = _lib.load()
-        tensors = {k: v.detach().to(device=self.device, dtype=torch.float32).contiguous() for k, v in state.items()
-                   if k != "attn_mask"}
-        names, ptrs, n = _lib.tensor_table(tensors)
         c = _lib.RarConfig(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.intermediate_size,
-                           cfg.image_seq_len, cfg.codebook_size, cfg.condition_num_classes, self.max_batch)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.wmar_rar_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(self.device), C.byref(h)))
-        self._h = h
-        self._L = L
+                           cfg.image_seq_len, cfg.codebook_size, cfg.condition_num_classes, int(max_batch))
+        self._create(c, state, lambda k: k != "attn_mask", device, max_batch)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.wmar_rar_destroy(h)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        return int(self._L.wmar_rar_device_bytes(self._h))
+    def _staging(self, class_ids: torch.Tensor, cfg_scales: Optional[torch.Tensor]):
+        """Arguments both generate calls share: class ids [B], the token buffer [B, L] and the guidance scales as
+        (host tensor kept alive, float pointer or None, use_guidance)."""
+        _require_cuda(class_ids, "class ids")
+        class_ids = class_ids.to(torch.int64).contiguous().view(-1)
+        out = torch.empty(class_ids.shape[0], self.cfg.image_seq_len, dtype=torch.int64, device=self.device)
+        if cfg_scales is None:
+            return class_ids, out, (None, None, 0)
+        sc = cfg_scales.detach().to("cpu", torch.float32).contiguous()
+        assert sc.numel() == self.cfg.image_seq_len
+        return class_ids, out, (sc, C.cast(sc.data_ptr(), C.POINTER(C.c_float)), 1)
 
     def launch_status(self) -> Dict[str, int]:
         """{"fused": the fused residual + modulation launch is in use, "fallbacks": calls re-run on the two-launch pair}."""
@@ -234,122 +225,59 @@ class RAREngine:
     def generate(self, class_ids: torch.Tensor, q: torch.Tensor, cfg_scales: Optional[torch.Tensor], temperature=1.0,
                  wm_ctx: Optional[_lib.WmCtx] = None, use_graph: bool = True) -> torch.Tensor:
         """class_ids int64 [B]; q float32 [L, B, V]; cfg_scales float32 [L] on the host (None: no guidance)."""
-        _require_cuda(class_ids, "class ids")
+        class_ids, out, (sc, sc_ptr, guided) = self._staging(class_ids, cfg_scales)
         _require_cuda(q, "q")
-        class_ids = class_ids.to(torch.int64).contiguous().view(-1)
         B = class_ids.shape[0]
-        Ls, V = self.cfg.image_seq_len, self.cfg.codebook_size
-        assert q.shape == (Ls, B, V) and q.dtype == torch.float32 and q.is_contiguous()
-        out = torch.empty(B, Ls, dtype=torch.int64, device=self.device)
-        sc = None
-        if cfg_scales is not None:
-            sc = cfg_scales.detach().to("cpu", torch.float32).contiguous()
-            assert sc.numel() == Ls
+        assert q.shape == (self.cfg.image_seq_len, B, self.cfg.codebook_size) and q.dtype == torch.float32 and q.is_contiguous()
         with torch.cuda.device(self.device):
             _lib.check(self._L.wmar_rar_generate(
-                self._h, C.byref(wm_ctx) if wm_ctx is not None else None, class_ids.data_ptr(), B,
-                C.cast(sc.data_ptr(), C.POINTER(C.c_float)) if sc is not None else None, 1 if sc is not None else 0,
+                self._h, C.byref(wm_ctx) if wm_ctx is not None else None, class_ids.data_ptr(), B, sc_ptr, guided,
                 float(temperature), q.data_ptr(), out.data_ptr(), 1 if use_graph else 0, _lib.stream_ptr(self.device)))
             _lib.check(self._L.wmar_rar_check(self._h, _lib.stream_ptr(self.device)))      # waits; raises if an in-launch wait gave up
         return out
 
     def generate_gumbel(self, class_ids, log_rs, cfg_scales, temperature=1.0, top_p=0.0, top_k=0, use_graph=True):
         """RAR.generate with the Gumbel-key sampler (extension, include/wmar_hip.h wmar_rar_generate_gumbel)."""
-        _require_cuda(class_ids, "class ids")
+        class_ids, out, (sc, sc_ptr, guided) = self._staging(class_ids, cfg_scales)
         _require_cuda(log_rs, "gumbel key")
-        class_ids = class_ids.to(torch.int64).contiguous().view(-1)
-        B = class_ids.shape[0]
-        Ls, V = self.cfg.image_seq_len, self.cfg.codebook_size
-        assert log_rs.shape == (V,) and log_rs.dtype == torch.float32 and log_rs.is_contiguous()
-        out = torch.empty(B, Ls, dtype=torch.int64, device=self.device)
-        sc = None
-        if cfg_scales is not None:
-            sc = cfg_scales.detach().to("cpu", torch.float32).contiguous()
-            assert sc.numel() == Ls
+        assert log_rs.shape == (self.cfg.codebook_size,) and log_rs.dtype == torch.float32 and log_rs.is_contiguous()
         with torch.cuda.device(self.device):
             _lib.check(self._L.wmar_rar_generate_gumbel(
-                self._h, class_ids.data_ptr(), B, C.cast(sc.data_ptr(), C.POINTER(C.c_float)) if sc is not None else None,
-                1 if sc is not None else 0, float(temperature), float(top_p), int(top_k), log_rs.data_ptr(), out.data_ptr(),
-                1 if use_graph else 0, _lib.stream_ptr(self.device)))
+                self._h, class_ids.data_ptr(), class_ids.shape[0], sc_ptr, guided, float(temperature), float(top_p), int(top_k),
+                log_rs.data_ptr(), out.data_ptr(), 1 if use_graph else 0, _lib.stream_ptr(self.device)))
             _lib.check(self._L.wmar_rar_check(self._h, _lib.stream_ptr(self.device)))
         return out
 
 
-class MaskgitVQEngine:
+class MaskgitVQEngine(_TokenizerEngine):
     """MaskGIT-VQGAN tokenizer of RAR; replaces PretrainedTokenizer.encode / decode_tokens
     (deps/rar/modeling/titok.py:75-89) incl. the wrapper's [-1,1] <-> [0,1] rescaling."""
 
+    _prefix = "wmar_mvq"
+
     def __init__(self, cfg, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda"):
         self.cfg = cfg
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
-        L = _lib.load()
-        tensors = {k: v.detach().to(device=self.device, dtype=torch.float32).contiguous() for k, v in state.items()
-                   if k.startswith(("encoder.", "decoder.", "quantize."))}
-        names, ptrs, n = _lib.tensor_table(tensors)
+        self._out_channels, self._code_dim = cfg.num_channels, cfg.z_channels
         c = _lib.MvqConfig()
         c.hidden_channels, c.num_res_blocks, c.resolution = cfg.hidden_channels, cfg.num_res_blocks, cfg.resolution
         c.num_channels, c.z_channels, c.num_embeddings = cfg.num_channels, cfg.z_channels, cfg.num_embeddings
         c.n_levels = len(cfg.channel_mult)
         for i, m in enumerate(cfg.channel_mult):
             c.channel_mult[i] = m
-        c.max_batch = self.max_batch
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.wmar_mvq_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(self.device), C.byref(h)))
-        self._h = h
-        self._L = L
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.wmar_mvq_destroy(h)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        return int(self._L.wmar_mvq_device_bytes(self._h))
-
-    def decode(self, codes: torch.Tensor) -> torch.Tensor:
-        _require_cuda(codes, "codes")
-        codes = codes.to(torch.int64).contiguous()
-        B = codes.shape[0]
-        R = self.cfg.resolution
-        out = torch.empty(B, self.cfg.num_channels, R, R, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, self.max_batch):
-                b1 = min(B, b0 + self.max_batch)
-                _lib.check(self._L.wmar_mvq_decode(self._h, codes[b0:b1].data_ptr(), b1 - b0, out[b0:b1].data_ptr(),
-                                                   _lib.stream_ptr(self.device)))
-        return out
-
-    def encode(self, images: torch.Tensor, return_prequant: bool = False):
-        _require_cuda(images, "images")
-        images = images.to(torch.float32).contiguous()
-        B = images.shape[0]
-        S = self.cfg.codes_size
-        codes = torch.empty(B, S * S, dtype=torch.int64, device=self.device)
-        pre = torch.empty(B * S * S, self.cfg.z_channels, dtype=torch.float32, device=self.device) if return_prequant else None
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, self.max_batch):
-                b1 = min(B, b0 + self.max_batch)
-                _lib.check(self._L.wmar_mvq_encode(
-                    self._h, images[b0:b1].data_ptr(), b1 - b0, codes[b0:b1].data_ptr(),
-                    pre[b0 * S * S:b1 * S * S].data_ptr() if pre is not None else None, _lib.stream_ptr(self.device)))
-        return (codes, pre) if return_prequant else codes
+        c.max_batch = int(max_batch)
+        self._create(c, state, lambda k: k.startswith(("encoder.", "decoder.", "quantize.")), device, max_batch)
 
 
-class ChameleonEngine:
+class ChameleonEngine(_Engine):
     """Chameleon / Anole transformer decode with KV cache, three guidance streams and the fused sampler; replaces
     ChameleonModelAdapter + Transformer.forward_with_attn_bias + the ImageDecoder token loop
     (deps/chameleon/inference/model_adapter.py:36-119, transformer.py:288-337, chameleon.py:299-389)."""
 
+    _prefix = "wmar_cham"
+
     def __init__(self, cfg, state: Dict[str, torch.Tensor], max_batch: int = 16, max_seq_len: int = 1024 + 128, device="cuda"):
         self.cfg = cfg
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
         self.max_seq_len = int(max_seq_len)
-        L = _lib.load()
         state = dict(state)
         for l in range(cfg.n_layers):   # the reference's load hooks (transformer.py:84-98, 197-208)
             p = f"layers.{l}."
@@ -362,28 +290,11 @@ class ChameleonEngine:
         state.pop("rope.freqs", None)
         dts = {v.dtype for v in state.values()}
         bf16 = dts == {torch.bfloat16}
-        dt = torch.bfloat16 if bf16 else torch.float32
-        tensors = {k: v.detach().to(device=self.device, dtype=dt).contiguous() for k, v in state.items()}
-        names, ptrs, n = _lib.tensor_table(tensors)
         c = _lib.ChamConfig(cfg.dim, cfg.n_layers, cfg.n_heads, cfg.n_kv_heads, cfg.vocab_size, cfg.ffn_hidden, cfg.norm_eps,
-                            cfg.rope_theta, int(cfg.qk_normalization), int(cfg.swin_norm), 3 * self.max_batch, self.max_seq_len,
+                            cfg.rope_theta, int(cfg.qk_normalization), int(cfg.swin_norm), 3 * int(max_batch), self.max_seq_len,
                             int(bf16))
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.wmar_cham_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(self.device), C.byref(h)))
-            torch.cuda.synchronize(self.device)
-        self._h = h
-        self._L = L
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.wmar_cham_destroy(h)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        return int(self._L.wmar_cham_device_bytes(self._h))
+        self._create(c, state, lambda k: True, device, max_batch, torch.bfloat16 if bf16 else torch.float32)
+        torch.cuda.synchronize(self.device)
 
     def forward_tokens(self, tok: torch.Tensor, pos: torch.Tensor, want_logits: bool = True) -> Optional[torch.Tensor]:
         """tok int64 [M], pos int32 [M] -> logits float32 [M, V] (one token per sequence, warm caches)."""
