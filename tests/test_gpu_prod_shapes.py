@@ -90,7 +90,8 @@ def test_gpt_1536_watermarked_loop_256_steps(pv, kat, gpt, graph, phases):
 
 
 def test_gpt_1536_batch_33_and_1_vs_fixture_rows(pv, gpt):
-    """rows are independent: batches of 1 and 33 (one / two row tiles, other GEMM variants) give the same logits."""
+    """rows are independent: batches of 1 and 33 (one / two row tiles, other GEMM variants) give the same logits.
+    (The sweep over the row counts 13..128 through all 256 positions lives in test_gpu_row_counts.py.)"""
     seq = torch.from_numpy(pv["gpt_seq"].astype(np.int64)).cuda()
     for B in (1, 33):
         for t in range(3):

@@ -52,7 +52,7 @@ struct wmar_gpt {
     // small-batch path (1..12 rows, n_embd 1536, head_dim 64): streaming kernels on row-major weights, five launches per layer
     std::vector<SmallW> sw;
     float *whead_rm = nullptr, *lnfw = nullptr, *lnfb = nullptr;
-    float *xs = nullptr, *ys = nullptr, *hs = nullptr, *qs = nullptr;     // [8][D], [8][D], [8][4D], [8][D] row-major
+    float *xs = nullptr, *ys = nullptr, *hs = nullptr, *qs = nullptr;     // [SG_MAX_ROWS][D], [..][D], [..][4D], [..][D] row-major
     bool small_ok = false;
     // ... and for 1..5 rows the whole step as ONE persistent launch (decode_persist.h): needs all 256 workgroups resident and the
     // blockIdx % 8 -> XCD grouping; a barrier that gives up switches the engine back to the five-launch plan (the call is re-run)
