@@ -43,12 +43,14 @@ def get_parser():
     parser.add_argument("--orig_only", type=str2bool, nargs="?", help="orig only", default=False)
     parser.add_argument("--include_neural_compress", type=str2bool, nargs="?", help="include NC", default=True)
     parser.add_argument("--include_diffpure", type=str2bool, nargs="?", help="include diffpure", default=True)
-    parser.add_argument("--wm_method", type=str, nargs="?", help="method", choices=["none", "gentime"])
+    parser.add_argument("--wm_method", type=str, nargs="?", help="method", choices=["none", "gentime", "gumbel"])
     parser.add_argument("--wm_seed_strategy", type=str, nargs="?", help="", choices=["fixed", "linear", "spatial"])
     parser.add_argument("--wm_split_strategy", type=str, nargs="?", help="", choices=["rand", "stratifiedrand", "clustering"])
     parser.add_argument("--wm_context_size", type=int, nargs="?", help="context size", default=0)
     parser.add_argument("--wm_delta", type=float, nargs="?", help="wm strength")
     parser.add_argument("--wm_gamma", type=float, nargs="?", help="wm gamma", default=0)
+    parser.add_argument("--wm_gumbel_seed", type=int, nargs="?", default=42,
+                        help="key seed of --wm_method gumbel (--model rar; independent of --seed; --wm_context_size is its ngram)")
     parser.add_argument("--sync", type=str2bool, default=False)
     parser.add_argument("--syncpath", type=str)
     parser.add_argument("--seed", type=int, nargs="?", help="seed", default=42)
@@ -63,9 +65,22 @@ def get_parser():
     return parser
 
 
+def check_wm_args(args):
+    """Combinations of watermark flags a model cannot run; raises ValueError with the reason."""
+    if args.wm_method == "gumbel" and args.model != "rar":
+        raise ValueError(f"--wm_method gumbel needs --model rar: {args.model} has no Gumbel-key generation loop")
+    if args.wm_method == "gumbel" and not 0 <= args.wm_context_size <= 16:
+        raise ValueError("--wm_method gumbel: --wm_context_size (the ngram of the key) must be in 0..16")
+
+
 def main():
     sys.path.append(os.getcwd())
-    args, _ = get_parser().parse_known_args()
+    parser = get_parser()
+    args, _ = parser.parse_known_args()
+    try:
+        check_wm_args(args)
+    except ValueError as e:
+        parser.error(str(e))
     assert args.outdir, "Output directory is not set"
     assert args.model in ("taming", "rar", "chameleon7b"), f"Model {args.model} not supported"
     assert not args.sync, "--sync (WAM/SyncSeal) is outside the MI355X hot path"
@@ -131,7 +146,9 @@ def main():
         text = model.vocab.text_tokens
         conditionings = [(c, [text[(c * 37 + j * 11) % len(text)] for j in range(12 + c % 5)]) for c in conditionings]
     all_inputs = [c for c in conditionings for _ in range(args.num_samples_per_conditioning)]
-    if "chameleon" in args.model or "rar" in args.model:
+    if args.model == "rar" and args.wm_method == "gumbel":
+        pass      # the Gumbel key has no seed / split strategy
+    elif "chameleon" in args.model or "rar" in args.model:
         assert (args.wm_method in ["none", "gentime"] and args.wm_seed_strategy in ["linear", "fixed"]
                 and args.wm_split_strategy == "stratifiedrand"), \
             "Chameleon and RAR models only support none or gentime watermarking with fixed/linear seed and stratifiedrand split"
@@ -144,6 +161,11 @@ def main():
                                        args.wm_gamma, model.device)
         if world > 1:  # build the key once, broadcast it over RCCL
             harness.broadcast_key_table(watermarker, device)
+    elif args.wm_method == "gumbel":
+        # RAR ignores gen_params (as in the reference): temperature 1.0, no top-p / top-k (--top_k / --top_p default to Taming's)
+        from wmar_amd.watermarking.gumbel_watermark import GumbelWatermark
+        watermarker = GumbelWatermark(vocab_size, seed=args.wm_gumbel_seed, temperature=1.0, top_p=0.0, top_k=0, device=model.device,
+                                      ngram=args.wm_context_size)
     model.set_watermarker(watermarker)
 
     # evaluation transforms: the classic ones run batched on the GPU; neural codecs and DiffPure are outside this build

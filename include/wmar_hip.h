@@ -10,7 +10,7 @@
  *     wmar_last_error() returns a human-readable message for the calling thread.
  *   - engines allocate in *_create; afterwards only small per-call scratch is allocated (prompt tables of
  *     wmar_cham_generate_image, the one-off unconditional adaLN table of wmar_rar_generate, a status word of
- *     wmar_gumbel_score).
+ *     wmar_gumbel_score / wmar_gumbel_score_ctx).
  *   - an engine handle (wmar_gpt / wmar_rar / wmar_cham / wmar_vq / wmar_mvq) is NOT thread-safe: it owns
  *     its workspaces, KV cache and captured graphs; use it from one thread and one stream at a time
  *     (the reference is single-threaded per model too).
@@ -242,6 +242,16 @@ int wmar_rar_generate_gumbel(wmar_rar* g, const int64_t* class_ids_dev, int64_t 
                              int32_t use_guidance, float temperature, float top_p, int32_t top_k,
                              const float* log_rs_dev, int64_t* tokens_out_dev, int32_t use_graph, void* stream);
 
+/* The same with a CONTEXT-KEYED key (ngram in 1..WMAR_MAX_CONTEXT).  Context = the generated ids only.  Position l >= ngram of row b
+ * is sampled with the key of hash = h0 ^ ids[b, l-ngram] ^ ... ^ ids[b, l-1], derived on the device inside the step (the arrays of
+ * wmar_gumbel_key_rows); h0 = the hash of the empty window (first randint(0, 2^31 - 1) of the CPU generator seeded with the
+ * watermark seed: the caller computes it).  Positions l < ngram are unkeyed: u_dev float [ngram, B, V], uniform in [0, 1), takes the
+ * place of rs in the same sampler arithmetic -- plain sampling from p.  One captured graph serves every position (keyed or not is
+ * decided on the device-side step counter); use_graph = 0 gives the same tokens. */
+int wmar_rar_generate_gumbel_ctx(wmar_rar* g, const int64_t* class_ids_dev, int64_t B, const float* cfg_scale_host,
+                                 int32_t use_guidance, float temperature, float top_p, int32_t top_k, uint64_t h0, int32_t ngram,
+                                 const float* u_dev, int64_t* tokens_out_dev, int32_t use_graph, void* stream);
+
 /* In-launch synchronisation of the RAR engine: the fused residual + adaLN modulation launch of a block (k_resid_mod) lets its
  * workgroups wait for each other's partial sums.  wmar_rar_create enables it when the device holds the whole grid at once
  * (occupancy x compute units; WMAR_NO_XR=1 disables it), otherwise the same work runs as a two-launch pair (bit-identical results).
@@ -277,6 +287,20 @@ int wmar_gumbel_sample(const float* logits_dev, int64_t B, int64_t V, const floa
  * accumulates into zeros_like(tokens)).  Either output may be null. */
 int wmar_gumbel_score(const int64_t* tokens_dev, int64_t B, int64_t L, int64_t V, const float* score_key_dev,
                       int64_t key_row_stride, int64_t* scores_i64_dev, float* scores_f32_dev, void* stream);
+
+/* The arrays of wmar_gumbel_key_build for N window hashes, derived ON THE DEVICE (MT19937 per hash, state in LDS; the logarithms in
+ * fp64, rounded once): rs / log_rs / score rows float [N, V], bit-equal to the host builder's for seed = hash & 0xffffffff.
+ * hash_dev int64 [N] on the device; any output may be null.  Asynchronous: no host copy, no synchronisation. */
+int wmar_gumbel_key_rows(const int64_t* hash_dev, int64_t N, int64_t V, float* rs_out_dev, float* log_rs_out_dev,
+                         float* score_out_dev, void* stream);
+
+/* Detector of the context-keyed watermark for tokens int64 [B, L], ngram in 1..WMAR_MAX_CONTEXT, V <= 16384, L <= 4096.
+ * Position l >= ngram is scored when its (ngram+1)-tuple ids[b, l-ngram .. l] has not occurred at an earlier scored position of
+ * the row: scored_mask_dev int8 [B, L], n_scored_dev int32 [B] (nullable), scores_f32_dev[b, l] = -log(1 - rs_hash)[ids[b, l]] with
+ * hash = h0 ^ ids[b, l-ngram] ^ ... ^ ids[b, l-1] (0 where unscored).  L <= ngram: WMAR_ESHORT.  Token ids outside [0, V) are
+ * rejected like wmar_gumbel_score's (the call waits for the stream). */
+int wmar_gumbel_score_ctx(const int64_t* tokens_dev, int64_t B, int64_t L, int64_t V, uint64_t h0, int32_t ngram,
+                          float* scores_f32_dev, int8_t* scored_mask_dev, int32_t* n_scored_dev, void* stream);
 
 /* ------------------------------------------------------------------ Chameleon (row C1)
  * Chameleon / Anole text->image decode: deps/chameleon/inference/transformer.py:288-353

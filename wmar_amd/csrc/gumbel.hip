@@ -195,6 +195,164 @@ int launch_gumbel_sample(const GumbelArgs& a, hipStream_t st) {
     return launch_status("k_gumbel_sample");
 }
 
+// ------------------------------------------------------------------ key rows derived on the device (ngram > 0)
+// rs = torch.rand(V, generator = CPU MT19937 seeded with hash & 0xffffffff): the generator of keytable.cpp's Mt19937, run by one
+// workgroup per hash with its 624-word state in LDS.
+//   * seeding s[j] = 1812433253 (s[j-1] ^ s[j-1] >> 30) + j is a dependent chain: one lane walks it (623 steps);
+//   * a twist s[k] = s[k+397 mod 624] ^ f(s[k], s[k+1 mod 624]) in ascending k reads NEW words only at distance -227: words 0..226
+//     read old state only, 227..453 read the first group's results, 454..623 the second's (and word 623 the new s[0]) -- three
+//     parallel phases, each "read, barrier, write, barrier" because word k-1 still needs the old s[k];
+//   * tempering and the low 24 bits are per word; the two logarithms are taken in fp64 and rounded to fp32 once, as the host builder
+//     (wmar_gumbel_key_build) does: log_rs decides tokens through comparisons of log_rs * (1/p), so the rows must equal the host's bit
+//     for bit (tests/test_gpu_gumbel_ctx.py compares 4096 x 16384 entries of all three arrays).
+constexpr int MT_N = 624, MT_M = 397;
+constexpr int KEY_THREADS = 256;
+constexpr int SCORE_THREADS = 64;
+
+__device__ __forceinline__ void mt_seed(uint32_t* s, uint32_t seed) {
+    if (threadIdx.x == 0) {
+        uint32_t x = seed;
+        s[0] = x;
+        for (int j = 1; j < MT_N; ++j) { x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)j; s[j] = x; }
+    }
+    __syncthreads();
+}
+
+// every thread of the workgroup (NT of them) calls it; ends behind a barrier
+template <int NT>
+__device__ __forceinline__ void mt_twist(uint32_t* s) {
+    constexpr int PER = (MT_N - MT_M + NT - 1) / NT;      // 227 words in the largest phase
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int ph = 0; ph < 3; ++ph) {
+        const int lo = ph * (MT_N - MT_M), hi = ph == 2 ? MT_N : lo + (MT_N - MT_M);
+        uint32_t v[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int k = lo + tid + i * NT;
+            v[i] = 0;
+            if (k < hi) {
+                const int k1 = k + 1 < MT_N ? k + 1 : 0, km = k + MT_M < MT_N ? k + MT_M : k + MT_M - MT_N;
+                const uint32_t y = (s[k] & 0x80000000u) | (s[k1] & 0x7fffffffu);
+                v[i] = s[km] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int k = lo + tid + i * NT;
+            if (k < hi) s[k] = v[i];
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ float mt_uniform(uint32_t y) {      // at::uniform_real_distribution<float>: 24 bits of the tempered word
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= y >> 18;
+    return (float)(y & 0xffffffu) * 5.9604644775390625e-08f;
+}
+__device__ __forceinline__ float gum_log_rs(float rs) { return (float)log((double)rs); }                  // -inf for rs == 0
+__device__ __forceinline__ float gum_score_of(float rs) { return (float)(-log((double)(1.0f - rs))); }
+
+// the three arrays of one hash (any may be null), by the whole workgroup of KEY_THREADS threads
+__device__ __forceinline__ void key_row_emit(uint32_t* s, uint32_t seed, int V, float* rs_o, float* lr_o, float* sc_o) {
+    mt_seed(s, seed);
+    for (int base = 0; base < V; base += MT_N) {
+        mt_twist<KEY_THREADS>(s);
+        // (the next twist overwrites s only behind its first barrier, i.e. after every thread has left this loop)
+        for (int j = threadIdx.x; j < MT_N && base + j < V; j += KEY_THREADS) {
+            const float rs = mt_uniform(s[j]);
+            if (rs_o) rs_o[base + j] = rs;
+            if (lr_o) lr_o[base + j] = gum_log_rs(rs);
+            if (sc_o) sc_o[base + j] = gum_score_of(rs);
+        }
+    }
+}
+
+__global__ __launch_bounds__(KEY_THREADS) void k_gumbel_key_rows(const long long* hash, long long V, float* rs, float* lr, float* sc) {
+    __shared__ uint32_t s[MT_N];
+    const long long b = blockIdx.x;
+    const uint32_t seed = (uint32_t)((unsigned long long)hash[b] & 0xffffffffull);      // manual_seed keeps the low 32 bits
+    key_row_emit(s, seed, (int)V, rs ? rs + b * V : nullptr, lr ? lr + b * V : nullptr, sc ? sc + b * V : nullptr);
+}
+
+// hash of the window in front of position l of one row: h0 ^ ids[l-n] ^ ... ^ ids[l-1]
+__device__ __forceinline__ uint32_t ctx_seed(const long long* row, long long l, unsigned long long h0, int n) {
+    unsigned long long h = h0;
+    for (int i = 0; i < n; ++i) h ^= (unsigned long long)row[l - n + i];
+    return (uint32_t)(h & 0xffffffffull);
+}
+
+// One decode step of the keyed generation.  Keyed or not is decided on the device-side step counter (workgroup-uniform), so one
+// captured graph serves every position of the image.
+__global__ __launch_bounds__(KEY_THREADS) void k_gumbel_ctx_keys(GumbelCtxArgs a) {
+    __shared__ uint32_t s[MT_N];
+    const long long b = blockIdx.x;
+    const long long step = *a.step_dev;
+    float* out = a.log_rs_out + b * a.V;
+    if (step < a.ngram) {
+        const float* u = a.u + (step * a.B + b) * a.V;
+        for (int v = threadIdx.x; v < (int)a.V; v += KEY_THREADS) out[v] = gum_log_rs(u[v]);
+        return;
+    }
+    key_row_emit(s, ctx_seed(a.ids + b * a.ids_stride, step, a.h0, a.ngram), (int)a.V, nullptr, out, nullptr);
+}
+
+// Detector, part 1: which positions are scored.  One workgroup per image, its ids in LDS: position l >= n is scored when no
+// earlier position l' >= n carries the same (n+1)-tuple ids[l-n .. l].
+__global__ __launch_bounds__(256) void k_gumbel_ctx_mask(const long long* tokens, int L, long long V, int n, signed char* mask,
+                                                         int* n_scored, int* bad) {
+    extern __shared__ long long tk[];
+    __shared__ int cnt;
+    const long long b = blockIdx.x;
+    if (threadIdx.x == 0) cnt = 0;
+    for (int l = threadIdx.x; l < L; l += blockDim.x) {
+        const long long t = tokens[b * L + l];
+        if (t < 0 || t >= V) *bad = 1;
+        tk[l] = t;
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int l = threadIdx.x; l < L; l += blockDim.x) {
+        bool first = l >= n;
+        for (int e = n; first && e < l; ++e) {
+            bool same = true;
+            for (int i = 0; i <= n; ++i) same = same && tk[e - i] == tk[l - i];
+            first = !same;
+        }
+        mask[b * L + l] = first ? 1 : 0;
+        mine += first ? 1 : 0;
+    }
+    if (mine) atomicAdd(&cnt, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && n_scored) n_scored[b] = cnt;
+}
+
+// Detector, part 2: one wave per position.  Entry ids[b, l] of the window's key needs ids[b, l] / 624 + 1 twists and one logarithm.
+__global__ __launch_bounds__(SCORE_THREADS) void k_gumbel_ctx_score(const long long* tokens, long long L, long long V,
+                                                                    unsigned long long h0, int n, const signed char* mask,
+                                                                    float* scores) {
+    __shared__ uint32_t s[MT_N];
+    const long long i = blockIdx.x, l = i % L;
+    const long long t = tokens[i];
+    if (!mask[i] || t < 0 || t >= V) {          // workgroup-uniform
+        if (threadIdx.x == 0) scores[i] = 0.f;
+        return;
+    }
+    mt_seed(s, ctx_seed(tokens + (i - l), l, h0, n));
+    const int blocks = (int)(t / MT_N) + 1;
+    for (int k = 0; k < blocks; ++k) mt_twist<SCORE_THREADS>(s);
+    if (threadIdx.x == 0) scores[i] = gum_score_of(mt_uniform(s[t % MT_N]));
+}
+
+int launch_gumbel_ctx_keys(const GumbelCtxArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_gumbel_ctx_keys, dim3((unsigned)a.B), dim3(KEY_THREADS), 0, st, a);
+    return launch_status("k_gumbel_ctx_keys");
+}
+
 }  // namespace wmar
 
 using namespace wmar;
@@ -236,6 +394,52 @@ int wmar_gumbel_score(const int64_t* tokens_dev, int64_t B, int64_t L, int64_t V
     (void)hipFree(bad);
     if (e != hipSuccess) { set_error("gumbel_score: %s", hipGetErrorString(e)); return WMAR_EHIP; }
     WMAR_REQUIRE(!hbad, "gumbel_score: token id outside [0, %lld)", (long long)V);
+    return WMAR_OK;
+}
+
+int wmar_gumbel_key_rows(const int64_t* hash_dev, int64_t N, int64_t V, float* rs_out_dev, float* log_rs_out_dev,
+                         float* score_out_dev, void* stream) {
+    WMAR_REQUIRE(hash_dev || N == 0, "gumbel_key_rows: null argument");
+    WMAR_REQUIRE(N >= 0 && N < (1ll << 31) && V >= 1 && V < (1ll << 31), "gumbel_key_rows: bad shape");
+    if (N == 0 || !(rs_out_dev || log_rs_out_dev || score_out_dev)) return WMAR_OK;
+    hipLaunchKernelGGL(k_gumbel_key_rows, dim3((unsigned)N), dim3(KEY_THREADS), 0, (hipStream_t)stream, (const long long*)hash_dev,
+                       (long long)V, rs_out_dev, log_rs_out_dev, score_out_dev);
+    return launch_status("k_gumbel_key_rows");
+}
+
+int wmar_gumbel_score_ctx(const int64_t* tokens_dev, int64_t B, int64_t L, int64_t V, uint64_t h0, int32_t ngram,
+                          float* scores_f32_dev, int8_t* scored_mask_dev, int32_t* n_scored_dev, void* stream) {
+    WMAR_REQUIRE(tokens_dev && scores_f32_dev && scored_mask_dev, "gumbel_score_ctx: null argument");
+    WMAR_REQUIRE(ngram >= 1 && ngram <= WMAR_MAX_CONTEXT, "gumbel_score_ctx: ngram %d outside 1..%d", ngram, WMAR_MAX_CONTEXT);
+    WMAR_REQUIRE(B >= 0 && B < (1ll << 31) && V >= 1 && V <= GUM_EPT * GUM_THREADS, "gumbel_score_ctx: bad shape");
+    if (L <= ngram) {
+        set_error("gumbel_score_ctx: %lld codes leave nothing to score behind a window of %d", (long long)L, ngram);
+        return WMAR_ESHORT;
+    }
+    WMAR_REQUIRE(L <= 4096 && B * L < (1ll << 31), "gumbel_score_ctx: passage of %lld codes too long (4096)", (long long)L);
+    if (B == 0) return WMAR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    int* bad = nullptr;
+    WMAR_HIP_CHECK(hipMalloc(&bad, sizeof(int)));
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_gumbel_ctx_mask, dim3((unsigned)B), dim3(256), (size_t)L * sizeof(long long), st,
+                           (const long long*)tokens_dev, (int)L, (long long)V, (int)ngram, (signed char*)scored_mask_dev,
+                           (int*)n_scored_dev, bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_gumbel_ctx_score, dim3((unsigned)(B * L)), dim3(SCORE_THREADS), 0, st, (const long long*)tokens_dev,
+                           (long long)L, (long long)V, (unsigned long long)h0, (int)ngram, (const signed char*)scored_mask_dev,
+                           scores_f32_dev);
+        e = hipGetLastError();
+    }
+    int hbad = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(bad);
+    if (e != hipSuccess) { set_error("gumbel_score_ctx: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+    WMAR_REQUIRE(!hbad, "gumbel_score_ctx: token id outside [0, %lld)", (long long)V);
     return WMAR_OK;
 }
 

@@ -424,6 +424,7 @@ struct wmar_rar {
     bool mod_u_ready = false;
     double* stats = nullptr;
     float *kcache = nullptr, *vcache = nullptr, *logits = nullptr, *scratch = nullptr, *cfg_scale = nullptr;
+    float* gum_keys = nullptr;     // [Bmax][V] log(rs) rows of the current position (context-keyed Gumbel watermark); codebooks <= 16384
     long long *ids = nullptr, *cond_ids = nullptr;
     int* ctr = nullptr;   // [pos, step, len]
     unsigned long long* part = nullptr;   // [2 L launch sites][STAT_CHUNKS_MAX][Mpad][2]: k_resid_mod's published partial sums, poisoned at the start of every position
@@ -772,6 +773,7 @@ int wmar_rar_create(const wmar_rar_config* cfg, const char* const* names, const 
     WMAR_TRY(g->mem.alloc(&g->logits, (size_t)g->Mmax * V));
     WMAR_TRY(g->mem.alloc(&g->scratch, (size_t)g->Bmax * V));
     WMAR_TRY(g->mem.alloc(&g->cfg_scale, (size_t)cfg->image_seq_len));
+    if (V <= 16384) WMAR_TRY(g->mem.alloc(&g->gum_keys, (size_t)g->Bmax * V));
     WMAR_TRY(g->mem.alloc_zero(&g->ids, (size_t)g->Bmax * cfg->image_seq_len, st));
     WMAR_TRY(g->mem.alloc_zero(&g->cond_ids, (size_t)g->Mmax, st));
     WMAR_TRY(g->mem.alloc(&g->ctr, 4));
@@ -870,7 +872,7 @@ int wmar_rar_forward_position(wmar_rar* g, const int64_t* tok_dev, const int64_t
 
 static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,
                              const float* cfg_scale_host, int32_t use_guidance, float temperature, const float* q_dev,
-                             const float* log_rs_dev, float top_p, int32_t top_k,
+                             const float* log_rs_dev, float top_p, int32_t top_k, uint64_t h0, int32_t ngram, const float* u_dev,
                              int64_t* tokens_out_dev, int32_t use_graph, void* stream) {
     WMAR_REQUIRE(g && class_ids_dev && (q_dev || log_rs_dev) && tokens_out_dev, "rar_generate: null argument");
     WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "rar_generate: batch %lld outside 1..%d", (long long)B, g->Bmax);
@@ -930,14 +932,20 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
     if (use_guidance) { a.logits_uncond = g->logits + (long long)B * V; a.cfg_scale = g->cfg_scale; }
     GumbelArgs ga{};
     ga.logits = g->logits; ga.logits_uncond = a.logits_uncond; ga.cfg_scale = a.cfg_scale; ga.step_dev = g->ctr + 1;
-    ga.t_dev = g->ctr + 2; ga.V = V; ga.B = B; ga.log_rs = log_rs_dev; ga.key_row_stride = 0;
+    ga.t_dev = g->ctr + 2; ga.V = V; ga.B = B; ga.log_rs = log_rs_dev; ga.key_row_stride = ngram > 0 ? V : 0;
     ga.use_sampling = 1; ga.temp = temperature; ga.top_p = top_p; ga.top_k = top_k;
     ga.tok_out = (long long*)tokens_out_dev; ga.tok_out_stride = L; ga.past_append = g->ids; ga.past_stride = L;
+    // context-keyed Gumbel watermark (ngram > 0): the key rows of the position are derived from the ids generated so far by a launch
+    // of their own in front of the unchanged sampler (log_rs_dev is then g->gum_keys, one row per batch row)
+    GumbelCtxArgs gc{};
+    gc.ids = g->ids; gc.ids_stride = L; gc.step_dev = g->ctr + 1; gc.h0 = h0; gc.ngram = ngram; gc.u = u_dev; gc.V = V; gc.B = B;
+    gc.log_rs_out = g->gum_keys;
 
     auto one_step = [&](hipStream_t s) -> int {
         RarPlan q(g, M, (int)B, nullptr, s, shared_u);
         int rc = q.position(true, g->logits);
         if (rc) return rc;
+        if (ngram > 0 && (rc = launch_gumbel_ctx_keys(gc, s))) return rc;
         if ((rc = log_rs_dev ? launch_gumbel_sample(ga, s) : launch_sample_fused(a, s))) return rc;
         hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->ctr);
         return launch_status("k_advance3");
@@ -963,14 +971,14 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
 
 static int rar_generate_impl(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,
                              const float* cfg_scale_host, int32_t use_guidance, float temperature, const float* q_dev,
-                             const float* log_rs_dev, float top_p, int32_t top_k,
+                             const float* log_rs_dev, float top_p, int32_t top_k, uint64_t h0, int32_t ngram, const float* u_dev,
                              int64_t* tokens_out_dev, int32_t use_graph, void* stream) {
     WMAR_REQUIRE(g, "rar_generate: null argument");
     // on the fused path the call waits for its replays and reads the wait flag; a run that raised it is repeated on the
     // two-launch pair (same inputs, same noise: the same tokens)
     return run_with_fallback("rar_generate: the in-launch wait flag is up on the two-launch pair", [&] {
         return rar_generate_once(g, wm, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, log_rs_dev, top_p, top_k,
-                                 tokens_out_dev, use_graph, stream);
+                                 h0, ngram, u_dev, tokens_out_dev, use_graph, stream);
     }, [&] { return rar_sync_failed(g, (hipStream_t)stream); });
 }
 
@@ -978,7 +986,7 @@ int wmar_rar_generate(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_i
                       const float* cfg_scale_host, int32_t use_guidance, float temperature, const float* q_dev,
                       int64_t* tokens_out_dev, int32_t use_graph, void* stream) {
     WMAR_REQUIRE(q_dev, "rar_generate: null argument");
-    return rar_generate_impl(g, wm, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, nullptr, 0.f, 0,
+    return rar_generate_impl(g, wm, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, nullptr, 0.f, 0, 0, 0, nullptr,
                              tokens_out_dev, use_graph, stream);
 }
 
@@ -988,7 +996,19 @@ int wmar_rar_generate_gumbel(wmar_rar* g, const int64_t* class_ids_dev, int64_t 
     WMAR_REQUIRE(log_rs_dev, "rar_generate_gumbel: null key");
     WMAR_REQUIRE(g && g->V <= 16384, "rar_generate_gumbel: codebook larger than 16384");
     return rar_generate_impl(g, nullptr, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, nullptr, log_rs_dev, top_p,
-                             top_k, tokens_out_dev, use_graph, stream);
+                             top_k, 0, 0, nullptr, tokens_out_dev, use_graph, stream);
+}
+
+int wmar_rar_generate_gumbel_ctx(wmar_rar* g, const int64_t* class_ids_dev, int64_t B, const float* cfg_scale_host,
+                                 int32_t use_guidance, float temperature, float top_p, int32_t top_k, uint64_t h0, int32_t ngram,
+                                 const float* u_dev, int64_t* tokens_out_dev, int32_t use_graph, void* stream) {
+    WMAR_REQUIRE(g && u_dev, "rar_generate_gumbel_ctx: null argument");
+    WMAR_REQUIRE(g->V <= 16384 && g->gum_keys, "rar_generate_gumbel_ctx: codebook larger than 16384");
+    WMAR_REQUIRE(ngram >= 1 && ngram <= WMAR_MAX_CONTEXT && ngram < g->cfg.image_seq_len,
+                 "rar_generate_gumbel_ctx: ngram %d outside 1..%d (and below the %d positions of an image)", ngram, WMAR_MAX_CONTEXT,
+                 g->cfg.image_seq_len);
+    return rar_generate_impl(g, nullptr, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, nullptr, g->gum_keys, top_p,
+                             top_k, h0, ngram, u_dev, tokens_out_dev, use_graph, stream);
 }
 
 }  // extern "C"

@@ -88,4 +88,19 @@ struct GumbelArgs {
 
 int launch_gumbel_sample(const GumbelArgs& a, hipStream_t st);
 
+// Key rows of one decode step of the context-keyed Gumbel watermark (gumbel.hip, k_gumbel_ctx_keys): row b of log_rs_out is
+// log(rs) of the key hashed from the ngram ids in front of position *step_dev, or log(u[*step_dev, b]) while *step_dev < ngram.
+struct GumbelCtxArgs {
+    const long long* ids;        // [B, ids_stride] generated ids
+    long long ids_stride;
+    const int* step_dev;         // position being sampled
+    unsigned long long h0;       // hash of the empty window
+    int ngram;
+    const float* u;              // [ngram, B, V] uniform noise of the unkeyed positions
+    long long V, B;
+    float* log_rs_out;           // [B, V]
+};
+
+int launch_gumbel_ctx_keys(const GumbelCtxArgs& a, hipStream_t st);
+
 }  // namespace wmar

@@ -248,6 +248,22 @@ class RAREngine(_Engine):
             _lib.check(self._L.wmar_rar_check(self._h, _lib.stream_ptr(self.device)))
         return out
 
+    def generate_gumbel_ctx(self, class_ids, h0: int, ngram: int, u: torch.Tensor, cfg_scales, temperature=1.0, top_p=0.0, top_k=0,
+                            use_graph=True):
+        """RAR.generate with the context-keyed Gumbel sampler (include/wmar_hip.h wmar_rar_generate_gumbel_ctx): ``h0`` the hash of
+        the empty window, ``u`` float32 [ngram, B, V] uniform noise of the unkeyed first ``ngram`` positions."""
+        class_ids, out, (sc, sc_ptr, guided) = self._staging(class_ids, cfg_scales)
+        _require_cuda(u, "u")
+        B = class_ids.shape[0]
+        assert u.shape == (int(ngram), B, self.cfg.codebook_size) and u.dtype == torch.float32 and u.is_contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.wmar_rar_generate_gumbel_ctx(
+                self._h, class_ids.data_ptr(), B, sc_ptr, guided, float(temperature), float(top_p), int(top_k),
+                C.c_uint64(int(h0) & 0xFFFFFFFFFFFFFFFF), int(ngram), u.data_ptr(), out.data_ptr(), 1 if use_graph else 0,
+                _lib.stream_ptr(self.device)))
+            _lib.check(self._L.wmar_rar_check(self._h, _lib.stream_ptr(self.device)))
+        return out
+
 
 class MaskgitVQEngine(_TokenizerEngine):
     """MaskGIT-VQGAN tokenizer of RAR; replaces PretrainedTokenizer.encode / decode_tokens

@@ -106,6 +106,16 @@ class RarARMMWrapper(AutoregressiveMultimodalModelWrapper):
             q[n].copy_(self._noise_draw(lambda t, g: t.exponential_(1, generator=g), (B, cfg.codebook_size), generator))
         return q
 
+    def draw_gumbel_noise(self, B: int, ngram: int, generator=None) -> torch.Tensor:
+        """The draws of a context-keyed Gumbel generation, in order: the label-drop mask [B, 1] (as ``draw_noise``), then one
+        uniform [B, V] tensor per unkeyed position -> float32 [ngram, B, V]."""
+        cfg = self.model.cfg
+        self._noise_draw(lambda t, g: t.uniform_(0, 1, generator=g), (B, 1), generator)
+        u = torch.empty(ngram, B, cfg.codebook_size, dtype=torch.float32, device=self.model.device)
+        for n in range(ngram):
+            u[n].copy_(self._noise_draw(lambda t, g: t.uniform_(0, 1, generator=g), (B, cfg.codebook_size), generator))
+        return u
+
     # conditioning: list of size [b] of class indices; gen_params ignored (as in the reference)
     def sample(self, conditioning, gen_params=None, apply_watermark=False, q: Optional[torch.Tensor] = None):
         conditioning = torch.as_tensor(conditioning, device=self.model.device).view(-1)
@@ -117,6 +127,15 @@ class RarARMMWrapper(AutoregressiveMultimodalModelWrapper):
         if apply_watermark and isinstance(self.watermarker, GumbelWatermark):
             # Gumbel key: the key replaces the sampling noise (extension)
             w = self.watermarker
+            if w.ngram > 0:
+                # context-keyed: the first ngram positions are sampled from uniform noise (q, when given: float32 [ngram, B, V]),
+                # drawn per chunk in order
+                for b0 in range(0, B, mb):
+                    b1 = min(B, b0 + mb)
+                    u = q[:, b0:b1].contiguous() if q is not None else self.draw_gumbel_noise(b1 - b0, w.ngram)
+                    out[b0:b1] = self.model.engine.generate_gumbel_ctx(conditioning[b0:b1], w.h0, w.ngram, u, scales, w.temperature,
+                                                                       w.top_p, w.top_k, use_graph=self.use_graph)
+                return out.detach()
             for b0 in range(0, B, mb):
                 b1 = min(B, b0 + mb)
                 out[b0:b1] = self.model.engine.generate_gumbel(conditioning[b0:b1], w.log_rs, scales, w.temperature, w.top_p,
