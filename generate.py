@@ -88,13 +88,7 @@ def main():
 
     import torch.distributed as dist
 
-    from wmar_amd import harness
-    from wmar_amd.models.chameleon_wrapper import ChameleonARMMWrapper
-    from wmar_amd.models.rar_wrapper import RarARMMWrapper
-    from wmar_amd.models.taming_wrapper import TamingARMMWrapper
-    from wmar_amd.utils import synth
-    from wmar_amd.utils.utils import update_weights
-    from wmar_amd.watermarking.gentime_watermark import GentimeWatermark, SeedStrategy, SplitStrategy
+    from wmar_amd import cli, harness
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -108,33 +102,7 @@ def main():
 
     device = f"cuda:{local_rank}"
     seed = args.seed + 1000 * chunk_id
-    if args.model == "taming":
-        if args.synthetic and args.synthetic_config == "harness":
-            gcfg, vcfg = synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)
-            model = TamingARMMWrapper(None, gpt_cfg=gcfg, vq_cfg=vcfg, gpt_state=synth.synth_gpt_state(gcfg, 21, "cpu", 40.0),
-                                      vq_state=synth.synth_vq_state(vcfg, 21, "cpu"), device=device,
-                                      max_batch=min(args.batch_size, 128))
-        elif args.synthetic:
-            model = TamingARMMWrapper.synthetic(synth.TAMING_GPT, synth.TAMING_VQ, seed=0, device=device,
-                                                max_batch=min(args.batch_size, 128))
-        else:
-            model = TamingARMMWrapper(args.modelpath, device=device, max_batch=min(args.batch_size, 128))
-    elif args.model == "rar":
-        if args.synthetic:
-            model = RarARMMWrapper.synthetic(device=device, max_batch=min(args.batch_size, 64))
-        else:
-            model = RarARMMWrapper(args.modelpath, device=device, max_batch=min(args.batch_size, 64))
-    else:
-        if args.synthetic:
-            model = ChameleonARMMWrapper.synthetic(seed=seed, device=device, max_batch=min(args.batch_size, 16))
-        else:
-            model = ChameleonARMMWrapper(args.modelpath, seed, device=device, max_batch=min(args.batch_size, 16))
-    model.noise_device = args.noise_device
-    # Patch model: enc and/or dec (the reference's own calls, generate.py:327-332; all three tokenizers expose the handles)
-    if args.encoder_ft_ckpt is not None and args.encoder_ft_ckpt != "none":
-        update_weights(model.get_image_tokenizer().encoder, args.encoder_ft_ckpt)
-    if args.decoder_ft_ckpt is not None and args.decoder_ft_ckpt != "none":
-        update_weights(model.get_image_tokenizer().decoder, args.decoder_ft_ckpt)
+    model = cli.build_model(args, device, seed)
 
     if ".txt" in args.conditioning:      # file with prompts (Chameleon): (index, prompt) tuples
         with open(args.conditioning, "r") as f:
@@ -153,19 +121,9 @@ def main():
                 and args.wm_split_strategy == "stratifiedrand"), \
             "Chameleon and RAR models only support none or gentime watermarking with fixed/linear seed and stratifiedrand split"
 
-    vocab_size = model.get_total_vocab_size()
-    watermarker = None
-    if args.wm_method == "gentime":
-        watermarker = GentimeWatermark(model.get_vq(), vocab_size, SeedStrategy(args.wm_seed_strategy),
-                                       SplitStrategy(args.wm_split_strategy), args.wm_context_size, args.wm_delta,
-                                       args.wm_gamma, model.device)
-        if world > 1:  # build the key once, broadcast it over RCCL
-            harness.broadcast_key_table(watermarker, device)
-    elif args.wm_method == "gumbel":
-        # RAR ignores gen_params (as in the reference): temperature 1.0, no top-p / top-k (--top_k / --top_p default to Taming's)
-        from wmar_amd.watermarking.gumbel_watermark import GumbelWatermark
-        watermarker = GumbelWatermark(vocab_size, seed=args.wm_gumbel_seed, temperature=1.0, top_p=0.0, top_k=0, device=model.device,
-                                      ngram=args.wm_context_size)
+    watermarker = cli.build_watermarker(args, model)
+    if args.wm_method == "gentime" and world > 1:  # build the key once, broadcast it over RCCL
+        harness.broadcast_key_table(watermarker, device)
     model.set_watermarker(watermarker)
 
     # evaluation transforms: the classic ones run batched on the GPU; neural codecs and DiffPure are outside this build

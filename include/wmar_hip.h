@@ -10,7 +10,8 @@
  *     wmar_last_error() returns a human-readable message for the calling thread.
  *   - engines allocate in *_create; afterwards only small per-call scratch is allocated (prompt tables of
  *     wmar_cham_generate_image, the one-off unconditional adaLN table of wmar_rar_generate, a status word of
- *     wmar_gumbel_score / wmar_gumbel_score_ctx).
+ *     wmar_gumbel_score / wmar_gumbel_score_ctx); wmar_image_ingest keeps one scratch buffer per device between calls and
+ *     grows it to the largest batch seen (coefficient tables + 8-bit intermediate: rows x target x 3 bytes per image).
  *   - an engine handle (wmar_gpt / wmar_rar / wmar_cham / wmar_vq / wmar_mvq) is NOT thread-safe: it owns
  *     its workspaces, KV cache and captured graphs; use it from one thread and one stream at a time
  *     (the reference is single-threaded per model too).
@@ -439,6 +440,35 @@ int wmar_augment(int32_t op, const float* in_dev, float* out_dev, const float* n
 int64_t wmar_jpeg_workspace_bytes(int64_t B, int32_t H, int32_t W);
 int wmar_jpeg(const float* in_dev, float* out_dev, void* workspace_dev, int64_t workspace_bytes, int64_t B, int32_t H, int32_t W,
               int32_t quality, int32_t pm1, int32_t passthrough, void* stream);
+
+/* ------------------------------------------------------------------------ image ingest
+ * ImageTokenizer.img_tokens_from_pil up to the VQGAN (deps/chameleon/inference/image_tokenizer.py:51-98): _whiten_transparency, then
+ * _vqgan_input_from = PIL's resize(LANCZOS) to short side `target`, centre crop, u8 / 255 * 2 - 1 -- for a batch of 8-bit images of
+ * any sizes, bit for bit what PIL returns (Pillow's 8-bit resample is integer arithmetic on coefficient tables built in double).
+ *
+ * wmar_resample_coeffs (host only): Pillow's LANCZOS tables for one axis of in_size -> out_size pixels and the output window
+ * [out0, out0 + n_out): first input pixel xmin_out and tap count count_out, int32 [n_out] each; 22-bit fixed-point weights k_out int32
+ * [n_out * ksize] (row i = the taps of output out0 + i, zero beyond its count); *ksize_out = ceil(support) * 2 + 1.  k_capacity:
+ * entries k_out holds; in_size up to 32768. */
+int wmar_resample_coeffs(int32_t in_size, int32_t out_size, int32_t out0, int32_t n_out, int32_t* xmin_out, int32_t* count_out,
+                         int32_t* k_out, int32_t k_capacity, int32_t* ksize_out);
+
+/* One image of a batch: `offset` bytes into the pixel buffer, width x height pixels of `channels` bytes, row-major (HWC).  The resized
+ * size and the crop origin are the caller's: the reference computes them with Python's round() (half to even) and //. */
+typedef struct wmar_image_desc {
+    int64_t offset;
+    int32_t width, height, channels; /* 3 = RGB, 4 = RGBA (blended over white first) */
+    int32_t new_width, new_height, crop_x0, crop_y0;
+} wmar_image_desc;
+
+/* pixels_dev: uint8 images back to back, 4-byte aligned, pixels_bytes in total; desc_host: n descriptors on the host, every one
+ * validated against pixels_bytes and its own resized size (sides 1..32768, channels 3 | 4, crop window of target x target inside the
+ * resized image) BEFORE anything is launched: WMAR_EINVAL names the image.  out_dev float [n, 3, target, target] in [-1, 1];
+ * out_u8_dev (nullable) uint8 [n, target, target, 3], the cropped 8-bit image.  Only the crop window is computed.  Two launches per
+ * batch.  The tables and the 8-bit intermediate between the passes live in a per-device scratch buffer the library keeps and grows
+ * (the whitening table is uploaded when it is allocated); the call waits for its launches, and calls on one device take turns. */
+int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n, int32_t target,
+                      float* out_dev, uint8_t* out_u8_dev, void* stream);
 
 /* ------------------------------------------------------------------------ exchange step (RCCL over xGMI)
  * The sharded job (one process per GPU; rank r == the reference's `--chunk_id r --num_chunks world`, generate.py:204, :304) has no

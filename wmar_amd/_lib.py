@@ -23,7 +23,7 @@ SYMBOLS = [
     "wmar_mvq_encode", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
     "wmar_cham_create", "wmar_cham_destroy", "wmar_cham_device_bytes", "wmar_cham_forward_tokens", "wmar_cham_generate_image",
     "wmar_cham_sample",
-    "wmar_augment", "wmar_jpeg_workspace_bytes", "wmar_jpeg",
+    "wmar_augment", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
 
@@ -83,6 +83,11 @@ class ChamSampleParams(C.Structure):
                 ("guidance_scale_image", C.c_float), ("use_graph", C.c_int32), ("pad_id", C.c_int32)]
 
 
+class ImageDesc(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("new_width", C.c_int32), ("new_height", C.c_int32), ("crop_x0", C.c_int32), ("crop_y0", C.c_int32)]
+
+
 class WmarError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libwmar_hip: {msg} (status {code})")
@@ -123,6 +128,8 @@ def load():
     L.wmar_jpeg_workspace_bytes.restype = i64
     L.wmar_jpeg_workspace_bytes.argtypes = [i64, i32, i32]
     L.wmar_jpeg.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp]
+    L.wmar_resample_coeffs.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, C.POINTER(i32)]
+    L.wmar_image_ingest.argtypes = [vp, i64, C.POINTER(ImageDesc), i64, i32, vp, vp, vp]
     L.wmar_comm_unique_id.argtypes = [vp, i64]
     L.wmar_comm_init.argtypes = [vp, i64, i32, i32, C.POINTER(vp)]
     L.wmar_comm_bcast.argtypes = [vp, vp, i64, i32, vp]

@@ -24,6 +24,7 @@ SOURCES = [
     ("vqgan.hip", []),
     ("augment.hip", ["-ffp-contract=off"]),
     ("jpeg.hip", ["-ffp-contract=off"]),
+    ("ingest.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-x", "hip"]

@@ -1,0 +1,58 @@
+"""What the command-line entry points share: the model and the watermarker as the flags of ``generate.get_parser`` describe them
+(the reference's dispatch, generate.py:319-345).  ``generate.py`` generates with them, ``detect.py`` detects."""
+from __future__ import annotations
+
+
+def build_model(args, device, seed):
+    """The wrapper of ``--model`` (checkpoints from ``--modelpath``, or seeded random-init weights with ``--synthetic``) with the
+    tokenizer patches of ``--encoder_ft_ckpt`` / ``--decoder_ft_ckpt`` applied."""
+    from .models.chameleon_wrapper import ChameleonARMMWrapper
+    from .models.rar_wrapper import RarARMMWrapper
+    from .models.taming_wrapper import TamingARMMWrapper
+    from .utils import synth
+    from .utils.utils import update_weights
+
+    if args.model == "taming":
+        if args.synthetic and args.synthetic_config == "harness":
+            gcfg, vcfg = synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)
+            model = TamingARMMWrapper(None, gpt_cfg=gcfg, vq_cfg=vcfg, gpt_state=synth.synth_gpt_state(gcfg, 21, "cpu", 40.0),
+                                      vq_state=synth.synth_vq_state(vcfg, 21, "cpu"), device=device,
+                                      max_batch=min(args.batch_size, 128))
+        elif args.synthetic:
+            model = TamingARMMWrapper.synthetic(synth.TAMING_GPT, synth.TAMING_VQ, seed=0, device=device,
+                                                max_batch=min(args.batch_size, 128))
+        else:
+            model = TamingARMMWrapper(args.modelpath, device=device, max_batch=min(args.batch_size, 128))
+    elif args.model == "rar":
+        if args.synthetic:
+            model = RarARMMWrapper.synthetic(device=device, max_batch=min(args.batch_size, 64))
+        else:
+            model = RarARMMWrapper(args.modelpath, device=device, max_batch=min(args.batch_size, 64))
+    else:
+        if args.synthetic:
+            model = ChameleonARMMWrapper.synthetic(seed=seed, device=device, max_batch=min(args.batch_size, 16))
+        else:
+            model = ChameleonARMMWrapper(args.modelpath, seed, device=device, max_batch=min(args.batch_size, 16))
+    model.noise_device = args.noise_device
+    # Patch model: enc and/or dec (the reference's own calls, generate.py:327-332; all three tokenizers expose the handles)
+    if args.encoder_ft_ckpt is not None and args.encoder_ft_ckpt != "none":
+        update_weights(model.get_image_tokenizer().encoder, args.encoder_ft_ckpt)
+    if args.decoder_ft_ckpt is not None and args.decoder_ft_ckpt != "none":
+        update_weights(model.get_image_tokenizer().decoder, args.decoder_ft_ckpt)
+    return model
+
+
+def build_watermarker(args, model):
+    """The watermarker of ``--wm_method`` over the model's vocabulary (None for ``none``)."""
+    vocab_size = model.get_total_vocab_size()
+    if args.wm_method == "gentime":
+        from .watermarking.gentime_watermark import GentimeWatermark, SeedStrategy, SplitStrategy
+        return GentimeWatermark(model.get_vq(), vocab_size, SeedStrategy(args.wm_seed_strategy),
+                                SplitStrategy(args.wm_split_strategy), args.wm_context_size, args.wm_delta,
+                                args.wm_gamma, model.device)
+    if args.wm_method == "gumbel":
+        # RAR ignores gen_params (as in the reference): temperature 1.0, no top-p / top-k (--top_k / --top_p default to Taming's)
+        from .watermarking.gumbel_watermark import GumbelWatermark
+        return GumbelWatermark(vocab_size, seed=args.wm_gumbel_seed, temperature=1.0, top_p=0.0, top_k=0, device=model.device,
+                               ngram=args.wm_context_size)
+    return None

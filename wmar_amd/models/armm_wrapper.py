@@ -73,6 +73,23 @@ class AutoregressiveMultimodalModelWrapper:
         vq.alive_ids = torch.tensor(alive, dtype=torch.long)
         vq.dead_ids = torch.tensor(dead, dtype=torch.long)
 
+    # ---- images that did not come from this build (files, photos, RGBA): an EXTENSION for Taming and RAR -- the reference has the
+    # PIL entry only for Chameleon (ImageTokenizer.img_tokens_from_pil, deps/chameleon/inference/image_tokenizer.py:94-98); the same
+    # steps (blend over white, LANCZOS resize of the short side, centre crop, u8 / 255 * 2 - 1) at the model's own image_size
+    def images_from_pil(self, images):
+        """PIL images / paths / ``file:`` / ``data:`` strings / uint8 HWC arrays of any sizes -> float32
+        [n, 3, image_size, image_size] in [-1, 1] on the model's device, bit for bit the reference's PIL path
+        (wmar_amd.utils.ingest: one device call per batch)."""
+        from ..utils.ingest import ingest
+        return ingest(list(images), self.image_size, self.model.device)
+
+    def codes_from_pil(self, images):
+        """``images_from_pil`` + the tokenizer's encoder: codes [n, codes_size**2], in the id space ``images_to_codes`` returns."""
+        return self._encode_ingested(self.images_from_pil(images))
+
+    def _encode_ingested(self, x):
+        return self.images_to_codes(x)
+
     # ---- shape rules
     def is_codes_shaped(self, codes):
         n = self.codes_size * self.codes_size

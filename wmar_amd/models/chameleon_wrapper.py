@@ -137,14 +137,61 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
         return len(self.vocab.all_tokens)
 
     # ---- prompt handling
+    def _encode_ingested(self, x):
+        # the ingested tensor already sits on the 8-bit grid: straight to the encoder, as img_tokens_from_pil does
+        # (image_tokenizer.py:94-98), not through images_to_codes' own 8-bit round trip
+        return self.translation.convert_img2bp2(self.vq_engine.encode(x)).to(torch.int64)
+
+    def tokenize_images(self, images) -> List[List[int]]:
+        """``tokenize_image`` for several images through ONE ingest call (and the chunked encoder)."""
+        if not images:
+            return []
+        codes = self.codes_from_pil(images).tolist()
+        return [[self.vocab.begin_image] + c + [self.vocab.end_image] for c in codes]
+
+    def tokenize_image(self, img) -> List[int]:
+        """TokenManager.tokenize_image (chameleon.py:131-138): [boi] + img2bpe(codes of the image) + [eoi]."""
+        return self.tokenize_images([img])[0]
+
+    def tokenize_b64img(self, b64img: str) -> List[int]:
+        """TokenManager.tokenize_b64img (chameleon.py:140-143)."""
+        import base64
+        import io
+        from PIL import Image
+        return self.tokenize_image(Image.open(io.BytesIO(base64.b64decode(b64img))))
+
+    @staticmethod
+    def _ui_image(value):
+        """The value of an {"type": "image"} entry as something ingest opens; the reference's checks and error strings
+        (chameleon.py:150-164)."""
+        from PIL import Image
+        if isinstance(value, str):
+            if value.startswith("data:") or value.startswith("file:"):
+                return value
+            raise ValueError("Unknown image format.")
+        if isinstance(value, Image.Image):
+            return value
+        raise ValueError("Unknown image type.")
+
+    def tokens_from_ui_batch(self, prompts: List[List[dict]]) -> List[List[int]]:
+        """``tokens_from_ui`` for a batch of prompts: every image of every prompt goes through one ingest call."""
+        images = [self._ui_image(inp["value"]) for inputs in prompts for inp in inputs if inp["type"] == "image"]
+        image_tokens = iter(self.tokenize_images(images))
+        return [self._tokens_from_ui(inputs, image_tokens) for inputs in prompts]
+
     def tokens_from_ui(self, inputs: List[dict]) -> List[int]:
-        """TokenManager.tokens_from_ui (chameleon.py:139-172) for text / sentinel / ids entries."""
+        """TokenManager.tokens_from_ui (chameleon.py:139-172): text / image / sentinel / ids entries."""
+        return self.tokens_from_ui_batch([inputs])[0]
+
+    def _tokens_from_ui(self, inputs: List[dict], image_tokens) -> List[int]:
         tokens = [self.vocab.bos_id]
         for inp in inputs:
             if inp["type"] == "text":
                 if self.tokenizer is None:
                     raise RuntimeError("no text tokenizer loaded: pass prompts as {'type': 'ids', 'value': [...]}")
                 tokens += self.tokenizer.encode(inp["value"]).ids
+            elif inp["type"] == "image":
+                tokens += next(image_tokens)
             elif inp["type"] == "sentinel":
                 tokens += [{"<START-OF-IMAGE>": self.vocab.begin_image, "<END-OF-TURN>": self.vocab.eot_id}[inp["value"]]]
             elif inp["type"] == "ids":
@@ -311,12 +358,17 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
             q[n].copy_(self._noise_draw(lambda t, g: t.exponential_(1, generator=g), (B, V), generator))
         return q
 
-    # conditioning: list of (index, prompt) tuples (prompt: str, or a list of token ids); gen_params: {top_p, temperature}
+    # conditioning: list of (index, prompt) tuples (prompt: str, a list of token ids, or a list of tokens_from_ui entries -- text, image,
+    # ids, sentinel dicts -- for a prompt that holds images); gen_params: {top_p, temperature}
     def sample(self, conditioning, gen_params, apply_watermark=False, q: Optional[torch.Tensor] = None):
-        prompts = []
+        ui = []
         for _, prompt in conditioning:
-            item = {"type": "text", "value": prompt} if isinstance(prompt, str) else {"type": "ids", "value": prompt}
-            prompts.append(self.tokens_from_ui([item, {"type": "sentinel", "value": "<END-OF-TURN>"}]))
+            if isinstance(prompt, (list, tuple)) and prompt and isinstance(prompt[0], dict):
+                items = list(prompt)
+            else:
+                items = [{"type": "text", "value": prompt} if isinstance(prompt, str) else {"type": "ids", "value": prompt}]
+            ui.append(items + [{"type": "sentinel", "value": "<END-OF-TURN>"}])
+        prompts = self.tokens_from_ui_batch(ui)
         B = len(prompts)
         dev = self.model.device
         out = torch.empty(B, self.n_image_tokens, dtype=torch.int64, device=dev)
