@@ -6,8 +6,8 @@ Takes the model and watermark flags of ``generate.py`` (the key must be the one 
     --images DIR | FILE [FILE ...]   --batch_size N   --out results.json
 
 and writes one JSON list in sorted file order: ``file``, ``width``, ``height``, ``pvalue`` and the detector's counts
-(``n_scored``, and ``n_green`` for the greenlist watermark); a file PIL cannot open gets ``error`` instead, the rest are processed and
-the exit status is 1.
+(``n_scored``, and ``n_green`` for the greenlist watermark; none for a ``--wm_method custom`` watermarker that only offers the
+reference's ``detect``); a file PIL cannot open gets ``error`` instead, the rest are processed and the exit status is 1.
 """
 import json
 import os
@@ -33,6 +33,9 @@ def list_images(images):
 
 def detect_codes(watermarker, codes):
     """pvalue (float64 [n]) and whatever counts the watermarker exposes, as lists per image."""
+    if not hasattr(watermarker, "detect_counts"):   # a reference-style watermarker: detect(codes) -> float64 [B], no counts
+        import torch
+        return torch.as_tensor(watermarker.detect(codes)).reshape(-1).cpu().tolist(), {}
     res = watermarker.detect_counts(codes)          # (pvalue, n_scored[, n_green])
     counts = dict(zip(("n_scored", "n_green"), (t.cpu().tolist() for t in res[1:])))
     return res[0].cpu().tolist(), counts
@@ -78,7 +81,7 @@ def main():
     if not args.out:
         parser.error("--out is required")
     if args.wm_method in (None, "none"):
-        parser.error("--wm_method: a watermark to look for is required (gentime | gumbel)")
+        parser.error("--wm_method: a watermark to look for is required (gentime | gumbel | custom)")
     assert args.model in ("taming", "rar", "chameleon7b"), f"Model {args.model} not supported"
 
     import torch

@@ -43,7 +43,10 @@ def get_parser():
     parser.add_argument("--orig_only", type=str2bool, nargs="?", help="orig only", default=False)
     parser.add_argument("--include_neural_compress", type=str2bool, nargs="?", help="include NC", default=True)
     parser.add_argument("--include_diffpure", type=str2bool, nargs="?", help="include diffpure", default=True)
-    parser.add_argument("--wm_method", type=str, nargs="?", help="method", choices=["none", "gentime", "gumbel"])
+    parser.add_argument("--wm_method", type=str, nargs="?", help="method", choices=["none", "gentime", "gumbel", "custom"])
+    parser.add_argument("--wm_factory", type=str, default=None,
+                        help="with --wm_method custom: 'pkg.module:callable'; callable(model, args) returns a reference-style watermarker "
+                             "(spawn_logit_processor(), detect(codes) -> float64 [B], __str__), run through the engines' hooked mode")
     parser.add_argument("--wm_seed_strategy", type=str, nargs="?", help="", choices=["fixed", "linear", "spatial"])
     parser.add_argument("--wm_split_strategy", type=str, nargs="?", help="", choices=["rand", "stratifiedrand", "clustering"])
     parser.add_argument("--wm_context_size", type=int, nargs="?", help="context size", default=0)
@@ -71,6 +74,13 @@ def check_wm_args(args):
         raise ValueError(f"--wm_method gumbel needs --model rar: {args.model} has no Gumbel-key generation loop")
     if args.wm_method == "gumbel" and not 0 <= args.wm_context_size <= 16:
         raise ValueError("--wm_method gumbel: --wm_context_size (the ngram of the key) must be in 0..16")
+    factory = getattr(args, "wm_factory", None)
+    if args.wm_method == "custom" and not factory:
+        raise ValueError("--wm_method custom needs --wm_factory pkg.module:callable")
+    if factory and args.wm_method != "custom":
+        raise ValueError("--wm_factory is only read with --wm_method custom")
+    if factory and (factory.count(":") != 1 or not all(factory.split(":"))):
+        raise ValueError(f"--wm_factory {factory!r}: expected pkg.module:callable")
 
 
 def main():
@@ -114,8 +124,8 @@ def main():
         text = model.vocab.text_tokens
         conditionings = [(c, [text[(c * 37 + j * 11) % len(text)] for j in range(12 + c % 5)]) for c in conditionings]
     all_inputs = [c for c in conditionings for _ in range(args.num_samples_per_conditioning)]
-    if args.model == "rar" and args.wm_method == "gumbel":
-        pass      # the Gumbel key has no seed / split strategy
+    if (args.model == "rar" and args.wm_method == "gumbel") or args.wm_method == "custom":
+        pass      # the Gumbel key has no seed / split strategy; a custom watermarker reads what it wants from args
     elif "chameleon" in args.model or "rar" in args.model:
         assert (args.wm_method in ["none", "gentime"] and args.wm_seed_strategy in ["linear", "fixed"]
                 and args.wm_split_strategy == "stratifiedrand"), \

@@ -37,6 +37,7 @@ extern "C" {
 #define WMAR_MAX_CONTEXT 16
 #define WMAR_ENOMEM (-4)
 #define WMAR_EMISSING (-5) /* a required checkpoint tensor is missing      */
+#define WMAR_ECALLBACK (-6) /* a wmar_logits_hook returned non-zero: the run was stopped */
 
 /* enum values of wmar.watermarking.gentime_watermark.SeedStrategy / SplitStrategy (:95-106) */
 #define WMAR_SEED_FIXED 0
@@ -159,6 +160,35 @@ int wmar_gpt_generate(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_sample_para
                       int64_t B, int32_t steps, const float* q_dev, int64_t* tokens_out_dev,
                       float* logits_trace_dev, void* stream);
 
+/* ------------------------------------------------------------------------ hooked generation
+ * The reference's loops hand the logits of every step to an arbitrary `logit_processor` (mingpt.py:348-350, rar.py:450-451,
+ * generation.py:86).  The *_hooked entry points below run the same captured step as their fused siblings, cut in two where the
+ * reference calls the processor:
+ *   graph A   the model step (+ wmar_cfg_mix where the model runs under guidance) -> logits_io_dev float [B, V]
+ *   hook      hook(user, step, t) on the calling thread; everything it enqueues on `stream` is ordered between the two graphs;
+ *             t = valid columns of past_io_dev int64 [B, past_stride].  No host synchronisation.
+ *   graph B   k_sample_fused without watermark on logits_io_dev; token -> past_io_dev[:, t] and tokens_out_dev[:, step]; counters + 1
+ * Both buffers are the caller's.  A non-zero return of the hook stops the run: WMAR_ECALLBACK, the engine stays usable.  The
+ * in-launch barrier check is made once behind the last step (as in the fused calls): a run that raised the flag is repeated, and
+ * the hook is then called again from step 0 -- it must be a function of its arguments.  The graphs of this mode live in slots of
+ * their own: alternating fused and hooked calls re-captures neither. */
+typedef int (*wmar_logits_hook)(void* user, int32_t step, int64_t t);
+
+/* Guidance as a launch of its own (inside the fused sampler otherwise), fp32 [B, V] -> out_dev [B, V]; the arithmetic is the fused
+ * sampler's, operation for operation:
+ *   img_dev == NULL:  out = uncond + (cond - uncond) * scale_dev[step_dev ? *step_dev : 0]          (rar.py:437-442)
+ *   else:             out = uncond + g_image * (img - uncond) + g_text * (cond - img)               (logits_processor.py:312-336)
+ * 16-byte vector accesses when V % 4 == 0 and the four pointers are 16-byte aligned, scalar otherwise.  V <= 65536 is what the
+ * engines use; any V < 2^31 is accepted. */
+int wmar_cfg_mix(const float* cond_dev, const float* img_dev, const float* uncond_dev, float* out_dev, int64_t B, int64_t V,
+                 const float* scale_dev, const int32_t* step_dev, float g_text, float g_image, void* stream);
+
+/* sample_with_past with a host processor.  past_io_dev rows: the class token, then the generated tokens (mingpt.py:329,350):
+ * t = step + 1, past_stride >= steps + 1.  logits_io_dev = the raw head output. */
+int wmar_gpt_generate_hooked(wmar_gpt* g, const wmar_sample_params* sp, const int64_t* cond_dev, int64_t B, int32_t steps,
+                             const float* q_dev, int64_t* tokens_out_dev, float* logits_io_dev, int64_t* past_io_dev,
+                             int64_t past_stride, wmar_logits_hook hook, void* user, void* stream);
+
 /* Per-kernel-class device times of the last wmar_gpt_generate call, measured with HIP events
  * recorded on the caller's stream around every launch.  Only available for eager runs
  * (use_graph = 0) after wmar_gpt_set_timing(g, 1); used by bench.py for the roofline line.
@@ -235,6 +265,13 @@ int wmar_rar_forward_position(wmar_rar* g, const int64_t* tok_dev, const int64_t
 int wmar_rar_generate(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,
                       const float* cfg_scale_host, int32_t use_guidance, float temperature, const float* q_dev,
                       int64_t* tokens_out_dev, int32_t use_graph, void* stream);
+
+/* RAR.generate with a host processor (see "hooked generation" above).  past_io_dev rows: the generated tokens only, t = step
+ * (empty at the first step, rar.py:420,451), past_stride >= image_seq_len.  logits_io_dev = after guidance, before temperature. */
+int wmar_rar_generate_hooked(wmar_rar* g, const int64_t* class_ids_dev, int64_t B, const float* cfg_scale_host,
+                             int32_t use_guidance, float temperature, const float* q_dev, int64_t* tokens_out_dev,
+                             int32_t use_graph, float* logits_io_dev, int64_t* past_io_dev, int64_t past_stride,
+                             wmar_logits_hook hook, void* user, void* stream);
 
 /* RAR generation with the Gumbel-key sampler below instead of multinomial + greenlist (BASELINE
  * config "RAR-XL ... Gumbel-key watermark"; an EXTENSION -- the reference image code has no such
@@ -359,6 +396,16 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
                              const int32_t* prompt_lens_host, int64_t B, const wmar_cham_sample_params* sp,
                              const uint32_t* allow_dev, const int32_t* allow_ids_dev, int32_t n_allow, const float* q_dev,
                              int32_t n_tokens, int64_t* tokens_out_dev, void* stream);
+
+/* The same with a host processor (see "hooked generation" above): guidance mix (wmar_cfg_mix) -> hook -> allow-only -> temperature
+ * -> top-p -> multinomial (chameleon.py:313-327).  past_io_dev rows: the first stream's whole prompt, left-padded with pad_id to the
+ * longest of the 3B prompts (P entries), then the generated tokens: t = P + step, past_stride >= P + n_tokens.  The reference hands
+ * its processors all 3B rows and samples from the first third (token_selector.py:34-47); here the processor sees that third only. */
+int wmar_cham_generate_image_hooked(wmar_cham* g, const int64_t* prompt_tokens_host, const int32_t* prompt_lens_host, int64_t B,
+                                    const wmar_cham_sample_params* sp, const uint32_t* allow_dev, const int32_t* allow_ids_dev,
+                                    int32_t n_allow, const float* q_dev, int32_t n_tokens, int64_t* tokens_out_dev,
+                                    float* logits_io_dev, int64_t* past_io_dev, int64_t past_stride, wmar_logits_hook hook,
+                                    void* user, void* stream);
 
 /* The ImageDecoder logits pipeline of one step as ONE launch (chameleon.py:313-327, generation.py:84-93):
  * logits3_dev float [3B, V] = [full | image-conditioned | unconditioned] rows; guidance mix

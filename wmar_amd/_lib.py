@@ -23,11 +23,16 @@ SYMBOLS = [
     "wmar_mvq_encode", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
     "wmar_cham_create", "wmar_cham_destroy", "wmar_cham_device_bytes", "wmar_cham_forward_tokens", "wmar_cham_generate_image",
     "wmar_cham_sample",
+    "wmar_cfg_mix", "wmar_gpt_generate_hooked", "wmar_rar_generate_hooked", "wmar_cham_generate_image_hooked",
     "wmar_augment", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
 
 WMAR_ESHORT = -3
+WMAR_ECALLBACK = -6
+
+# wmar_logits_hook (include/wmar_hip.h): int (*)(void* user, int32_t step, int64_t t)
+LOGITS_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64)
 
 
 class KeyParams(C.Structure):
@@ -185,6 +190,11 @@ def load():
     L.wmar_cham_forward_tokens.argtypes = [vp, vp, vp, i64, vp, vp]
     L.wmar_cham_generate_image.argtypes = [vp, C.POINTER(WmCtx), vp, vp, i64, C.POINTER(ChamSampleParams), vp, vp, i32, vp, i32, vp, vp]
     L.wmar_cham_sample.argtypes = [C.POINTER(WmCtx), vp, i64, i64, vp, i64, i64, f32, f64, f32, f32, vp, vp, i32, vp, vp, vp, vp]
+    L.wmar_cfg_mix.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, f32, f32, vp]
+    L.wmar_gpt_generate_hooked.argtypes = [vp, C.POINTER(SampleParams), vp, i64, i32, vp, vp, vp, vp, i64, LOGITS_HOOK, vp, vp]
+    L.wmar_rar_generate_hooked.argtypes = [vp, vp, i64, C.POINTER(f32), i32, f32, vp, vp, i32, vp, vp, i64, LOGITS_HOOK, vp, vp]
+    L.wmar_cham_generate_image_hooked.argtypes = [vp, vp, vp, i64, C.POINTER(ChamSampleParams), vp, vp, i32, vp, i32, vp, vp, vp, i64,
+                                                  LOGITS_HOOK, vp, vp]
     L.wmar_mvq_create.argtypes = [C.POINTER(MvqConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
     L.wmar_mvq_destroy.argtypes = [vp]
     L.wmar_mvq_destroy.restype = None

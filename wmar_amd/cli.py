@@ -55,4 +55,10 @@ def build_watermarker(args, model):
         from .watermarking.gumbel_watermark import GumbelWatermark
         return GumbelWatermark(vocab_size, seed=args.wm_gumbel_seed, temperature=1.0, top_p=0.0, top_k=0, device=model.device,
                                ngram=args.wm_context_size)
+    if args.wm_method == "custom":
+        # a reference-style watermarker from the user's own code: spawn_logit_processor(), detect(codes), __str__ -- the wrappers run
+        # its processor through the engines' hooked generation mode
+        import importlib
+        module, _, name = args.wm_factory.partition(":")
+        return getattr(importlib.import_module(module), name)(model, args)
     return None

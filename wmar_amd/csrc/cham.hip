@@ -49,6 +49,10 @@ struct wmar_cham {
     // wmar_cham_generate_image waits for its stream before it returns (it frees the prompt tables): no replay outlives the call,
     // so it never marks the graph as replaying
     GraphSlots<1> gr;
+    // hooked generation (wmar_cham_generate_image_hooked): graph A (token bookkeeping + model step + guidance mix) and graph B
+    // (sampler + counters) in slots and under a key of their own: kept across calls, untouched by the fused calls
+    GraphSlots<2> grh;
+    unsigned long long hook_key[16] = {0};
 };
 
 namespace {
@@ -288,6 +292,7 @@ int wmar_cham_create(const wmar_cham_config* cfg, const char* const* names, cons
         rc = launch_status("k_rope_table");
     }
     WMAR_TRY(g->gr.init());
+    WMAR_TRY(g->grh.init());
     if (rc == WMAR_OK) {
         const hipError_t er = hipStreamSynchronize(st);
         if (er != hipSuccess) { set_error("cham_create: %s", hipGetErrorString(er)); rc = WMAR_EHIP; }
@@ -311,10 +316,10 @@ int wmar_cham_forward_tokens(wmar_cham* g, const int64_t* tok_dev, const int32_t
     return p.step(logits_dev != nullptr, logits_dev);
 }
 
-int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t* prompt_tokens_host,
-                             const int32_t* prompt_lens_host, int64_t B, const wmar_cham_sample_params* sp,
-                             const uint32_t* allow_dev, const int32_t* allow_ids_dev, int32_t n_allow, const float* q_dev,
-                             int32_t n_tokens, int64_t* tokens_out_dev, void* stream) {
+static int cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t* prompt_tokens_host,
+                               const int32_t* prompt_lens_host, int64_t B, const wmar_cham_sample_params* sp,
+                               const uint32_t* allow_dev, const int32_t* allow_ids_dev, int32_t n_allow, const float* q_dev,
+                               int32_t n_tokens, int64_t* tokens_out_dev, void* stream, const HookIO* hk) {
     WMAR_REQUIRE(g && prompt_tokens_host && prompt_lens_host && sp && q_dev && tokens_out_dev, "cham_generate_image: null argument");
     WMAR_REQUIRE(B >= 1 && 3 * B <= g->Mmax, "cham_generate_image: batch %lld needs %lld rows, engine has %d", (long long)B,
                  (long long)(3 * B), g->Mmax);
@@ -332,11 +337,19 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
     }
     WMAR_REQUIRE(maxlen + n_tokens <= g->T, "cham_generate_image: %d prompt + %d image tokens exceed max_seq_len %d", maxlen,
                  n_tokens, g->T);
-    g->gr.drop();
+    if (hk) {
+        WMAR_REQUIRE(hk->logits && hk->past && hk->hook && !wm, "cham_generate_image_hooked: null argument");
+        WMAR_REQUIRE(hk->past_stride >= (long long)maxlen + n_tokens, "cham_generate_image_hooked: past_stride %lld below prompt %d + image tokens %d",
+                     hk->past_stride, maxlen, n_tokens);
+    } else {
+        g->gr.drop();
+    }
     // right-aligned prompt tables (alignment.py:27-52): row m idles (token 0 at position 0) until its prompt starts
     // the watermark sees the whole padded row: keep its last CTX entries (prompt tokens, pad_id where the row is still padding)
-    const int CTX = maxlen < 3 ? maxlen : 3;
-    std::vector<long long> tt((size_t)maxlen * M), first_ctx((size_t)B * 3, 0);
+    // (hooked mode: the processor sees the whole padded row of the first stream, generation.py:86)
+    const int CTX = hk ? maxlen : (maxlen < 3 ? maxlen : 3);
+    const int CW = hk ? maxlen : 3;       // row width of first_ctx
+    std::vector<long long> tt((size_t)maxlen * M), first_ctx((size_t)B * CW, 0);
     std::vector<int> tp((size_t)maxlen * M);
     size_t off = 0;
     for (int m = 0; m < M; ++m) {
@@ -351,7 +364,7 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
         if (m < B)
             for (int c = 0; c < CTX; ++c) {
                 const int i = len - CTX + c;
-                first_ctx[(size_t)m * 3 + c] = i >= 0 ? prompt_tokens_host[off + i] : (long long)sp->pad_id;
+                first_ctx[(size_t)m * CW + c] = i >= 0 ? prompt_tokens_host[off + i] : (long long)sp->pad_id;
             }
         off += len;
     }
@@ -367,8 +380,9 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
     hipError_t e = hipMemcpyAsync(tab_tok, tt.data(), tt.size() * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(tab_pos, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, st);
     // the watermark context is the whole input row: the tail of the padded prompt, then the generated tokens
-    const long long ids_stride = g->T + 4;
-    if (e == hipSuccess) e = hipMemcpy2DAsync(g->ids, ids_stride * 8, first_ctx.data(), 3 * 8, (size_t)CTX * 8, (size_t)B, hipMemcpyHostToDevice, st);
+    const long long ids_stride = hk ? hk->past_stride : g->T + 4;
+    long long* ids = hk ? hk->past : g->ids;
+    if (e == hipSuccess) e = hipMemcpy2DAsync(ids, ids_stride * 8, first_ctx.data(), (size_t)CW * 8, (size_t)CTX * 8, (size_t)B, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { set_error("cham_generate_image: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
     ChamPlan p(g, M, st);
@@ -382,13 +396,15 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
 
     SampArgs a{};
     a.wm = make_wm(wm);
-    a.logits = g->logits; a.V = V; a.past = g->ids; a.past_stride = ids_stride; a.t_dev = g->ctr + 2;
+    a.logits = hk ? hk->logits : g->logits; a.V = V; a.past = ids; a.past_stride = ids_stride; a.t_dev = g->ctr + 2;
     a.temperature = sp->temperature; a.top_k = 0; a.use_top_p = sp->top_p >= 0; a.top_p_thr = (float)(1.0 - sp->top_p);
     a.q = q_dev; a.q_step_stride = (long long)B * V; a.step_dev = g->ctr + 1;
     a.scratch = a.V > 65536 ? g->scratch : nullptr;   /* rows up to 65536 entries live in the sampler's registers */
     a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = n_tokens;
-    a.past_append = g->ids; a.trace = nullptr; a.B = B;
-    a.logits_img = g->logits + (long long)B * V; a.logits_uncond = g->logits + 2ll * B * V;
+    a.past_append = ids; a.trace = nullptr; a.B = B;
+    // hooked mode: the guidance mix has left the sampler (k_cfg_mix in front of the hook); allow-only and the row compaction stay
+    // behind it (chameleon.py:313-327: CFG -> processors -> allow-only -> temperature -> top-p)
+    if (!hk) { a.logits_img = g->logits + (long long)B * V; a.logits_uncond = g->logits + 2ll * B * V; }
     a.g_text = sp->guidance_scale_text; a.g_image = sp->guidance_scale_image; a.allow = allow_dev;
     if (allow_ids_dev && n_allow > 0) { a.gather = allow_ids_dev; a.Vsrc = V; a.V = n_allow; }
 
@@ -407,6 +423,42 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
         if (r) return r;
         return sample(s);
     };
+    CfgMixArgs mx{};
+    mx.cond = g->logits; mx.img = g->logits + (long long)B * V; mx.uncond = g->logits + 2ll * B * V; mx.V = V; mx.B = B;
+    mx.g_text = sp->guidance_scale_text; mx.g_image = sp->guidance_scale_image;
+    if (hk) {
+        mx.out = hk->logits;
+        auto step_a = [&](hipStream_t s) -> int {         // consume the token sampled last -> mixed logits of the next one
+            hipLaunchKernelGGL(k_cham_step, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, g->tok, g->pos, (const long long*)nullptr,
+                               (const int*)nullptr, 0, M, (const long long*)tokens_out_dev, (long long)n_tokens, (const int*)(g->ctr + 1),
+                               (int)B, 1);
+            ChamPlan q(g, M, s);
+            if (int r = q.step(true, g->logits)) return r;
+            return launch_cfg_mix(mx, s);
+        };
+        if (rc == WMAR_OK && sp->use_graph) {
+            unsigned long long key[16] = {(unsigned long long)B, (unsigned long long)n_tokens, (unsigned long long)(uintptr_t)q_dev,
+                                          (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)hk->logits,
+                                          (unsigned long long)(uintptr_t)hk->past, (unsigned long long)ids_stride,
+                                          (unsigned long long)(uintptr_t)allow_dev, (unsigned long long)(uintptr_t)allow_ids_dev,
+                                          (unsigned long long)n_allow, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+            memcpy(&key[10], &sp->temperature, 4); memcpy(&key[11], &sp->top_p, 8);
+            memcpy(&key[12], &sp->guidance_scale_text, 4); memcpy(&key[13], &sp->guidance_scale_image, 4);
+            if (memcmp(key, g->hook_key, sizeof(key)) != 0 || !g->grh.exec[0] || !g->grh.exec[1]) {
+                g->grh.drop();
+                memset(g->hook_key, 0, sizeof(g->hook_key));
+                rc = g->grh.capture(0, step_a);
+                if (rc == WMAR_OK) rc = g->grh.capture(1, sample);
+                if (rc == WMAR_OK) memcpy(g->hook_key, key, sizeof(key));
+            }
+        }
+        for (int n = 0; n < n_tokens && rc == WMAR_OK; ++n) {
+            if (n == 0) rc = launch_cfg_mix(mx, st);       // first image token from the prefill logits
+            else rc = sp->use_graph ? g->grh.replay(0, st) : step_a(st);
+            if (rc == WMAR_OK) rc = call_hook(*hk, n, (long long)maxlen + n);
+            if (rc == WMAR_OK) rc = sp->use_graph ? g->grh.replay(1, st) : sample(st);
+        }
+    } else {
     if (rc == WMAR_OK) rc = sample(st);                 // first image token from the prefill logits
     if (rc == WMAR_OK && n_tokens > 1) {
         if (sp->use_graph) {
@@ -426,13 +478,34 @@ int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t*
             for (int n = 1; n < n_tokens && rc == WMAR_OK; ++n) rc = one_step(st);
         }
     }
+    }
     // the prompt tables are read by the prefill only; it has been enqueued on `st`, free after it ran
     hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(tab_tok);
     (void)hipFree(tab_pos);
     if (rc == WMAR_OK && e2 != hipSuccess) { set_error("cham_generate_image: %s", hipGetErrorString(e2)); rc = WMAR_EHIP; }
-    if (rc != WMAR_OK) g->gr.drop();
+    if (rc != WMAR_OK && !hk) g->gr.drop();
+    if (rc != WMAR_OK && rc != WMAR_ECALLBACK && hk) g->grh.drop();
     return rc;
+}
+
+int wmar_cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t* prompt_tokens_host,
+                             const int32_t* prompt_lens_host, int64_t B, const wmar_cham_sample_params* sp,
+                             const uint32_t* allow_dev, const int32_t* allow_ids_dev, int32_t n_allow, const float* q_dev,
+                             int32_t n_tokens, int64_t* tokens_out_dev, void* stream) {
+    return cham_generate_image(g, wm, prompt_tokens_host, prompt_lens_host, B, sp, allow_dev, allow_ids_dev, n_allow, q_dev, n_tokens,
+                               tokens_out_dev, stream, nullptr);
+}
+
+int wmar_cham_generate_image_hooked(wmar_cham* g, const int64_t* prompt_tokens_host, const int32_t* prompt_lens_host, int64_t B,
+                                    const wmar_cham_sample_params* sp, const uint32_t* allow_dev, const int32_t* allow_ids_dev,
+                                    int32_t n_allow, const float* q_dev, int32_t n_tokens, int64_t* tokens_out_dev,
+                                    float* logits_io_dev, int64_t* past_io_dev, int64_t past_stride, wmar_logits_hook hook,
+                                    void* user, void* stream) {
+    // (this engine has no in-launch barrier: nothing to check behind the run, no re-run)
+    const HookIO hk{logits_io_dev, (long long*)past_io_dev, (long long)past_stride, hook, user};
+    return cham_generate_image(g, nullptr, prompt_tokens_host, prompt_lens_host, B, sp, allow_dev, allow_ids_dev, n_allow, q_dev,
+                               n_tokens, tokens_out_dev, stream, &hk);
 }
 
 }  // extern "C"

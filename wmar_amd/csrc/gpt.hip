@@ -78,6 +78,10 @@ struct wmar_gpt {
     // cache is short / medium / long (att_phase(): fixed cost 7.0 / 9.8 / 13.5 us against loads in flight).
     static constexpr int N_PHASE = 3;
     GraphSlots<N_PHASE> gr;
+    // hooked generation (wmar_gpt_generate_hooked): the model step per attention phase (graph A), then the sampler + counters
+    // (graph B, slot N_PHASE) -- slots and key of their own, so that fused and hooked calls do not evict each other's graphs
+    GraphSlots<N_PHASE + 1> grh;
+    unsigned long long hook_key[12] = {0};
     int att_nw = 2;                // waves per attention workgroup of the step being enqueued
     unsigned long long graph_key[12] = {0};
     // phase of the step that attends to `kv` cached rows (including the new one)
@@ -748,6 +752,7 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
     WMAR_TRY(g->mem.alloc_zero(&g->xsync, 8 * 64 + 64, st));
     g->step_dev = g->pos_dev + 1;
     WMAR_TRY(g->gr.init());
+    WMAR_TRY(g->grh.init());
     if (rc == WMAR_OK) {
         hipError_t e = hipEventCreate(&g->ev0);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -785,6 +790,7 @@ static int gpt_persist_failed(wmar_gpt* g, hipStream_t st) {
     WMAR_HIP_CHECK(hipStreamSynchronize(st));
     if (!f) return 0;
     g->gr.drop();
+    g->grh.drop();
     WMAR_HIP_CHECK(hipMemsetAsync(g->ss_bar, 0, SS_BAR_WORDS * 4, st));
     g->persist_ok = false;
     g->fallbacks += 1;
@@ -803,6 +809,7 @@ static int gpt_sync_failed(wmar_gpt* g, hipStream_t st) {
     WMAR_HIP_CHECK(hipStreamSynchronize(st));
     if (!f[0] && !f[1]) return 0;
     g->gr.drop();
+    g->grh.drop();
     WMAR_HIP_CHECK(hipMemsetAsync(g->xsync, 0, (8 * 64 + 64) * 4, st));
     g->xcd_ok = false;                  // the two-launch path from here on
     g->fallbacks += 1;
@@ -1140,6 +1147,92 @@ int wmar_gpt_generate(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_sample_para
     // stays asynchronous.
     return run_with_fallback("generate: the in-launch barrier flag is up on the two-launch path",
                              [&] { return gpt_generate_once(g, wm, sp, cond_dev, B, steps, q_dev, tokens_out_dev, logits_trace_dev, stream); },
+                             [&] { return gpt_sync_failed(g, (hipStream_t)stream); });
+}
+
+// wmar_gpt_generate with the step cut in two at the point where sample_with_past calls its logit processor (mingpt.py:348-350):
+// graph A = enqueue_step (head output straight into the caller's logits buffer), the hook on the calling thread, graph B = the
+// sampler without watermark + the counters.  The caller's past buffer IS the token source of the model step: class token in column 0,
+// the sampler appends behind it.
+static int gpt_generate_hooked_once(wmar_gpt* g, const wmar_sample_params* sp, const int64_t* cond_dev, int64_t B, int32_t steps,
+                                    const float* q_dev, int64_t* tokens_out_dev, const HookIO& hk, void* stream) {
+    WMAR_REQUIRE(g && sp && cond_dev && q_dev && tokens_out_dev && hk.logits && hk.past && hk.hook, "generate_hooked: null argument");
+    WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "generate_hooked: batch %lld outside 1..%d", (long long)B, g->Bmax);
+    WMAR_REQUIRE(steps >= 1 && steps <= g->Tmax, "generate_hooked: steps %d outside 1..block_size %d", steps, g->Tmax);
+    WMAR_REQUIRE(hk.past_stride >= (long long)steps + 1, "generate_hooked: past_stride %lld below steps + 1 = %d", hk.past_stride, steps + 1);
+    WMAR_REQUIRE(!(sp->top_p >= 0) || sp->top_p <= 1.0, "`top_p` has to be a float > 0 and < 1, but is %f", sp->top_p);
+    hipStream_t st = (hipStream_t)stream;
+    const long long pstride = hk.past_stride;
+    if (int rc = gpt_inject(g, st)) return rc;
+    WMAR_HIP_CHECK(hipMemcpy2DAsync(hk.past, pstride * 8, cond_dev, 8, 8, (size_t)B, hipMemcpyDeviceToDevice, st));
+    WMAR_HIP_CHECK(hipMemsetAsync(g->pos_dev, 0, 8, st));
+    int* len_dev = g->pos_dev + 2;
+    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, len_dev, 1);
+
+    SampArgs a{};
+    a.wm = make_wm(nullptr);
+    a.logits = hk.logits; a.V = g->V; a.past = hk.past; a.past_stride = pstride; a.t_dev = len_dev;
+    a.temperature = sp->temperature; a.top_k = sp->top_k; a.use_top_p = sp->top_p >= 0;
+    a.top_p_thr = (float)(1.0 - sp->top_p);
+    a.q = q_dev; a.q_step_stride = (long long)B * g->V; a.step_dev = g->step_dev;
+    a.scratch = a.V > 65536 ? g->scratch : nullptr;
+    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = steps;
+    a.past_append = hk.past; a.trace = nullptr; a.B = B;
+
+    StepIO io{hk.past, pstride, 1, hk.logits};
+    auto step_a = [&](hipStream_t s, int phase) -> int {
+        g->att_nw = wmar_gpt::phase_waves(phase);
+        return enqueue_step(g, B, io, s);
+    };
+    auto step_b = [&](hipStream_t s) -> int {
+        if (int rc = launch_sample_fused(a, s)) return rc;
+        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->pos_dev);
+        return launch_status("k_advance3");
+    };
+    constexpr int SLOT_B = wmar_gpt::N_PHASE;
+    if (sp->use_graph) {
+        unsigned long long key[12] = {(unsigned long long)B, (unsigned long long)steps, (unsigned long long)(uintptr_t)q_dev,
+                                      (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)hk.logits,
+                                      (unsigned long long)(uintptr_t)hk.past, (unsigned long long)pstride, 0ull, 0ull, 0ull,
+                                      (unsigned long long)sp->top_k, 0ull};
+        const float ft = sp->temperature;
+        memcpy(&key[9], &ft, 4); memcpy(&key[11], &sp->top_p, 8);
+        bool need[wmar_gpt::N_PHASE] = {false, false, false};
+        for (int n = 0; n < steps; ++n) need[g->att_phase(n + 1, B)] = true;
+        if (memcmp(key, g->hook_key, sizeof(key)) != 0) g->grh.drop();
+        bool have = g->grh.exec[SLOT_B] != nullptr;
+        for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) have = have && (!need[ph] || g->grh.exec[ph]);
+        if (!have) {
+            g->grh.drop();
+            memset(g->hook_key, 0, sizeof(g->hook_key));
+            for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) {
+                if (!need[ph]) continue;
+                if (int rc = g->grh.capture(ph, [&](hipStream_t s) { return step_a(s, ph); })) return rc;
+            }
+            if (int rc = g->grh.capture(SLOT_B, step_b)) return rc;
+            memcpy(g->hook_key, key, sizeof(key));
+        }
+    }
+    { StepPlan pl(g, B, io, nullptr); if (!pl.small && pl.proj_xr) g->xr_enqueued = true; if (pl.persist) g->ps_enqueued = true; }
+    int rc = WMAR_OK;
+    for (int n = 0; n < steps && rc == WMAR_OK; ++n) {
+        const int ph = g->att_phase(n + 1, B);
+        rc = sp->use_graph ? g->grh.replay(ph, st) : step_a(st, ph);
+        if (rc == WMAR_OK) rc = call_hook(hk, n, (long long)n + 1);
+        if (rc == WMAR_OK) rc = sp->use_graph ? g->grh.replay(SLOT_B, st) : step_b(st);
+    }
+    if (sp->use_graph) { if (int r = g->grh.replayed(st)) return rc ? rc : r; }
+    return rc;
+}
+
+int wmar_gpt_generate_hooked(wmar_gpt* g, const wmar_sample_params* sp, const int64_t* cond_dev, int64_t B, int32_t steps,
+                             const float* q_dev, int64_t* tokens_out_dev, float* logits_io_dev, int64_t* past_io_dev,
+                             int64_t past_stride, wmar_logits_hook hook, void* user, void* stream) {
+    WMAR_REQUIRE(g, "generate_hooked: null argument");
+    const HookIO hk{logits_io_dev, (long long*)past_io_dev, (long long)past_stride, hook, user};
+    // the barrier check behind the last step, as wmar_gpt_generate: a run that raised the flag is repeated (the hook from step 0)
+    return run_with_fallback("generate_hooked: the in-launch barrier flag is up on the two-launch path",
+                             [&] { return gpt_generate_hooked_once(g, sp, cond_dev, B, steps, q_dev, tokens_out_dev, hk, stream); },
                              [&] { return gpt_sync_failed(g, (hipStream_t)stream); });
 }
 

@@ -435,6 +435,10 @@ struct wmar_rar {
     int inject_fail = 0;           // WMAR_INJECT_SYNC_FAIL=1 at creation (tests): the next fused call finds the flag raised
     int fallbacks = 0;
     GraphSlots<1> gr;
+    // hooked generation (wmar_rar_generate_hooked): graph A (position + guidance mix) and graph B (sampler + counters) in slots and
+    // under a key of their own: kept across calls, untouched by the fused calls
+    GraphSlots<2> grh;
+    unsigned long long hook_key[12] = {0};
 };
 
 namespace {
@@ -450,6 +454,8 @@ struct RarPlan {
     bool shared_u;          // rows [Bhalf, M) all carry the "none" condition: their adaLN modulation comes from g->mod_u
     int MTc;                // row tiles of the adaLN GEMM
     bool bx = false;        // 128 rows: QKV / proj / FC2 on the bf16 matrix pipe
+    const long long* ids = nullptr;   // generated ids the embedding reads: the engine's, or the caller's past buffer (hooked mode)
+    long long ids_stride = 0;
 
     RarPlan(wmar_rar* g_, int M_, int Bhalf_, const long long* tok_, hipStream_t st_, bool shared_u_ = false)
         : g(g_), M(M_), Bhalf(Bhalf_), st(st_), tok(tok_), shared_u(shared_u_) {
@@ -461,6 +467,7 @@ struct RarPlan {
         S_fc2 = pick_split(tiles, KBF, 4);
         bx = MT == 4 && g->bx_ok && !g->no_bx;
         if (bx) { S_proj = g->bx_proj.S; S_fc2 = g->bx_fc2.S; }
+        ids = g->ids; ids_stride = g->cfg.image_seq_len;
     }
     GemmArgs base() const {
         GemmArgs a{};
@@ -471,7 +478,7 @@ struct RarPlan {
     int embed() {
         RarEmbedArgs e{};
         e.x = g->x; e.sc = g->sc; e.stats = g->stats; e.emb = g->emb; e.cls = g->cls; e.pos = g->pos; e.tape = g->tape;
-        e.tstep = g->tstep; e.tok = tok; e.cond = g->cond_ids; e.ids = g->ids; e.ids_stride = g->cfg.image_seq_len;
+        e.tstep = g->tstep; e.tok = tok; e.cond = g->cond_ids; e.ids = ids; e.ids_stride = ids_stride;
         e.pos_dev = g->ctr; e.KB = KBD; e.MT = MT; e.n_chunks = nch; e.M = M; e.Bhalf = Bhalf; e.K = D; e.MTsc = MTc;
         e.scq = ada_bx() ? g->scq : nullptr;
         hipLaunchKernelGGL(k_rar_embed, dim3(nch * MT), dim3(256), 0, st, e);
@@ -792,6 +799,7 @@ int wmar_rar_create(const wmar_rar_config* cfg, const char* const* names, const 
         { const char* e = getenv("WMAR_INJECT_SYNC_FAIL"); g->inject_fail = (e && atoi(e) > 0) ? 1 : 0; }
     }
     WMAR_TRY(g->gr.init());
+    WMAR_TRY(g->grh.init());
     if (rc == WMAR_OK) {
         const hipError_t er = hipStreamSynchronize(st);
         if (er != hipSuccess) { set_error("rar_create: %s", hipGetErrorString(er)); rc = WMAR_EHIP; }
@@ -817,6 +825,7 @@ static int rar_sync_failed(wmar_rar* g, hipStream_t st, bool always = false) {
     if (!f) return 0;
     if (!g->rm_fused) { WMAR_HIP_CHECK(hipMemsetAsync(g->sync_fail, 0, 4, st)); return 2; }
     g->gr.drop();
+    g->grh.drop();
     WMAR_HIP_CHECK(hipMemsetAsync(g->sync_fail, 0, 4, st));
     g->rm_fused = false;
     g->fallbacks += 1;
@@ -870,18 +879,86 @@ int wmar_rar_forward_position(wmar_rar* g, const int64_t* tok_dev, const int64_t
     }, [&] { return rar_sync_failed(g, st); });
 }
 
+// The generation loop of wmar_rar_generate_hooked behind the shared staging of rar_generate_once (condition ids, guidance scales, the
+// unconditional adaLN table): RAR.generate with the step cut in two where the reference calls its logit processor (rar.py:450-451),
+// i.e. behind the guidance mix.  Graph A = the position (+ k_cfg_mix under guidance) -> the caller's logits; hook; graph B = the sampler
+// without guidance and watermark on that buffer + the counters.  The embedding reads the generated ids from the caller's past buffer.
+static int rar_hooked_loop(wmar_rar* g, const HookIO& hk, int M, int B, bool shared_u, float temperature, const float* q_dev,
+                           int64_t* tokens_out_dev, int32_t use_graph, hipStream_t st) {
+    const int L = g->cfg.image_seq_len, V = g->V;
+    const bool guided = M != B;
+    auto plan = [&](hipStream_t s) {
+        RarPlan p(g, M, B, nullptr, s, shared_u);
+        p.ids = hk.past; p.ids_stride = hk.past_stride;
+        return p;
+    };
+    hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, 0, 0, 0);
+    { RarPlan p = plan(st); if (int rc = p.position(false, nullptr)) return rc; }      // position 0: the cls token
+    hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, 1, 0, 0);              // pos = 1, step = 0, len(ids) = 0
+
+    CfgMixArgs mx{};
+    mx.cond = g->logits; mx.uncond = g->logits + (long long)B * V; mx.out = hk.logits; mx.V = V; mx.B = B;
+    mx.scale = g->cfg_scale; mx.step_dev = g->ctr + 1;
+    SampArgs a{};
+    a.wm = make_wm(nullptr);
+    a.logits = hk.logits; a.V = V; a.past = hk.past; a.past_stride = hk.past_stride; a.t_dev = g->ctr + 2;
+    a.temperature = temperature; a.top_k = 0; a.use_top_p = 0; a.top_p_thr = 0.f;
+    a.q = q_dev; a.q_step_stride = (long long)B * V; a.step_dev = g->ctr + 1;
+    a.scratch = a.V > 65536 ? g->scratch : nullptr;
+    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = L;
+    a.past_append = hk.past; a.trace = nullptr; a.B = B;
+    auto step_a = [&](hipStream_t s) -> int {
+        RarPlan p = plan(s);
+        if (!guided) return p.position(true, hk.logits);
+        if (int rc = p.position(true, g->logits)) return rc;
+        return launch_cfg_mix(mx, s);
+    };
+    auto step_b = [&](hipStream_t s) -> int {
+        if (int rc = launch_sample_fused(a, s)) return rc;
+        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->ctr);
+        return launch_status("k_advance3");
+    };
+    if (use_graph) {
+        unsigned long long key[12] = {(unsigned long long)M, (unsigned long long)B, (unsigned long long)(uintptr_t)q_dev,
+                                      (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)hk.logits,
+                                      (unsigned long long)(uintptr_t)hk.past, (unsigned long long)hk.past_stride, 0ull,
+                                      (unsigned long long)shared_u, (unsigned long long)g->rm_fused, 0ull, 0ull};
+        memcpy(&key[7], &temperature, 4);
+        if (memcmp(key, g->hook_key, sizeof(key)) != 0 || !g->grh.exec[0] || !g->grh.exec[1]) {
+            g->grh.drop();
+            memset(g->hook_key, 0, sizeof(g->hook_key));
+            if (int rc = g->grh.capture(0, step_a)) return rc;
+            if (int rc = g->grh.capture(1, step_b)) return rc;
+            memcpy(g->hook_key, key, sizeof(key));
+        }
+    }
+    int rc = WMAR_OK;
+    for (int n = 0; n < L && rc == WMAR_OK; ++n) {
+        rc = use_graph ? g->grh.replay(0, st) : step_a(st);
+        if (rc == WMAR_OK) rc = call_hook(hk, n, (long long)n);
+        if (rc == WMAR_OK) rc = use_graph ? g->grh.replay(1, st) : step_b(st);
+    }
+    if (use_graph) { if (int r = g->grh.replayed(st)) return rc ? rc : r; }
+    return rc;
+}
+
 static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,
                              const float* cfg_scale_host, int32_t use_guidance, float temperature, const float* q_dev,
                              const float* log_rs_dev, float top_p, int32_t top_k, uint64_t h0, int32_t ngram, const float* u_dev,
-                             int64_t* tokens_out_dev, int32_t use_graph, void* stream) {
+                             int64_t* tokens_out_dev, int32_t use_graph, void* stream, const HookIO* hk = nullptr) {
     WMAR_REQUIRE(g && class_ids_dev && (q_dev || log_rs_dev) && tokens_out_dev, "rar_generate: null argument");
+    if (hk) {
+        WMAR_REQUIRE(hk->logits && hk->past && hk->hook && q_dev && !wm && !log_rs_dev, "rar_generate_hooked: null argument");
+        WMAR_REQUIRE(hk->past_stride >= g->cfg.image_seq_len, "rar_generate_hooked: past_stride %lld below image_seq_len %d", hk->past_stride,
+                     g->cfg.image_seq_len);
+    }
     WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "rar_generate: batch %lld outside 1..%d", (long long)B, g->Bmax);
     WMAR_REQUIRE(!use_guidance || cfg_scale_host, "rar_generate: guidance scales missing");
     if (wm) WMAR_REQUIRE(wm->table_dev && wm->vocab_size == g->V, "rar_generate: watermark vocab mismatch");
     hipStream_t st = (hipStream_t)stream;
     const int L = g->cfg.image_seq_len, V = g->V;
     const int M = use_guidance ? 2 * (int)B : (int)B;
-    g->gr.drop();
+    if (!hk) g->gr.drop();
     if (int rc = rar_inject(g, st)) return rc;
     // condition ids: class + codebook_size + 1, unconditional rows get the "none" id (rar.py:303-312)
     std::vector<long long> hc((size_t)B);
@@ -915,6 +992,7 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
         g->mod_u_ready = true;
     }
     const bool shared_u = use_guidance != 0;
+    if (hk) return rar_hooked_loop(g, *hk, M, (int)B, shared_u, temperature, q_dev, tokens_out_dev, use_graph, st);
     RarPlan p(g, M, (int)B, nullptr, st, shared_u);
     // position 0: the cls token (no logits needed)
     hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, 0, 0, 0);
@@ -988,6 +1066,19 @@ int wmar_rar_generate(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_i
     WMAR_REQUIRE(q_dev, "rar_generate: null argument");
     return rar_generate_impl(g, wm, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, nullptr, 0.f, 0, 0, 0, nullptr,
                              tokens_out_dev, use_graph, stream);
+}
+
+int wmar_rar_generate_hooked(wmar_rar* g, const int64_t* class_ids_dev, int64_t B, const float* cfg_scale_host,
+                             int32_t use_guidance, float temperature, const float* q_dev, int64_t* tokens_out_dev,
+                             int32_t use_graph, float* logits_io_dev, int64_t* past_io_dev, int64_t past_stride,
+                             wmar_logits_hook hook, void* user, void* stream) {
+    WMAR_REQUIRE(g && q_dev, "rar_generate_hooked: null argument");
+    const HookIO hk{logits_io_dev, (long long*)past_io_dev, (long long)past_stride, hook, user};
+    // the flag check behind the last position, as wmar_rar_generate: a run that raised it is repeated (the hook from step 0)
+    return run_with_fallback("rar_generate_hooked: the in-launch wait flag is up on the two-launch pair", [&] {
+        return rar_generate_once(g, nullptr, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, q_dev, nullptr, 0.f, 0, 0, 0,
+                                 nullptr, tokens_out_dev, use_graph, stream, &hk);
+    }, [&] { return rar_sync_failed(g, (hipStream_t)stream); });
 }
 
 int wmar_rar_generate_gumbel(wmar_rar* g, const int64_t* class_ids_dev, int64_t B, const float* cfg_scale_host,

@@ -67,6 +67,37 @@ struct SampArgs {
 
 int launch_sample_fused(const SampArgs& a, hipStream_t st);
 
+// Guidance as a launch of its own (k_cfg_mix, watermark.hip): what k_sample_fused does to its rows in front of the watermark bias,
+// written out as fp32 [B, V] -- the hooked generation mode hands that buffer to the host's logit processor.
+struct CfgMixArgs {
+    const float* cond;           // [B, V] conditional (RAR) / fully conditioned (Chameleon) rows
+    const float* img;            // nullable [B, V]: image-conditioned rows -> the three-way form
+    const float* uncond;         // [B, V]
+    float* out;                  // [B, V]
+    long long V, B;
+    const float* scale;          // two-way: device float [steps], indexed by *step_dev (0 when step_dev is null)
+    const int* step_dev;
+    float g_text, g_image;       // three-way
+};
+
+int launch_cfg_mix(const CfgMixArgs& a, hipStream_t st);
+
+// The host's side of a hooked generation (wmar_*_generate_hooked): its buffers and its callback.
+struct HookIO {
+    float* logits;               // [B, V]
+    long long* past;             // [B, past_stride]
+    long long past_stride;
+    wmar_logits_hook hook;
+    void* user;
+};
+
+// hook(user, step, t) between the two graphs of a step; non-zero -> WMAR_ECALLBACK
+inline int call_hook(const HookIO& h, int step, long long t) {
+    const int r = h.hook(h.user, (int32_t)step, (int64_t)t);
+    if (r != 0) { set_error("the logits hook returned %d at step %d: generation stopped", r, step); return WMAR_ECALLBACK; }
+    return WMAR_OK;
+}
+
 // Gumbel-key sampler (gumbel.hip): same step / append plumbing as SampArgs.
 struct GumbelArgs {
     const float* logits;

@@ -33,6 +33,74 @@ __global__ __launch_bounds__(256) void k_wm_bias(WmDev wm, float* logits, long l
     }
 }
 
+// ---------------------------------------------------------------------- guidance
+// The two guidance forms, one operation per statement (no contraction: -ffp-contract=off); k_sample_fused and k_cfg_mix both call
+// these, so that guidance inside the sampler and guidance as a launch of its own give the same bits.
+// RAR.generate (rar.py:437-442): uncond + (cond - uncond) * scale
+__device__ __forceinline__ float cfg_mix2(float c, float u, float scale) {
+    const float dlt = c - u;
+    const float sc = dlt * scale;
+    return u + sc;
+}
+// InBatchInstructCFG (logits_processor.py:312-336): uncond + g_image * (img - uncond) + g_text * (full - img)
+__device__ __forceinline__ float cfg_mix3(float full, float im, float u, float g_text, float g_image) {
+    const float d1 = im - u;
+    const float t1 = g_image * d1;
+    const float s1 = u + t1;
+    const float d2 = full - im;
+    const float t2 = g_text * d2;
+    return s1 + t2;
+}
+
+// One launch over [B, V]: blockIdx.y = row, the row's float4 groups (VEC) or elements strided over blockIdx.x.  Every stream is
+// read once, 16 bytes per lane; V % 4 != 0 or a misaligned pointer takes the scalar form.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_cfg_mix(CfgMixArgs a) {
+    const long long b = blockIdx.y;
+    const long long off = b * a.V;
+    const bool three = a.img != nullptr;
+    const float scale = three ? 0.f : a.scale[a.step_dev ? *a.step_dev : 0];
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    if (VEC) {
+        const long long n4 = a.V >> 2;
+        const float4* c4 = reinterpret_cast<const float4*>(a.cond + off);
+        const float4* u4 = reinterpret_cast<const float4*>(a.uncond + off);
+        const float4* i4 = three ? reinterpret_cast<const float4*>(a.img + off) : nullptr;
+        float4* o4 = reinterpret_cast<float4*>(a.out + off);
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+            const float4 c = c4[i], u = u4[i];
+            float4 r;
+            if (three) {
+                const float4 m = i4[i];
+                r.x = cfg_mix3(c.x, m.x, u.x, a.g_text, a.g_image); r.y = cfg_mix3(c.y, m.y, u.y, a.g_text, a.g_image);
+                r.z = cfg_mix3(c.z, m.z, u.z, a.g_text, a.g_image); r.w = cfg_mix3(c.w, m.w, u.w, a.g_text, a.g_image);
+            } else {
+                r.x = cfg_mix2(c.x, u.x, scale); r.y = cfg_mix2(c.y, u.y, scale);
+                r.z = cfg_mix2(c.z, u.z, scale); r.w = cfg_mix2(c.w, u.w, scale);
+            }
+            o4[i] = r;
+        }
+    } else {
+        for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < a.V; v += stride) {
+            const float c = a.cond[off + v], u = a.uncond[off + v];
+            a.out[off + v] = three ? cfg_mix3(c, a.img[off + v], u, a.g_text, a.g_image) : cfg_mix2(c, u, scale);
+        }
+    }
+}
+
+int launch_cfg_mix(const CfgMixArgs& a, hipStream_t st) {
+    const auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    const bool vec = a.V % 4 == 0 && al(a.cond) && al(a.uncond) && al(a.out) && (!a.img || al(a.img));
+    const long long per_row = vec ? a.V / 4 : a.V;
+    long long gx = (per_row + 255) / 256;
+    if (gx > 64) gx = 64;
+    if (gx < 1) gx = 1;
+    const dim3 grid((unsigned)gx, (unsigned)a.B);
+    if (vec) hipLaunchKernelGGL(k_cfg_mix<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_cfg_mix<false>, grid, dim3(256), 0, st, a);
+    return launch_status("k_cfg_mix");
+}
+
 // ---------------------------------------------------------------------- fused sampler
 constexpr int SAMP_THREADS = 1024;
 constexpr int SAMP_WAVES = SAMP_THREADS / 64;
@@ -232,11 +300,8 @@ __global__ __launch_bounds__(SAMP_THREADS) void k_sample_fused(SampArgs a) {
                 const long long v = tid + (long long)i * SAMP_THREADS;
                 const long long sv = v < V ? WMAR_SRC(v) : 0;
                 lv[j] = v < V ? lg[sv] : 0.f;
-                if (il && v < V) {
-                    const float u = ul[sv], im = il[sv];
-                    const float d1 = im - u; const float t1 = a.g_image * d1; const float s1 = u + t1;
-                    const float d2 = lv[j] - im; const float t2 = a.g_text * d2; lv[j] = s1 + t2;
-                } else if (ul && v < V) { const float u = ul[sv]; const float dlt = lv[j] - u; const float sc = dlt * cfg; lv[j] = u + sc; }
+                if (il && v < V) lv[j] = cfg_mix3(lv[j], il[sv], ul[sv], a.g_text, a.g_image);
+                else if (ul && v < V) lv[j] = cfg_mix2(lv[j], ul[sv], cfg);
             }
 #pragma unroll
             for (int j = 0; j < CH; ++j) {
@@ -259,11 +324,8 @@ __global__ __launch_bounds__(SAMP_THREADS) void k_sample_fused(SampArgs a) {
         for (long long v = tid; v < V; v += SAMP_THREADS) {
             const long long sv = WMAR_SRC(v);
             float xv = lg[sv];
-            if (il) {
-                const float u = ul[sv], im = il[sv];
-                const float d1 = im - u; const float t1 = a.g_image * d1; const float s1 = u + t1;
-                const float d2 = xv - im; const float t2 = a.g_text * d2; xv = s1 + t2;
-            } else if (ul) { const float u = ul[sv]; const float dlt = xv - u; const float sc = dlt * cfg; xv = u + sc; }
+            if (il) xv = cfg_mix3(xv, il[sv], ul[sv], a.g_text, a.g_image);
+            else if (ul) xv = cfg_mix2(xv, ul[sv], cfg);
             if (trace) trace[sv] = xv;
             if (grow && ((grow[sv >> 5] >> (sv & 31)) & 1u)) xv = xv + delta;
             if (a.allow && !((a.allow[sv >> 5] >> (sv & 31)) & 1u)) xv = -INFINITY;
@@ -723,6 +785,18 @@ int wmar_sample_fused(const wmar_wm_ctx* wm, const float* logits_dev, int64_t B,
     a.tok_out_stride = 1;
     a.B = B;
     return launch_sample_fused(a, (hipStream_t)stream);
+}
+
+int wmar_cfg_mix(const float* cond_dev, const float* img_dev, const float* uncond_dev, float* out_dev, int64_t B, int64_t V,
+                 const float* scale_dev, const int32_t* step_dev, float g_text, float g_image, void* stream) {
+    WMAR_REQUIRE(cond_dev && uncond_dev && out_dev, "cfg_mix: null argument");
+    WMAR_REQUIRE(img_dev || scale_dev, "cfg_mix: the two-way form needs its scale");
+    WMAR_REQUIRE(V > 0 && V < (1ll << 31) && B >= 0 && B <= 65535, "cfg_mix: bad shape");
+    if (B == 0) return WMAR_OK;
+    CfgMixArgs a{};
+    a.cond = cond_dev; a.img = img_dev; a.uncond = uncond_dev; a.out = out_dev; a.V = V; a.B = B;
+    a.scale = scale_dev; a.step_dev = step_dev; a.g_text = g_text; a.g_image = g_image;
+    return launch_cfg_mix(a, (hipStream_t)stream);
 }
 
 int wmar_cham_sample(const wmar_wm_ctx* wm, const float* logits3_dev, int64_t B, int64_t V, const int64_t* past_ids_dev,

@@ -73,6 +73,28 @@ class AutoregressiveMultimodalModelWrapper:
         vq.alive_ids = torch.tensor(alive, dtype=torch.long)
         vq.dead_ids = torch.tensor(dead, dtype=torch.long)
 
+    # ---- which generation loop a ``sample`` call takes
+    def _resolve_logit_processor(self, apply_watermark, logit_processor=None):
+        """The reference's loops take any callable as ``logit_processor`` (``sample_with_past(logit_processor=)``, mingpt.py:348-350;
+        ``RAR.generate``, rar.py:450-451; HF ``LogitsProcessorList`` for Chameleon).  Returns the processor the engines' hooked
+        generation mode has to run, or None for the fused loops:
+
+        * ``logit_processor`` given: that one (with or without a watermarker);
+        * ``apply_watermark`` with a watermarker that has no ``wm_ctx`` (anything that only offers the reference's interface:
+          ``spawn_logit_processor()`` / ``detect`` / ``__str__``): ``watermarker.spawn_logit_processor()``;
+        * otherwise (this build's ``GentimeWatermark`` with its device key table, no watermark): None -- the fused path.
+
+        The processor must be a function of its arguments: when the engine re-runs a generation behind a failed in-launch barrier it
+        is called again from step 0."""
+        if logit_processor is not None:
+            if not callable(logit_processor):
+                raise TypeError(f"logit_processor must be callable, got {type(logit_processor).__name__}")
+            return logit_processor
+        wm = getattr(self, "watermarker", None)
+        if apply_watermark and wm is not None and not hasattr(wm, "wm_ctx"):
+            return wm.spawn_logit_processor()
+        return None
+
     # ---- images that did not come from this build (files, photos, RGBA): an EXTENSION for Taming and RAR -- the reference has the
     # PIL entry only for Chameleon (ImageTokenizer.img_tokens_from_pil, deps/chameleon/inference/image_tokenizer.py:94-98); the same
     # steps (blend over white, LANCZOS resize of the short side, centre crop, u8 / 255 * 2 - 1) at the model's own image_size

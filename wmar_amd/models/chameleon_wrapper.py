@@ -285,12 +285,14 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
 
     # conditioning: list of (index, prompt) tuples; returns the segments of the ONE generated sequence (reference: batch 1)
     def sample_interleaved(self, conditioning, gen_params, apply_watermark=False, max_gen_len: int = 4096,
-                           text_temperature: float = 0.7, text_top_p: float = 0.9, repetition_penalty: float = 1.2):
+                           text_temperature: float = 0.7, text_top_p: float = 0.9, repetition_penalty: float = 1.2,
+                           logit_processor=None):
         """wmar/models/chameleon_wrapper.py:108-134 -> Generator with Options(txt=True) (chameleon.py:392-440): text tokens are
         decoded until every row emits <boi>, then 1024 image tokens under 3-way guidance, <eoi>, text again ... until <eos> or the
         length limit.  Every switch re-runs the prompt through a fresh decoder, exactly as the reference builds a new
         TextDecoder / ImageDecoder on the grown input.  The image phases are the captured engine loop; the text steps are eager
-        (one engine forward + the text chain per token)."""
+        (one engine forward + the text chain per token).  The image phases follow the rule of ``sample`` for ``logit_processor`` /
+        a watermarker without ``wm_ctx``: the hooked generation mode runs the processor."""
         v = self.vocab
         eng = self.model.engine
         # the reference's interleaved mode serves one prompt per call (its split_token_sequence asserts batch 1): fail at entry, not
@@ -306,7 +308,8 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
         max_seq_len = eng.max_seq_len
         generated: List[List[int]] = [[] for _ in range(B)]
         V = self.model.cfg.vocab_size
-        wm_ctx = self.watermarker.wm_ctx() if (apply_watermark and self.watermarker is not None) else None
+        processor = self._resolve_logit_processor(apply_watermark, logit_processor)
+        wm_ctx = self.watermarker.wm_ctx() if (apply_watermark and self.watermarker is not None and processor is None) else None
         done = False
         while not done:
             # ---------------- text decoder on the current inputs
@@ -344,7 +347,7 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
             q = self.draw_noise(B)
             img = eng.generate_image(self.split_inputs_for_cfg(inputs), q, self.n_image_tokens, gen_params["temperature"], gen_params["top_p"],
                                      self.guidance_scale_text, self.guidance_scale_image, allow=self._allow_img, wm_ctx=wm_ctx,
-                                     use_graph=self.use_graph, allow_ids=self._allow_ids, pad_id=v.pad_id)
+                                     use_graph=self.use_graph, allow_ids=self._allow_ids, pad_id=v.pad_id, processor=processor)
             for b in range(B):
                 generated[b] += img[b].tolist() + [v.end_image]
         codes = torch.tensor(generated, dtype=torch.int64, device=self.model.device).contiguous()
@@ -360,7 +363,16 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
 
     # conditioning: list of (index, prompt) tuples (prompt: str, a list of token ids, or a list of tokens_from_ui entries -- text, image,
     # ids, sentinel dicts -- for a prompt that holds images); gen_params: {top_p, temperature}
-    def sample(self, conditioning, gen_params, apply_watermark=False, q: Optional[torch.Tensor] = None):
+    def sample(self, conditioning, gen_params, apply_watermark=False, q: Optional[torch.Tensor] = None, logit_processor=None):
+        """``logit_processor``: a reference-style processor (an HF ``LogitsProcessor``, as the reference's ``LogitsProcessorList``
+        holds them).  Given one -- or with ``apply_watermark`` and a watermarker that only offers ``spawn_logit_processor()`` -- the
+        engine's hooked generation mode runs it at every image token
+        (``AutoregressiveMultimodalModelWrapper._resolve_logit_processor``), called POSITIONALLY, ``f(input_ids, logits)``:
+        ``input_ids`` int64 [B, P+n] = the first stream's prompt left-padded with ``pad_id`` to the longest of the 3B prompts, then
+        the ``n`` generated tokens (a strided view); ``logits`` float32 [B, V] behind the three-way guidance mix and in front of
+        allow-only (order: CFG -> processor -> allow-only -> temperature -> top-p, chameleon.py:313-327).  The reference hands its
+        processors all 3B rows and then samples from the first third only (token_selector.py:34-47); this build passes that first
+        third -- processors that need the other rows are out of scope."""
         ui = []
         for _, prompt in conditioning:
             if isinstance(prompt, (list, tuple)) and prompt and isinstance(prompt[0], dict):
@@ -372,7 +384,8 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
         B = len(prompts)
         dev = self.model.device
         out = torch.empty(B, self.n_image_tokens, dtype=torch.int64, device=dev)
-        wm_ctx = self.watermarker.wm_ctx() if (apply_watermark and self.watermarker is not None) else None
+        processor = self._resolve_logit_processor(apply_watermark, logit_processor)
+        wm_ctx = self.watermarker.wm_ctx() if (apply_watermark and self.watermarker is not None and processor is None) else None
         if q is None and self.seed is not None:
             torch.manual_seed(self.seed)          # enable_full_determinism(options.seed) at Generator start (chameleon.py:402-403)
         mb = self.model.max_batch
@@ -382,7 +395,7 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
             out[b0:b1] = self.model.engine.generate_image(
                 self.split_inputs_for_cfg(prompts[b0:b1]), qq, self.n_image_tokens, gen_params["temperature"], gen_params["top_p"],
                 self.guidance_scale_text, self.guidance_scale_image, allow=self._allow_img, wm_ctx=wm_ctx, use_graph=self.use_graph,
-                allow_ids=self._allow_ids, pad_id=self.vocab.pad_id)
+                allow_ids=self._allow_ids, pad_id=self.vocab.pad_id, processor=processor)
         codes = out.detach().contiguous()
         assert self.is_codes_shaped(codes), f"Codes shape: {codes.shape}"
         return codes

@@ -46,6 +46,48 @@ class _Engine:
         return int(getattr(self._L, self._prefix + "_device_bytes")(self._h))
 
 
+class _LogitsHook:
+    """The host side of a hooked generation (include/wmar_hip.h, "hooked generation"): owns the two buffers the engine and the
+    processor share and wraps the processor as the library's C callback.
+
+    ``logits``: float32 [B, V], contiguous; ``past``: int64 [B, width], of which the first ``t`` columns are valid at a step.  The
+    processor is called under ``torch.no_grad()`` on the device's current stream (the stream the engine replays its graphs on), as
+    ``f(past_ids=past[:, :t], logits=logits)`` or, with ``positional``, ``f(past[:, :t], logits)``.  It returns a [B, V] tensor; if
+    that is not the buffer itself it is copied in (``copy_`` converts the dtype).  ctypes swallows what a callback raises, so the
+    exception is kept here, the library is told to stop (non-zero return) and ``finish`` re-raises it."""
+
+    def __init__(self, processor, B: int, V: int, width: int, device, positional: bool):
+        self.processor, self.positional = processor, positional
+        self.logits = torch.empty(B, V, dtype=torch.float32, device=device)
+        self.past = torch.zeros(B, width, dtype=torch.int64, device=device)
+        self.error = None
+        self.cfunc = _lib.LOGITS_HOOK(self._call)
+
+    def _call(self, user, step, t):
+        try:
+            with torch.no_grad():
+                past = self.past[:, :t]
+                out = self.processor(past, self.logits) if self.positional else self.processor(past_ids=past, logits=self.logits)
+                if not isinstance(out, torch.Tensor):
+                    raise TypeError(f"logit processor returned {type(out).__name__}, expected a tensor of shape {tuple(self.logits.shape)}")
+                if out.shape != self.logits.shape:
+                    raise ValueError(f"logit processor returned shape {tuple(out.shape)}, expected {tuple(self.logits.shape)}")
+                if out is not self.logits and not (out.data_ptr() == self.logits.data_ptr() and out.dtype == self.logits.dtype
+                                                   and out.is_contiguous()):
+                    self.logits.copy_(out)
+            return 0
+        except BaseException as e:  # noqa: BLE001  (re-raised by finish(): nothing may cross the C frames)
+            self.error = e
+            return 1
+
+    def finish(self, rc: int):
+        """Status of the library call -> the processor's own exception, unchanged, or the library's error."""
+        err, self.error = self.error, None
+        if err is not None:
+            raise err
+        _lib.check(rc)
+
+
 class _TokenizerEngine(_Engine):
     """Chunked (max_batch images per call) encode / decode of the two VQ tokenizers."""
 
@@ -124,6 +166,27 @@ class GPTEngine(_Engine):
             # waits for the replays; raises if the fused projection launch's in-kernel barrier gave up (results invalid)
             _lib.check(self._L.wmar_gpt_check(self._h, _lib.stream_ptr(self.device)))
         return (out, trace) if trace_logits else out
+
+    def generate_hooked(self, cond: torch.Tensor, steps: int, q: torch.Tensor, processor, temperature=1.0, top_k=None, top_p=None,
+                        use_graph: bool = True) -> torch.Tensor:
+        """``generate`` with a reference-style ``logit_processor`` between the model step and the sampler (mingpt.py:348-350):
+        ``processor(past_ids=int64 [B, n+1] (class token, then the n tokens so far), logits=float32 [B, V] raw head output)``."""
+        _require_cuda(cond, "conditioning")
+        _require_cuda(q, "q")
+        cond = cond.to(torch.int64).contiguous().view(-1)
+        B = cond.shape[0]
+        V = self.cfg.vocab_size
+        assert q.shape == (steps, B, V) and q.dtype == torch.float32 and q.is_contiguous()
+        out = torch.empty(B, steps, dtype=torch.int64, device=self.device)
+        sp = _lib.SampleParams(float(temperature), int(top_k) if top_k else 0,
+                               float(top_p) if top_p is not None else -1.0, 1 if use_graph else 0)
+        with torch.cuda.device(self.device):
+            hook = _LogitsHook(processor, B, V, steps + 1, self.device, positional=False)
+            hook.finish(self._L.wmar_gpt_generate_hooked(
+                self._h, C.byref(sp), cond.data_ptr(), B, int(steps), q.data_ptr(), out.data_ptr(), hook.logits.data_ptr(),
+                hook.past.data_ptr(), hook.past.stride(0), hook.cfunc, None, _lib.stream_ptr(self.device)))
+            _lib.check(self._L.wmar_gpt_check(self._h, _lib.stream_ptr(self.device)))
+        return out
 
     def profile_role(self, role: str, B: int, kv_len: int = 128, iters: int = 96) -> float:
         """Average microseconds per launch of one role's kernel replayed back to back (HIP events)."""
@@ -236,6 +299,24 @@ class RAREngine(_Engine):
             _lib.check(self._L.wmar_rar_check(self._h, _lib.stream_ptr(self.device)))      # waits; raises if an in-launch wait gave up
         return out
 
+    def generate_hooked(self, class_ids: torch.Tensor, q: torch.Tensor, cfg_scales: Optional[torch.Tensor], processor,
+                        temperature=1.0, use_graph: bool = True) -> torch.Tensor:
+        """``generate`` with a reference-style ``logit_processor`` behind the guidance mix (rar.py:437-451):
+        ``processor(past_ids=int64 [B, n] (generated tokens only, [B, 0] at the first step), logits=float32 [B, V])``."""
+        class_ids, out, (sc, sc_ptr, guided) = self._staging(class_ids, cfg_scales)
+        _require_cuda(q, "q")
+        B = class_ids.shape[0]
+        L, V = self.cfg.image_seq_len, self.cfg.codebook_size
+        assert q.shape == (L, B, V) and q.dtype == torch.float32 and q.is_contiguous()
+        with torch.cuda.device(self.device):
+            hook = _LogitsHook(processor, B, V, L, self.device, positional=False)
+            hook.finish(self._L.wmar_rar_generate_hooked(
+                self._h, class_ids.data_ptr(), B, sc_ptr, guided, float(temperature), q.data_ptr(), out.data_ptr(),
+                1 if use_graph else 0, hook.logits.data_ptr(), hook.past.data_ptr(), hook.past.stride(0), hook.cfunc, None,
+                _lib.stream_ptr(self.device)))
+            _lib.check(self._L.wmar_rar_check(self._h, _lib.stream_ptr(self.device)))
+        return out
+
     def generate_gumbel(self, class_ids, log_rs, cfg_scales, temperature=1.0, top_p=0.0, top_k=0, use_graph=True):
         """RAR.generate with the Gumbel-key sampler (extension, include/wmar_hip.h wmar_rar_generate_gumbel)."""
         class_ids, out, (sc, sc_ptr, guided) = self._staging(class_ids, cfg_scales)
@@ -327,11 +408,13 @@ class ChameleonEngine(_Engine):
     def generate_image(self, prompts, q: torch.Tensor, n_tokens: int, temperature: float, top_p: Optional[float],
                        guidance_scale_text: float, guidance_scale_image: float, allow: Optional[torch.Tensor] = None,
                        wm_ctx: Optional[_lib.WmCtx] = None, use_graph: bool = True,
-                       allow_ids: Optional[torch.Tensor] = None, pad_id: int = 1) -> torch.Tensor:
+                       allow_ids: Optional[torch.Tensor] = None, pad_id: int = 1, processor=None) -> torch.Tensor:
         """prompts: the 3B token lists (full-, image-, un-conditioned, in that order); q float32 [n_tokens, B, V];
         allow: int32 bitmap [V/32] of permitted vocabulary entries; allow_ids: the same set as ascending int32 ids (lets the
         sampler work on the compacted row); pad_id: the id short prompts are left-padded with (it can enter the watermark context
-        of the first image tokens).  Returns int64 [B, n_tokens] vocabulary ids."""
+        of the first image tokens).  Returns int64 [B, n_tokens] vocabulary ids.  ``generate_image_hooked`` is this call with
+        ``processor``: ``processor(input_ids int64 [B, P+n], logits float32 [B, V])``, positional, on the first stream's left-padded
+        prompt plus the generated tokens and the logits behind the three-way mix, in front of allow-only."""
         _require_cuda(q, "q")
         M = len(prompts)
         assert M % 3 == 0
@@ -349,6 +432,17 @@ class ChameleonEngine(_Engine):
         if allow_ids is not None:
             _require_cuda(allow_ids, "allow ids")
             assert allow is not None and allow_ids.dtype == torch.int32 and allow_ids.is_contiguous()
+        if processor is not None:
+            assert wm_ctx is None, "a logit processor replaces the fused watermark"
+            P = int(lens.max())
+            with torch.cuda.device(self.device):
+                hook = _LogitsHook(processor, B, V, P + int(n_tokens), self.device, positional=True)
+                hook.finish(self._L.wmar_cham_generate_image_hooked(
+                    self._h, flat.ctypes.data, lens.ctypes.data, B, C.byref(sp), allow.data_ptr() if allow is not None else None,
+                    allow_ids.data_ptr() if allow_ids is not None else None, int(allow_ids.numel()) if allow_ids is not None else 0,
+                    q.data_ptr(), int(n_tokens), out.data_ptr(), hook.logits.data_ptr(), hook.past.data_ptr(), hook.past.stride(0),
+                    hook.cfunc, None, _lib.stream_ptr(self.device)))
+            return out
         with torch.cuda.device(self.device):
             _lib.check(self._L.wmar_cham_generate_image(
                 self._h, C.byref(wm_ctx) if wm_ctx is not None else None, flat.ctypes.data, lens.ctypes.data, B, C.byref(sp),
@@ -356,3 +450,11 @@ class ChameleonEngine(_Engine):
                 int(allow_ids.numel()) if allow_ids is not None else 0, q.data_ptr(), int(n_tokens), out.data_ptr(),
                 _lib.stream_ptr(self.device)))
         return out
+
+    def generate_image_hooked(self, prompts, q: torch.Tensor, n_tokens: int, processor, temperature: float, top_p: Optional[float],
+                              guidance_scale_text: float, guidance_scale_image: float, allow: Optional[torch.Tensor] = None,
+                              use_graph: bool = True, allow_ids: Optional[torch.Tensor] = None, pad_id: int = 1) -> torch.Tensor:
+        """``generate_image`` with a reference-style logit processor (HF ``LogitsProcessor`` call) between the guidance mix and
+        allow-only; see ``generate_image``."""
+        return self.generate_image(prompts, q, n_tokens, temperature, top_p, guidance_scale_text, guidance_scale_image, allow=allow,
+                                   use_graph=use_graph, allow_ids=allow_ids, pad_id=pad_id, processor=processor)

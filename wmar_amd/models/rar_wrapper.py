@@ -117,7 +117,14 @@ class RarARMMWrapper(AutoregressiveMultimodalModelWrapper):
         return u
 
     # conditioning: list of size [b] of class indices; gen_params ignored (as in the reference)
-    def sample(self, conditioning, gen_params=None, apply_watermark=False, q: Optional[torch.Tensor] = None):
+    def sample(self, conditioning, gen_params=None, apply_watermark=False, q: Optional[torch.Tensor] = None, logit_processor=None):
+        """``logit_processor``: the reference's ``RAR.generate(logit_processor=)``.  Given one -- or with ``apply_watermark`` and a
+        watermarker that only offers ``spawn_logit_processor()`` -- the engine's hooked generation mode runs it at every step
+        (``AutoregressiveMultimodalModelWrapper._resolve_logit_processor``), called as the reference calls it (rar.py:450-451):
+        ``f(past_ids=int64 [B, n], logits=float32 [B, V])`` -- the generated tokens only ([B, 0] at the first step; a strided view)
+        and the logits behind the guidance mix, in front of the temperature (contiguous, the engine's buffer: edit it in place or
+        return a new [B, V] tensor, which is copied in).  A ``GumbelWatermark`` keeps its own path, ``GentimeWatermark`` the fused
+        one."""
         conditioning = torch.as_tensor(conditioning, device=self.model.device).view(-1)
         cfg = self.model.cfg
         B = conditioning.shape[0]
@@ -141,12 +148,16 @@ class RarARMMWrapper(AutoregressiveMultimodalModelWrapper):
                 out[b0:b1] = self.model.engine.generate_gumbel(conditioning[b0:b1], w.log_rs, scales, w.temperature, w.top_p,
                                                                w.top_k, use_graph=self.use_graph)
             return out.detach()
-        wm_ctx = self.watermarker.wm_ctx() if apply_watermark else None
+        processor = self._resolve_logit_processor(apply_watermark, logit_processor)
+        wm_ctx = self.watermarker.wm_ctx() if (apply_watermark and processor is None) else None
         if q is None and B > mb:
             q = self.draw_noise(B)
         for b0 in range(0, B, mb):
             b1 = min(B, b0 + mb)
             qq = q[:, b0:b1].contiguous() if q is not None else self.draw_noise(b1 - b0)
+            if processor is not None:
+                out[b0:b1] = self.model.engine.generate_hooked(conditioning[b0:b1], qq, scales, processor, 1.0, use_graph=self.use_graph)
+                continue
             out[b0:b1] = self.model.engine.generate(conditioning[b0:b1], qq, scales, 1.0, wm_ctx, use_graph=self.use_graph)
         codes = out.detach()
         assert self.is_codes_shaped(codes), f"Codes shape: {codes.shape}"

@@ -140,11 +140,19 @@ class TamingARMMWrapper(AutoregressiveMultimodalModelWrapper):
         return q
 
     # conditioning: list of size [b]; gen_params: dict; returns detached codes [b, codes_size**2]
-    def sample(self, conditioning, gen_params, apply_watermark=False, q: Optional[torch.Tensor] = None):
+    def sample(self, conditioning, gen_params, apply_watermark=False, q: Optional[torch.Tensor] = None, logit_processor=None):
+        """``logit_processor``: the reference's ``sample_with_past(logit_processor=)``.  Given one -- or with ``apply_watermark`` and a
+        watermarker that only offers ``spawn_logit_processor()`` -- the engine's hooked generation mode runs it at every step
+        (``AutoregressiveMultimodalModelWrapper._resolve_logit_processor``), called as the reference calls it (mingpt.py:348-350):
+        ``f(past_ids=int64 [B, n+1], logits=float32 [B, V])`` -- the class token followed by the ``n`` tokens generated so far
+        (a strided view), and the raw head output (contiguous, the engine's buffer: edit it in place or return a new [B, V]
+        tensor of any floating dtype, which is copied in).  Runs under ``torch.no_grad()`` on the current stream; anything it raises
+        surfaces from this call."""
         conditioning = torch.as_tensor(conditioning, device=self.model.device).view(-1)
         steps = self.codes_size * self.codes_size
         B = conditioning.shape[0]
-        wm_ctx = self.watermarker.wm_ctx() if apply_watermark else None
+        processor = self._resolve_logit_processor(apply_watermark, logit_processor)
+        wm_ctx = self.watermarker.wm_ctx() if (apply_watermark and processor is None) else None
         out = torch.empty(B, steps, dtype=torch.int64, device=self.model.device)
         mb = self.model.max_batch
         if q is None and B > mb and steps * B * self.model.gpt_cfg.vocab_size * 4 <= (32 << 30):
@@ -152,6 +160,11 @@ class TamingARMMWrapper(AutoregressiveMultimodalModelWrapper):
         for b0 in range(0, B, mb):
             b1 = min(B, b0 + mb)
             qq = q[:, b0:b1].contiguous() if q is not None else self.draw_noise(steps, b1 - b0)
+            if processor is not None:
+                out[b0:b1] = self.model.transformer.generate_hooked(
+                    conditioning[b0:b1], steps, qq, processor, temperature=gen_params["temperature"], top_k=gen_params["top_k"],
+                    top_p=gen_params["top_p"], use_graph=self.use_graph)
+                continue
             out[b0:b1] = self.model.transformer.generate(
                 conditioning[b0:b1], steps, qq, temperature=gen_params["temperature"], top_k=gen_params["top_k"],
                 top_p=gen_params["top_p"], wm_ctx=wm_ctx, use_graph=self.use_graph)
