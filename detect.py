@@ -5,6 +5,9 @@ Takes the model and watermark flags of ``generate.py`` (the key must be the one 
 
     --images DIR | FILE [FILE ...]   --batch_size N   --out results.json
 
+(``--sync true --syncpath ... | --sync_factory ...`` removes the synchronisation layer's geometric attack estimate first, as
+``generate.py`` does in front of every re-encode.)
+
 and writes one JSON list in sorted file order: ``file``, ``width``, ``height``, ``pvalue`` and the detector's counts
 (``n_scored``, and ``n_green`` for the greenlist watermark; none for a ``--wm_method custom`` watermarker that only offers the
 reference's ``detect``); a file PIL cannot open gets ``error`` instead, the rest are processed and the exit status is 1.
@@ -41,8 +44,9 @@ def detect_codes(watermarker, codes):
     return res[0].cpu().tolist(), counts
 
 
-def run(model, watermarker, files, batch_size):
-    """One record per file, in the order given.  Batches are formed by count, whatever the images' sizes."""
+def run(model, watermarker, files, batch_size, sync_manager=None):
+    """One record per file, in the order given.  Batches are formed by count, whatever the images' sizes.  With a `sync_manager`
+    (--sync) the synchronisation signal is read and the estimated flip / rotation / crop reverted before the images are encoded."""
     from wmar_amd.utils.ingest import open_image, pixels_of
     records = []
     for b0 in range(0, len(files), batch_size):
@@ -59,7 +63,10 @@ def run(model, watermarker, files, batch_size):
             records.append(rec)
         if not batch:
             continue
-        codes = model.codes_from_pil(pix)
+        if sync_manager is None:
+            codes = model.codes_from_pil(pix)
+        else:
+            codes = model.images_to_codes(sync_manager.remove_sync(model.images_from_pil(pix)))
         pvals, counts = detect_codes(watermarker, codes)
         for i, rec in enumerate(batch):
             rec["pvalue"] = pvals[i]
@@ -92,7 +99,7 @@ def main():
     model = cli.build_model(args, f"cuda:{local_rank}", args.seed)
     watermarker = cli.build_watermarker(args, model)
     files = list_images(args.images)
-    records = run(model, watermarker, files, max(1, args.batch_size))
+    records = run(model, watermarker, files, max(1, args.batch_size), sync_manager=cli.build_sync_manager(args, f"cuda:{local_rank}"))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(records, f, indent=1)

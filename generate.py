@@ -56,6 +56,10 @@ def get_parser():
                         help="key seed of --wm_method gumbel (--model rar; independent of --seed; --wm_context_size is its ngram)")
     parser.add_argument("--sync", type=str2bool, default=False)
     parser.add_argument("--syncpath", type=str)
+    parser.add_argument("--sync_factory", type=str, default=None,
+                        help="with --sync true: 'pkg.module:callable'; callable(args, device) returns a SyncManager-like object "
+                             "(add_sync / remove_sync) or a WAM-like one (embed(imgs, msg) -> {'imgs_w'}, detect(imgs) -> {'preds'}) "
+                             "instead of the networks --syncpath names")
     parser.add_argument("--seed", type=int, nargs="?", help="seed", default=42)
     parser.add_argument("--synthetic", type=str2bool, default=False, help="random-init weights instead of checkpoints")
     parser.add_argument("--synthetic_config", type=str, default="full", choices=["full", "harness"],
@@ -81,6 +85,13 @@ def check_wm_args(args):
         raise ValueError("--wm_factory is only read with --wm_method custom")
     if factory and (factory.count(":") != 1 or not all(factory.split(":"))):
         raise ValueError(f"--wm_factory {factory!r}: expected pkg.module:callable")
+    sync_factory = getattr(args, "sync_factory", None)
+    if sync_factory and not getattr(args, "sync", False):
+        raise ValueError("--sync_factory is only read with --sync true")
+    if sync_factory and (sync_factory.count(":") != 1 or not all(sync_factory.split(":"))):
+        raise ValueError(f"--sync_factory {sync_factory!r}: expected pkg.module:callable")
+    if getattr(args, "sync", False) and not sync_factory and not getattr(args, "syncpath", None):
+        raise ValueError("--sync true needs --syncpath (wam_mit.pth | syncmodel.jit.pt) or --sync_factory")
 
 
 def main():
@@ -93,7 +104,6 @@ def main():
         parser.error(str(e))
     assert args.outdir, "Output directory is not set"
     assert args.model in ("taming", "rar", "chameleon7b"), f"Model {args.model} not supported"
-    assert not args.sync, "--sync (WAM/SyncSeal) is outside the MI355X hot path"
     os.makedirs(args.outdir, exist_ok=True)
 
     import torch.distributed as dist
@@ -135,6 +145,7 @@ def main():
     if args.wm_method == "gentime" and world > 1:  # build the key once, broadcast it over RCCL
         harness.broadcast_key_table(watermarker, device)
     model.set_watermarker(watermarker)
+    sync_manager = cli.build_sync_manager(args, device)      # None without --sync
 
     # evaluation transforms: the classic ones run batched on the GPU; neural codecs and DiffPure are outside this build
     if args.orig_only:
@@ -149,7 +160,7 @@ def main():
     gen_params = {"batch_size": args.batch_size, "temperature": args.temperature, "top_k": args.top_k,
                   "top_p": args.top_p}
     recs = harness.generate(args.outdir, model, all_inputs, watermarker, eval_params, gen_params, chunk_id=chunk_id,
-                            num_chunks=num_chunks)
+                            num_chunks=num_chunks, sync_manager=sync_manager)
     if world > 1:
         for r in recs:
             if isinstance(r["conditioning"], tuple):

@@ -517,6 +517,36 @@ typedef struct wmar_image_desc {
 int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n, int32_t target,
                       float* out_dev, uint8_t* out_u8_dev, void* stream);
 
+/* ------------------------------------------------------------------------ synchronisation layer (WAM geometry fit)
+ * wmar/watermarking/synchronization.py: the device half of WamSync.remove_sync.  All tensors contiguous; images and label maps are
+ * square, S x S.  No call waits for its launches; workspaces are the caller's.
+ *
+ * wmar_sync_positions: estimate_augmentation_with_wam :224-243 for a batch.  preds_dev fp32 [B, 33, S, S] (channel 0 the mask logit,
+ * 1..32 the bit logits, already at the image size); positions_dev int8 [B, S, S] in {-1, 0, 1, 2, 3}: the nearest of the four fixed
+ * messages 0^32, 0^16 1^16, 1^16 0^16, 1^32 by Hamming distance of `logit > 0` (first minimum), kept when the distance is <= 6 and
+ * fp32 sigmoid(mask logit) > 0.5 as torch evaluates it (false at 5e-8, true at 2e-7), else -1; sizes_dev int32 [B, 4] pixels per
+ * message (zeroed by the call).  One launch. */
+int wmar_sync_positions(const float* preds_dev, int64_t B, int32_t S, int8_t* positions_dev, int32_t* sizes_dev, void* stream);
+
+/* wmar_sync_fit: fit_best_aug + rotate_wm + find_cut (:90-201) for a batch of label maps positions_dev int8 [B, S, S] (0..3; anything
+ * else is background), 4 <= S <= 512.  aug_dev int32 [B, 4] = (rotation in degrees, cut_i, cut_j, flipped); total_error_dev
+ * (nullable) fp64 [B, 41] = errori + errorj of the angles -20..20 (1e9 per axis without signal).  Exactness contract: every pixel of
+ * the 41 x 4 rotated masks is thresholded on the fp64 value scipy.ndimage.rotate(order=3, mode="constant", reshape=False)
+ * interpolates (cubic B-spline prefilter with mirror initialisation, 4 x 4 taps), summed in scipy's order without contraction; a
+ * value closer than ~1e-12 to 0.5 may fall on either side.  Counts, thresholds (40 at S = 256, else 80), cumulative sums, the
+ * cut / flip search, its half-to-even roundings and the selection across angles are integer / fp64 restatements without tolerance.
+ * workspace_dev (16-byte aligned): error and cut tables of the batch plus the spline coefficients fp64 [n, S, S, 4] of as many
+ * images n as fit; wmar_sync_workspace_bytes(B, S) holds the whole batch (four launches), a smaller one (at least the tables plus
+ * one image) makes the call walk the batch in chunks of three launches each.  B <= 65535. */
+int64_t wmar_sync_workspace_bytes(int64_t B, int32_t S);
+int wmar_sync_fit(const int8_t* positions_dev, int64_t B, int32_t S, int32_t* aug_dev, double* total_error_dev, void* workspace_dev,
+                  int64_t workspace_bytes, void* stream);
+
+/* wmar_sync_rotate_labels (tests, debugging): rotate_wm of one angle (whole degrees): out_dev uint8 [B, S, S], the thresholded masks
+ * of labels 1..4 merged in ascending order (0 = background).  Workspace as wmar_sync_fit. */
+int wmar_sync_rotate_labels(const int8_t* positions_dev, int64_t B, int32_t S, int32_t angle, uint8_t* out_dev, void* workspace_dev,
+                            int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ exchange step (RCCL over xGMI)
  * The sharded job (one process per GPU; rank r == the reference's `--chunk_id r --num_chunks world`, generate.py:204, :304) has no
  * data-path collective.  Its two exchanges -- the finished key table from rank 0 once, the per-image records once per step

@@ -25,6 +25,7 @@ SYMBOLS = [
     "wmar_cham_sample",
     "wmar_cfg_mix", "wmar_gpt_generate_hooked", "wmar_rar_generate_hooked", "wmar_cham_generate_image_hooked",
     "wmar_augment", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
+    "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
 
@@ -135,6 +136,11 @@ def load():
     L.wmar_jpeg.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp]
     L.wmar_resample_coeffs.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, C.POINTER(i32)]
     L.wmar_image_ingest.argtypes = [vp, i64, C.POINTER(ImageDesc), i64, i32, vp, vp, vp]
+    L.wmar_sync_positions.argtypes = [vp, i64, i32, vp, vp, vp]
+    L.wmar_sync_workspace_bytes.restype = i64
+    L.wmar_sync_workspace_bytes.argtypes = [i64, i32]
+    L.wmar_sync_fit.argtypes = [vp, i64, i32, vp, vp, vp, i64, vp]
+    L.wmar_sync_rotate_labels.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp]
     L.wmar_comm_unique_id.argtypes = [vp, i64]
     L.wmar_comm_init.argtypes = [vp, i64, i32, i32, C.POINTER(vp)]
     L.wmar_comm_bcast.argtypes = [vp, vp, i64, i32, vp]

@@ -25,6 +25,7 @@ SOURCES = [
     ("augment.hip", ["-ffp-contract=off"]),
     ("jpeg.hip", ["-ffp-contract=off"]),
     ("ingest.hip", ["-ffp-contract=off"]),
+    ("sync.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-x", "hip"]

@@ -62,3 +62,23 @@ def build_watermarker(args, model):
         module, _, name = args.wm_factory.partition(":")
         return getattr(importlib.import_module(module), name)(model, args)
     return None
+
+
+def build_sync_manager(args, device):
+    """The synchronisation layer of ``--sync true`` (generate.py:407-410 of the reference): the networks ``--syncpath`` names, or what
+    ``--sync_factory pkg.module:callable`` returns -- a manager (add_sync / remove_sync) as it is, a WAM-like object (embed / detect)
+    wrapped into a WamSync so that its geometry fit runs on the device.  None without ``--sync``."""
+    if not getattr(args, "sync", False):
+        return None
+    from .watermarking.synchronization import SyncManager, WamSync
+    factory = getattr(args, "sync_factory", None)
+    if not factory:
+        return SyncManager(args.syncpath, device)
+    import importlib
+    module, _, name = factory.partition(":")
+    made = getattr(importlib.import_module(module), name)(args, device)
+    if hasattr(made, "add_sync") and hasattr(made, "remove_sync"):
+        return made if isinstance(made, SyncManager) else SyncManager(args.syncpath, device, sync=made)
+    if hasattr(made, "embed") and hasattr(made, "detect"):
+        return SyncManager(args.syncpath, device, sync=WamSync(args.syncpath, device, wam=made))
+    raise TypeError(f"--sync_factory {factory}: {type(made).__name__} has neither add_sync / remove_sync nor embed / detect")

@@ -46,17 +46,28 @@ def seed_everything(seed: int, chunk_id: int = 0):
 
 @torch.no_grad()
 def fill_batch_log(batch_log, key, model, codes, eval_params, sync_manager=None):
-    """generate.py:112-164 without the synchronization layer: decode, `max_roundtrips` encode->decode round trips, then
-    every (transform, parameter) of the augmentation table on the WHOLE batch (one re-encode launch sequence per parameter)."""
-    assert sync_manager is None, "the WAM/SyncSeal layer is outside the MI355X hot path"
+    """generate.py:112-164: decode, `max_roundtrips` encode->decode round trips, then every (transform, parameter) of the
+    augmentation table on the WHOLE batch (one re-encode launch sequence per parameter).  With a `sync_manager`
+    (wmar_amd.watermarking.synchronization) the synchronisation signal is added after the first decode and removed in front of every
+    re-encode; the de-synchronised images fill the tuples' fourth slot.  Without one nothing but the calls below runs."""
     imgs = model.codes_to_images(codes)  # [b, 3, R, R] in [-1, 1]
+    if sync_manager is not None:
+        imgs = sync_manager.add_sync(imgs)
+
+    def recode(x):
+        """(codes, de-synchronised images or None) of the images about to be re-encoded"""
+        if sync_manager is None:
+            return model.images_to_codes(x), None
+        nosync = sync_manager.remove_sync(x)
+        return model.images_to_codes(nosync), nosync.cpu().numpy()
+
     batch_log[key] = {}
     batch_log[key]["roundtrips"] = [(0, codes.cpu().numpy(), imgs.cpu().numpy(), None)]
     curr_imgs = imgs
     for T in range(1, eval_params["max_roundtrips"] + 1):
-        curr_codes = model.images_to_codes(curr_imgs)
+        curr_codes, nosync = recode(curr_imgs)
         curr_imgs = model.codes_to_images(curr_codes)
-        batch_log[key]["roundtrips"].append((T, curr_codes.cpu().numpy(), curr_imgs.cpu().numpy(), None))
+        batch_log[key]["roundtrips"].append((T, curr_codes.cpu().numpy(), curr_imgs.cpu().numpy(), nosync))
     from .augmentations import device_ops as _dev_aug
     # the fused form is the default table's arithmetic: only for the AugmentationManager's own entries (a caller's own callable under
     # one of its names keeps its callable)
@@ -70,8 +81,8 @@ def fill_batch_log(batch_log, key, model, codes, eval_params, sync_manager=None)
             if aug_imgs is None:
                 imgs_zero_to_one = imgs / 2.0 + 0.5
                 aug_imgs = aug_fn(imgs_zero_to_one, aug_param).clamp(0, 1) * 2.0 - 1.0
-            aug_codes = model.images_to_codes(aug_imgs)
-            batch_log[key][aug_name].append((aug_param, aug_codes.cpu().numpy(), aug_imgs.cpu().numpy(), None))
+            aug_codes, nosync = recode(aug_imgs)
+            batch_log[key][aug_name].append((aug_param, aug_codes.cpu().numpy(), aug_imgs.cpu().numpy(), nosync))
 
 
 def compute_metrics_and_save_from_batch_log(log, outdir, watermarker, eval_params, cond_indices, compressors=None):
@@ -111,6 +122,8 @@ def compute_metrics_and_save_from_batch_log(log, outdir, watermarker, eval_param
                         os.makedirs(curr_outdir, exist_ok=True)
                         stem = os.path.join(curr_outdir, f"{cond_index:04}_{method}_{transform}_{param}")
                         img.save(stem + ".png")
+                        if imgs_nosync is not None:
+                            chw_to_pillow(imgs_nosync[i]).save(stem + "_nosync.png")
                         np.save(stem + ".npy", code)
                         with open(stem + ".json", "w") as f:
                             json.dump(metrics, f)
