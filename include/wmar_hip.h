@@ -447,6 +447,31 @@ int wmar_vq_decode(wmar_vq* v, const int64_t* codes_dev, int64_t B, float* image
 int wmar_vq_encode(wmar_vq* v, const float* images_dev, int64_t B, int64_t* codes_dev, float* prequant_dev,
                    void* stream);
 
+/* Probes (tests, debugging): one layer at a time through the loader and the dispatch the two calls above use, so that every kernel
+ * variant can be compared with a float64 reference alone.  Activations cross them in the engine's own layout: NHWC fp32, channels
+ * padded with zeros to a multiple of 8 (cin_s, cout_s).  Each probe allocates and frees its scratch and waits for the stream; none
+ * of them is used by an engine path.  The text outputs name what the dispatch itself decided to launch.
+ *
+ * Convolution: w_dev [cout, cin, ks, ks] (torch layout, ks 1 or 3), bias_dev [cout] (nullable: zero), x_dev [B, Hs, Ws, cin_s],
+ * res_dev (nullable) [B, Ho, Wo, cout_s] added in the epilogue, y_dev [B, Ho, Wo, cout_s].  Conventions as in the networks: pad 1 for
+ * 3 x 3 stride 1, zero pad (0, 1, 0, 1) for stride 2, nearest x2 upsampling in front when up != 0.  gn_gamma_dev / gn_beta_dev [cin]
+ * (nullable, together): GroupNorm(32, eps 1e-6) of x, followed by swish when gn_swish != 0, applied by the patch loader as in a
+ * ResnetBlock (cin a multiple of 32, no upsampling).  out_mr_dev (nullable) float [B, 32, 2]: the (mean, rstd) the next GroupNorm on
+ * y would be handed (cout a multiple of 32); arm_stats != 0 arms the per-tile statistics of the conv epilogue as decode / encode do,
+ * and the text says which path delivered them.  kernel_buf: "conv=<kernel>;gn_in=<path>;stats=<path>". */
+int wmar_vq_probe_conv(const float* w_dev, const float* bias_dev, int32_t cout, int32_t cin, int32_t ks, const float* x_dev,
+                       const float* res_dev, const float* gn_gamma_dev, const float* gn_beta_dev, int32_t gn_swish, int64_t B, int32_t Hs,
+                       int32_t Ws, int32_t stride, int32_t up, int32_t arm_stats, float* y_dev, float* out_mr_dev, char* kernel_buf,
+                       int64_t buf_len, void* stream);
+/* Attention core of an AttnBlock: q, k, v [B, H * W, C] -> o = softmax(q k^T C^-1/2) v.  path_buf: "path=bf16_pipe|scalar;scores=<kernel>;
+ * pv=<kernel>". */
+int wmar_vq_probe_attn(const float* q_dev, const float* k_dev, const float* v_dev, int64_t B, int32_t H, int32_t W, int32_t C, float* o_dev,
+                       char* path_buf, int64_t buf_len, void* stream);
+/* Nearest-code search: z_dev [P, E], codebook_dev [n_embed, E] -> codes_dev int64 [P], first minimum of |z|^2 + |e|^2 - 2 z.e.
+ * path_buf: the search kernel and, for the split kernel, its number of code splits. */
+int wmar_vq_probe_argmin(const float* z_dev, int64_t P, int32_t E, const float* codebook_dev, int32_t n_embed, int64_t* codes_dev,
+                         char* path_buf, int64_t buf_len, void* stream);
+
 /* --------------------------------------------------------------- MaskGIT-VQGAN (RAR's tokenizer)
  * deps/rar/modeling/modules/maskgit_vqgan.py + PretrainedTokenizer (deps/rar/modeling/titok.py:41-89).
  * Tensors by key name (encoder.*, decoder.*, quantize.embedding.weight).  Images cross this API in the

@@ -7,8 +7,9 @@ l = bf16(x - h - m).  The kernels rely on three properties, checked here on rand
      below 2^-24 |w x|;
   3. the six kept products h*h + h*m + m*h + h*l + l*h + m*m, each EXACT in fp32 (8 x 8 significand bits) and summed in fp64 here,
      reproduce the fp32 product's exact value to 2^-24 relative -- the accuracy of one fp32 rounding.
-(The HIP kernels are checked against the reference's outputs in tests/test_gpu_vqgan.py / test_gpu_prod_shapes.py; this file pins
-the algorithm, on CPU.)"""
+(This file pins the algorithm, on CPU.  The HIP kernels: every k_conv_bx instantiation alone, one product per output and dense
+against float64, in tests/test_gpu_vq_layers.py; the decoders' k_qkvx_bx / k_bx against the fp64 oracle in
+tests/test_gpu_prod_shapes.py and test_gpu_row_counts.py; whole networks against the reference's outputs in tests/test_gpu_vqgan.py.)"""
 import numpy as np
 
 

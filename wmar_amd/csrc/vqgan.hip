@@ -1141,6 +1141,12 @@ struct GnTrack {
 };
 static thread_local GnTrack g_trk;
 
+// What the last run_conv / run_gn / run_vq_argmin on this thread launched: the dispatch reports its own decision (the wmar_vq_probe_*
+// entries hand it to the tests, which assert the variant they mean to cover)
+static thread_local const char* g_conv_kernel = "none";
+static thread_local const char* g_gn_path = "none";
+static thread_local int g_vq_splits = 0;       // code splits of k_vq_argmin_split<4>, 0 = k_vq_argmin
+
 // a GroupNorm whose statistics are ready and whose normalisation is applied by the convs that consume it
 struct GnRef {
     const float2* mr; const float* g; const float* b; int C, swish;
@@ -1188,27 +1194,29 @@ int run_conv(const ConvW& c, const float* in, float* out, const float* res, int 
         a.tiles_x = a.Wo / CF_T; a.tiles_y = a.Ho / CF_T;
         const unsigned gridf = (unsigned)((long long)B * a.tiles_x * a.tiles_y);
         const size_t ldsf = (size_t)CF_PW * CF_PW * CONV_PSTRIDE * sizeof(float);
-        if (c.cout == 3) hipLaunchKernelGGL(k_conv_few<3>, dim3(gridf), dim3(256), ldsf, st, a, (const float*)c.wf);
-        else hipLaunchKernelGGL(k_conv_few<4>, dim3(gridf), dim3(256), ldsf, st, a, (const float*)c.wf);
+        if (c.cout == 3) { g_conv_kernel = "k_conv_few<3>"; hipLaunchKernelGGL(k_conv_few<3>, dim3(gridf), dim3(256), ldsf, st, a, (const float*)c.wf); }
+        else { g_conv_kernel = "k_conv_few<4>"; hipLaunchKernelGGL(k_conv_few<4>, dim3(gridf), dim3(256), ldsf, st, a, (const float*)c.wf); }
     } else if (bx2) {
         static const hipError_t lds2_ok = hipFuncSetAttribute((const void*)k_conv_bx<4, 3, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         WMAR_REQUIRE(lds2_ok == hipSuccess, "k_conv_bx (stride 2): raising the dynamic LDS limit failed: %s", hipGetErrorString(lds2_ok));
+        g_conv_kernel = "k_conv_bx<4,3,2,2>";
         hipLaunchKernelGGL((k_conv_bx<4, 3, 2, 2>), dim3(grid), dim3(256), lds, st, a);
     } else if (wide) {
         // 75 KB of dynamic LDS (two 10 x 18-pixel patches): above the 64 KB a kernel gets without asking
         static const hipError_t lds_ok = hipFuncSetAttribute((const void*)k_conv_bx<4, 3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         WMAR_REQUIRE(lds_ok == hipSuccess, "k_conv_bx: raising the dynamic LDS limit failed: %s", hipGetErrorString(lds_ok));
+        g_conv_kernel = "k_conv_bx<4,3,4>";
         hipLaunchKernelGGL((k_conv_bx<4, 3, 4>), dim3(grid), dim3(256), lds, st, a);
     }
-    else if (bx && COT == 4 && c.ks == 3) hipLaunchKernelGGL((k_conv_bx<4, 3>), dim3(grid), dim3(256), lds, st, a);
-    else if (bx && COT == 4) hipLaunchKernelGGL((k_conv_bx<4, 1>), dim3(grid), dim3(256), lds, st, a);
-    else if (bx && COT == 2 && c.ks == 3) hipLaunchKernelGGL((k_conv_bx<2, 3>), dim3(grid), dim3(128), lds, st, a);
-    else if (bx && COT == 2) hipLaunchKernelGGL((k_conv_bx<2, 1>), dim3(grid), dim3(128), lds, st, a);
-    else if (bx && c.ks == 3) hipLaunchKernelGGL((k_conv_bx<1, 3>), dim3(grid), dim3(64), lds, st, a);
-    else if (bx) hipLaunchKernelGGL((k_conv_bx<1, 1>), dim3(grid), dim3(64), lds, st, a);
-    else if (COT == 4) hipLaunchKernelGGL(k_conv<4>, dim3(grid), dim3(256), lds, st, a);
-    else if (COT == 2) hipLaunchKernelGGL(k_conv<2>, dim3(grid), dim3(128), lds, st, a);
-    else hipLaunchKernelGGL(k_conv<1>, dim3(grid), dim3(64), lds, st, a);
+    else if (bx && COT == 4 && c.ks == 3) { g_conv_kernel = "k_conv_bx<4,3>"; hipLaunchKernelGGL((k_conv_bx<4, 3>), dim3(grid), dim3(256), lds, st, a); }
+    else if (bx && COT == 4) { g_conv_kernel = "k_conv_bx<4,1>"; hipLaunchKernelGGL((k_conv_bx<4, 1>), dim3(grid), dim3(256), lds, st, a); }
+    else if (bx && COT == 2 && c.ks == 3) { g_conv_kernel = "k_conv_bx<2,3>"; hipLaunchKernelGGL((k_conv_bx<2, 3>), dim3(grid), dim3(128), lds, st, a); }
+    else if (bx && COT == 2) { g_conv_kernel = "k_conv_bx<2,1>"; hipLaunchKernelGGL((k_conv_bx<2, 1>), dim3(grid), dim3(128), lds, st, a); }
+    else if (bx && c.ks == 3) { g_conv_kernel = "k_conv_bx<1,3>"; hipLaunchKernelGGL((k_conv_bx<1, 3>), dim3(grid), dim3(64), lds, st, a); }
+    else if (bx) { g_conv_kernel = "k_conv_bx<1,1>"; hipLaunchKernelGGL((k_conv_bx<1, 1>), dim3(grid), dim3(64), lds, st, a); }
+    else if (COT == 4) { g_conv_kernel = "k_conv<4>"; hipLaunchKernelGGL(k_conv<4>, dim3(grid), dim3(256), lds, st, a); }
+    else if (COT == 2) { g_conv_kernel = "k_conv<2>"; hipLaunchKernelGGL(k_conv<2>, dim3(grid), dim3(128), lds, st, a); }
+    else { g_conv_kernel = "k_conv<1>"; hipLaunchKernelGGL(k_conv<1>, dim3(grid), dim3(64), lds, st, a); }
     if (vq_trace()) {
         (void)hipEventRecord(e1, st); (void)hipEventSynchronize(e1);
         float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
@@ -1232,12 +1240,14 @@ int run_vq_argmin(VqArgs a, unsigned long long* best, hipStream_t st) {
         WMAR_HIP_CHECK(hipMemsetAsync(best, 0xff, (size_t)a.P * 8, st));
         static const hipError_t lds_ok = hipFuncSetAttribute((const void*)k_vq_argmin_split<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);      // + 4 KB static
         WMAR_REQUIRE(lds_ok == hipSuccess, "k_vq_argmin_split: raising the dynamic LDS limit failed: %s", hipGetErrorString(lds_ok));
+        g_vq_splits = CS;
         hipLaunchKernelGGL(k_vq_argmin_split<4>, dim3((unsigned)(groups * CS)), dim3(256), lds4, st, a, best, CS);
         hipLaunchKernelGGL(k_vq_finish, dim3((unsigned)((a.P + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)best, a.codes, a.P);
         return launch_status("k_vq_argmin_split");
     }
     const size_t lds = (size_t)64 * (a.E + 4) * sizeof(float);
     WMAR_HIP_CHECK(hipFuncSetAttribute((const void*)k_vq_argmin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    g_vq_splits = 0;
     hipLaunchKernelGGL(k_vq_argmin, dim3((unsigned)((a.P + 63) / 64)), dim3(256), lds, st, a);
     return launch_status("k_vq_argmin");
 }
@@ -1255,9 +1265,11 @@ int run_gn(double* gn_partial, const NormW& n, const float* x, int B, int HW, in
     float2* mr = (float2*)gn_partial;
     if (g_trk.part && g_trk.src == x && g_trk.C == n.C && g_trk.tiles * 64 == HW) {
         // the conv that produced x already left per-tile sums behind: no pass over the tensor
+        g_gn_path = "k_gn_finalize_tiles";
         hipLaunchKernelGGL(k_gn_finalize_tiles, dim3(B), dim3(256), 0, st, (const double*)g_trk.part, g_trk.tiles,
                            (double)HW * (n.C / 32), mr);
     } else {
+        g_gn_path = "k_gn_partial+k_gn_finalize";
         hipLaunchKernelGGL(k_gn_partial, dim3(nchunk, B), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_gn_finalize, dim3(B), dim3(32), 0, st, a, mr);
     }
@@ -1291,41 +1303,65 @@ int run_res(wmar_vq* v, const ResW& r, Bufs& bf, int B, int H, int W, hipStream_
     return WMAR_OK;
 }
 
+// softmax(q k^T C^-1/2) v for q, k, v [B][N = H W][C] -> o: the middle of an AttnBlock (model.py:176-189), shared by run_attn and
+// wmar_vq_probe_attn.  asc: [B][N][N] floats; attk / attv (nullable: the scalar kernels then): 3 B N C / 8 16-byte words each; zbias:
+// max(N, C) zeros.
+struct AttnScratch { float* asc; u32x4* attk; u32x4* attv; float* zbias; };
+static thread_local const char *g_attn_path = "none", *g_attn_scores = "none", *g_attn_pv = "none";      // reported as g_conv_kernel is
+
+int attn_core(const AttnScratch& s, const float* q, const float* k, const float* vv, float* o, int B, int H, int W, int C, hipStream_t st) {
+    int rc;
+    const int N = H * W;
+    const float scale = 1.0f / sqrtf((float)C);   // int(c)**(-0.5)
+    if (s.attk && N % 32 == 0 && C % 32 == 0 && H % 8 == 0 && W % 8 == 0 && N >= 64 && C >= 64 && !conv_no_bx()) {
+        // Both products as 1x1 convolutions with PER-IMAGE weights on the bf16 matrix pipe (k_conv_bx): scores = conv(q; weights K_b),
+        // out = conv(softmax(scores); weights V_b^T).  K_b and V_b^T are split into bf16 pieces by the weight packer.
+        ConvW ck{}, cv{};
+        ck.wq = s.attk; ck.bias = s.zbias; ck.cin = ck.cin_s = C; ck.cout = ck.cout_s = N; ck.ks = 1; ck.CT = N / 32; ck.KBc = C / 8;
+        cv.wq = s.attv; cv.bias = s.zbias; cv.cin = cv.cin_s = N; cv.cout = cv.cout_s = C; cv.ks = 1; cv.CT = C / 32; cv.KBc = N / 8;
+        const long long sk = (long long)ck.CT * (C / 16) * 192, sv = (long long)cv.CT * (N / 16) * 192;
+        const long long nk = (long long)ck.CT * (C / 16) * 64, nv = (long long)cv.CT * (N / 16) * 64;
+        hipLaunchKernelGGL(k_pack_conv_bx, dim3((unsigned)((nk + 255) / 256), B), dim3(256), 0, st, k, s.attk, N, C, 1, ck.CT,
+                           C / 16, (long long)N * C, sk, 0);
+        hipLaunchKernelGGL(k_pack_conv_bx, dim3((unsigned)((nv + 255) / 256), B), dim3(256), 0, st, vv, s.attv, C, N, 1, cv.CT,
+                           N / 16, (long long)N * C, sv, 1);
+        if ((rc = launch_status("k_pack_conv_bx"))) return rc;
+        if ((rc = run_conv(ck, q, s.asc, nullptr, B, H, W, 1, 0, st, nullptr, sk))) return rc;
+        g_attn_scores = g_conv_kernel;
+        hipLaunchKernelGGL(k_attn_softmax, dim3((unsigned)(((long long)B * N + 3) / 4)), dim3(256), 0, st, s.asc, (long long)B * N, N, scale);
+        if ((rc = launch_status("k_attn_softmax"))) return rc;
+        if ((rc = run_conv(cv, s.asc, o, nullptr, B, H, W, 1, 0, st, nullptr, sv))) return rc;
+        g_attn_path = "bf16_pipe"; g_attn_pv = g_conv_kernel;
+    } else {
+        hipLaunchKernelGGL(k_attn_scores, dim3(N, B), dim3(256), (size_t)C * 4, st, q, k, s.asc, N, C, scale);
+        hipLaunchKernelGGL(k_attn_pv, dim3(N, B), dim3(256), (size_t)N * 4, st, (const float*)s.asc, vv, o, N, C);
+        if ((rc = launch_status("k_attn"))) return rc;
+        g_attn_path = "scalar"; g_attn_scores = "k_attn_scores"; g_attn_pv = "k_attn_pv";
+    }
+    return WMAR_OK;
+}
+
 int run_attn(wmar_vq* v, const AttnW& w, Bufs& bf, int B, int H, int W, hipStream_t st) {
     int rc;
     const int N = H * W, C = w.n.C;
-    float *X = bf.X(), *A = bf.other(1), *T = bf.other(2);
+    float *X = bf.X(), *T = bf.other(2);
     GnRef gn{};
     if ((rc = run_gn(v->gn_partial, w.n, X, B, N, 0, st, &gn))) return rc;
     if ((rc = run_conv(w.q, X, v->aq, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
     if ((rc = run_conv(w.k, X, v->ak, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
     if ((rc = run_conv(w.v, X, v->av, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-    const float scale = 1.0f / sqrtf((float)C);   // int(c)**(-0.5)
-    if (v->attk && N % 32 == 0 && C % 32 == 0 && H % 8 == 0 && W % 8 == 0 && N >= 64 && C >= 64 && !conv_no_bx()) {
-        // Both products as 1x1 convolutions with PER-IMAGE weights on the bf16 matrix pipe (k_conv_bx): scores = conv(q; weights K_b),
-        // out = conv(softmax(scores); weights V_b^T).  K_b and V_b^T are split into bf16 pieces by the weight packer.
-        ConvW ck{}, cv{};
-        ck.wq = v->attk; ck.bias = v->zbias; ck.cin = ck.cin_s = C; ck.cout = ck.cout_s = N; ck.ks = 1; ck.CT = N / 32; ck.KBc = C / 8;
-        cv.wq = v->attv; cv.bias = v->zbias; cv.cin = cv.cin_s = N; cv.cout = cv.cout_s = C; cv.ks = 1; cv.CT = C / 32; cv.KBc = N / 8;
-        const long long sk = (long long)ck.CT * (C / 16) * 192, sv = (long long)cv.CT * (N / 16) * 192;
-        const long long nk = (long long)ck.CT * (C / 16) * 64, nv = (long long)cv.CT * (N / 16) * 64;
-        hipLaunchKernelGGL(k_pack_conv_bx, dim3((unsigned)((nk + 255) / 256), B), dim3(256), 0, st, (const float*)v->ak, v->attk, N, C, 1, ck.CT,
-                           C / 16, (long long)N * C, sk, 0);
-        hipLaunchKernelGGL(k_pack_conv_bx, dim3((unsigned)((nv + 255) / 256), B), dim3(256), 0, st, (const float*)v->av, v->attv, C, N, 1, cv.CT,
-                           N / 16, (long long)N * C, sv, 1);
-        if ((rc = launch_status("k_pack_conv_bx"))) return rc;
-        if ((rc = run_conv(ck, v->aq, v->asc, nullptr, B, H, W, 1, 0, st, nullptr, sk))) return rc;
-        hipLaunchKernelGGL(k_attn_softmax, dim3((unsigned)(((long long)B * N + 3) / 4)), dim3(256), 0, st, v->asc, (long long)B * N, N, scale);
-        if ((rc = launch_status("k_attn_softmax"))) return rc;
-        if ((rc = run_conv(cv, v->asc, v->ao, nullptr, B, H, W, 1, 0, st, nullptr, sv))) return rc;
-    } else {
-        hipLaunchKernelGGL(k_attn_scores, dim3(N, B), dim3(256), (size_t)C * 4, st, v->aq, v->ak, v->asc, N, C, scale);
-        hipLaunchKernelGGL(k_attn_pv, dim3(N, B), dim3(256), (size_t)N * 4, st, v->asc, v->av, v->ao, N, C);
-        if ((rc = launch_status("k_attn"))) return rc;
-    }
+    if ((rc = attn_core(AttnScratch{v->asc, v->attk, v->attv, v->zbias}, v->aq, v->ak, v->av, v->ao, B, H, W, C, st))) return rc;
     if ((rc = run_conv(w.proj, v->ao, T, X, B, H, W, 1, 0, st))) return rc;
     bf.advance(2);
     return WMAR_OK;
+}
+
+// the codebook as a 1x1 "conv" weight [n_embed][E] (same fragment packing) and its squared row norms
+int pack_codebook(const float* emb, float4* emb_p, float* enorm, int n_embed, int E, hipStream_t st) {
+    const size_t n = (size_t)(n_embed / 32) * (E / 8) * 64;
+    hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, emb, emb_p, n_embed, E, 1, n_embed / 32, E / 8);
+    hipLaunchKernelGGL(k_row_sqnorm, dim3(n_embed), dim3(64), 0, st, emb, enorm, E);
+    return launch_status("codebook pack");
 }
 
 }  // namespace
@@ -1416,14 +1452,7 @@ int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const vo
     }
     WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)cfg->n_embed * E / 4));
     WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)cfg->n_embed));
-    if (rc == WMAR_OK) {
-        // the codebook as a 1x1 "conv" weight [n_embed][E]: same fragment packing
-        size_t n = (size_t)(cfg->n_embed / 32) * (E / 8) * 64;
-        hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, emb, v->emb_p, cfg->n_embed, E, 1,
-                           cfg->n_embed / 32, E / 8);
-        hipLaunchKernelGGL(k_row_sqnorm, dim3(cfg->n_embed), dim3(64), 0, st, v->emb, v->enorm, E);
-        rc = launch_status("codebook pack");
-    }
+    if (rc == WMAR_OK) rc = pack_codebook(v->emb, v->emb_p, v->enorm, cfg->n_embed, E, st);
     // ---- workspaces: the largest activation any layer produces
     size_t maxel = 0;
     {
@@ -1563,6 +1592,139 @@ int wmar_vq_encode(wmar_vq* v, const float* images_dev, int64_t B, int64_t* code
     a.z = zq; a.ep = v->emb_p; a.enorm = v->enorm; a.znorm = v->znorm; a.codes = (long long*)codes_dev; a.P = P;
     a.E = E; a.n_embed = c.n_embed;
     return run_vq_argmin(a, v->vqbest, st);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------ probes (tests, debugging)
+// One layer at a time through the engines' own loader and dispatch (Loader::conv, run_gn, run_conv, attn_core, pack_codebook,
+// run_vq_argmin): no kernel and no dispatch rule of its own.  Scratch lives in an arena of the call; the call waits for the stream.
+namespace {
+
+int probe_conv_run(DeviceArena& mem, const float* w, const float* bias, int cout, int cin, int ks, const float* x, const float* res,
+                   const float* gamma, const float* beta, int swish, int B, int Hs, int Ws, int stride, int up, int arm_stats, float* y,
+                   float* out_mr, char* buf, int64_t buf_len, hipStream_t st) {
+    int rc;
+    const char* names[2] = {"probe.weight", "probe.bias"};
+    const void* tensors[2] = {w, bias};
+    Loader ld(names, tensors, bias ? 2 : 1, &mem, st);
+    ConvW c;
+    ld.conv("probe", cin, cout, ks, c, bias != nullptr);
+    if (ld.rc) return ld.rc;
+    const int Hc = up ? 2 * Hs : Hs, Wc = up ? 2 * Ws : Ws;
+    const int Ho = stride == 2 ? Hc / 2 : Hc, Wo = stride == 2 ? Wc / 2 : Wc;
+    const size_t gn_doubles = (size_t)GN_MR_DOUBLES + (size_t)B * GN_CHUNKS_MAX * 32 * 2;
+    g_trk = GnTrack{};
+    if (arm_stats) {            // as wmar_vq_decode / wmar_vq_encode arm it
+        const long long cap = (long long)B * ((Ho + 7) / 8) * ((Wo + 7) / 8) * 64;
+        double* tiles = nullptr;
+        if ((rc = mem.alloc(&tiles, (size_t)cap))) return rc;
+        g_trk.part = tiles; g_trk.cap = cap;
+    }
+    GnRef gin{};
+    const char* gn_in = "none";
+    if (gamma) {                // run_res: statistics first, the normalisation inside the conv's patch loader
+        double* part = nullptr;
+        if ((rc = mem.alloc(&part, gn_doubles))) return rc;
+        NormW n; n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta); n.C = c.cin_s;
+        if ((rc = run_gn(part, n, x, B, Hs * Ws, swish, st, &gin))) return rc;
+        gn_in = g_gn_path;
+    }
+    if ((rc = run_conv(c, x, y, res, B, Hs, Ws, stride, up, st, gamma ? &gin : nullptr))) return rc;
+    const char* conv = g_conv_kernel;
+    const char* stats = "none";
+    if (out_mr) {               // what the next Normalize on y would be handed
+        double* part = nullptr;
+        if ((rc = mem.alloc(&part, gn_doubles))) return rc;
+        NormW n; n.C = cout;
+        GnRef gout{};
+        if ((rc = run_gn(part, n, y, B, Ho * Wo, 0, st, &gout))) return rc;
+        stats = g_gn_path;
+        WMAR_HIP_CHECK(hipMemcpyAsync(out_mr, gout.mr, (size_t)B * 32 * sizeof(float2), hipMemcpyDeviceToDevice, st));
+    }
+    const int n = snprintf(buf, (size_t)buf_len, "conv=%s;gn_in=%s;stats=%s", conv, gn_in, stats);
+    WMAR_REQUIRE(n > 0 && n < buf_len, "vq_probe_conv: buffer of %lld bytes too small", (long long)buf_len);
+    return WMAR_OK;
+}
+
+// the arena of a probe is released only after the stream has drained (and the statistics tracker never outlives its buffer)
+int probe_finish(int rc, hipStream_t st) {
+    g_trk = GnTrack{};
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc == WMAR_OK && e != hipSuccess) { set_error("vq_probe: stream failed: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wmar_vq_probe_conv(const float* w_dev, const float* bias_dev, int32_t cout, int32_t cin, int32_t ks, const float* x_dev,
+                       const float* res_dev, const float* gn_gamma_dev, const float* gn_beta_dev, int32_t gn_swish, int64_t B, int32_t Hs,
+                       int32_t Ws, int32_t stride, int32_t up, int32_t arm_stats, float* y_dev, float* out_mr_dev, char* kernel_buf,
+                       int64_t buf_len, void* stream) {
+    WMAR_REQUIRE(w_dev && x_dev && y_dev && kernel_buf && buf_len > 0, "vq_probe_conv: null argument");
+    WMAR_REQUIRE(cout >= 1 && cin >= 1 && (ks == 1 || ks == 3) && B >= 1 && B <= 1024 && Hs >= 1 && Ws >= 1, "vq_probe_conv: bad shape");
+    WMAR_REQUIRE(stride == 1 || (stride == 2 && ks == 3 && !up), "vq_probe_conv: stride %d (2 only for 3 x 3 without upsampling)", stride);
+    WMAR_REQUIRE((gn_gamma_dev == nullptr) == (gn_beta_dev == nullptr), "vq_probe_conv: GroupNorm needs both gamma and beta");
+    WMAR_REQUIRE(!gn_gamma_dev || cin % 32 == 0, "vq_probe_conv: fused GroupNorm needs a multiple of 32 input channels, got %d", cin);
+    WMAR_REQUIRE(!out_mr_dev || cout % 32 == 0, "vq_probe_conv: output statistics need a multiple of 32 output channels, got %d", cout);
+    hipStream_t st = (hipStream_t)stream;
+    DeviceArena mem;
+    const int rc = probe_conv_run(mem, w_dev, bias_dev, cout, cin, ks, x_dev, res_dev, gn_gamma_dev, gn_beta_dev, gn_swish, (int)B, Hs, Ws,
+                                  stride, up, arm_stats, y_dev, out_mr_dev, kernel_buf, buf_len, st);
+    return probe_finish(rc, st);
+}
+
+int wmar_vq_probe_attn(const float* q_dev, const float* k_dev, const float* v_dev, int64_t B, int32_t H, int32_t W, int32_t C, float* o_dev,
+                       char* path_buf, int64_t buf_len, void* stream) {
+    WMAR_REQUIRE(q_dev && k_dev && v_dev && o_dev && path_buf && buf_len > 0, "vq_probe_attn: null argument");
+    WMAR_REQUIRE(B >= 1 && B <= 1024 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && C <= 1024, "vq_probe_attn: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)H * W;
+    DeviceArena mem;
+    AttnScratch s{};
+    int rc = WMAR_OK;
+    g_trk = GnTrack{};
+    WMAR_TRY(mem.alloc(&s.asc, (size_t)B * N * N));
+    if (N % 32 == 0 && C % 32 == 0) {      // as wmar_vq_create sizes them
+        WMAR_TRY(mem.alloc(&s.attk, (size_t)B * N * C * 3 / 8));
+        WMAR_TRY(mem.alloc(&s.attv, (size_t)B * N * C * 3 / 8));
+        WMAR_TRY(mem.alloc_zero(&s.zbias, N > (size_t)C ? N : (size_t)C, st));
+    }
+    WMAR_TRY(attn_core(s, q_dev, k_dev, v_dev, o_dev, (int)B, H, W, C, st));
+    if (rc == WMAR_OK) {
+        const int n = snprintf(path_buf, (size_t)buf_len, "path=%s;scores=%s;pv=%s", g_attn_path, g_attn_scores, g_attn_pv);
+        if (!(n > 0 && n < buf_len)) { set_error("vq_probe_attn: buffer of %lld bytes too small", (long long)buf_len); rc = WMAR_EINVAL; }
+    }
+    return probe_finish(rc, st);
+}
+
+int wmar_vq_probe_argmin(const float* z_dev, int64_t P, int32_t E, const float* codebook_dev, int32_t n_embed, int64_t* codes_dev,
+                         char* path_buf, int64_t buf_len, void* stream) {
+    WMAR_REQUIRE(z_dev && codebook_dev && codes_dev && path_buf && buf_len > 0, "vq_probe_argmin: null argument");
+    WMAR_REQUIRE(P >= 1 && E >= 8 && E % 8 == 0 && n_embed >= 32 && n_embed % 32 == 0, "vq_probe_argmin: embed_dim %% 8 and n_embed %% 32 must be 0");
+    hipStream_t st = (hipStream_t)stream;
+    DeviceArena mem;
+    float4* emb_p = nullptr; float *enorm = nullptr, *znorm = nullptr; unsigned long long* best = nullptr;
+    int rc = WMAR_OK;
+    WMAR_TRY(mem.alloc(&emb_p, (size_t)n_embed * E / 4));
+    WMAR_TRY(mem.alloc(&enorm, (size_t)n_embed));
+    WMAR_TRY(mem.alloc(&znorm, (size_t)P));
+    WMAR_TRY(mem.alloc(&best, (size_t)P));
+    WMAR_TRY(pack_codebook(codebook_dev, emb_p, enorm, n_embed, E, st));
+    if (rc == WMAR_OK) {
+        hipLaunchKernelGGL(k_row_sqnorm, dim3((unsigned)P), dim3(64), 0, st, z_dev, znorm, E);       // as wmar_vq_encode
+        VqArgs a{};
+        a.z = z_dev; a.ep = emb_p; a.enorm = enorm; a.znorm = znorm; a.codes = (long long*)codes_dev; a.P = P; a.E = E; a.n_embed = n_embed;
+        rc = run_vq_argmin(a, best, st);
+    }
+    if (rc == WMAR_OK) {
+        const int n = g_vq_splits > 0 ? snprintf(path_buf, (size_t)buf_len, "k_vq_argmin_split<4> (%d code splits)", g_vq_splits)
+                                      : snprintf(path_buf, (size_t)buf_len, "k_vq_argmin");
+        if (!(n > 0 && n < buf_len)) { set_error("vq_probe_argmin: buffer of %lld bytes too small", (long long)buf_len); rc = WMAR_EINVAL; }
+    }
+    return probe_finish(rc, st);
 }
 
 }  // extern "C"
@@ -1724,13 +1886,7 @@ int wmar_mvq_create(const wmar_mvq_config* cfg, const char* const* names, const 
     }
     WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)cfg->num_embeddings * z / 4));
     WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)cfg->num_embeddings));
-    if (rc == WMAR_OK) {
-        size_t n = (size_t)(cfg->num_embeddings / 32) * (z / 8) * 64;
-        hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, emb, v->emb_p, cfg->num_embeddings, z, 1,
-                           cfg->num_embeddings / 32, z / 8);
-        hipLaunchKernelGGL(k_row_sqnorm, dim3(cfg->num_embeddings), dim3(64), 0, st, v->emb, v->enorm, z);
-        rc = launch_status("codebook pack");
-    }
+    if (rc == WMAR_OK) rc = pack_codebook(v->emb, v->emb_p, v->enorm, cfg->num_embeddings, z, st);
     size_t maxel = 0;
     {
         int r = cfg->resolution;
