@@ -34,17 +34,22 @@
 #define WMAR_FX_SCALE 70368744177664.0            /* 2^46  */
 #define WMAR_FX_INV 1.4210854715202004e-14        /* 2^-46 */
 
-/* Monotone map fp32 -> u32: a < b (as floats, no NaN)  <=>  key(a) < key(b).
- * -0.0f and +0.0f get adjacent, distinct keys (-0 < +0); torch's `<` treats
- * them as equal, which only matters for logits that are exactly +-0. */
+/* Order-preserving map fp32 -> u32 (no NaN): a < b as floats  <=>  key(a) < key(b), and
+ * a == b as floats  <=>  key(a) == key(b).  -0.0f and +0.0f are ONE value to every float
+ * comparison of the reference (`logits < kth`, torch.argmax, torch.sort), so they get ONE
+ * key, 0x80000000: a negative float's key is the two's complement of its bits (0 - b), not
+ * the one's complement, which would put -0.0 one step below +0.0.  Same cost: one integer
+ * operation.  Keys run from 0x00800000 (-inf) to 0xff800000 (+inf); key 0 is never produced.
+ * Only ORDER is decided on keys; the values themselves (-0.0 included) are never rewritten. */
 WMAR_HD uint32_t wmar_f32_key(float x) {
     uint32_t b;
     memcpy(&b, &x, 4);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return (b & 0x80000000u) ? (0u - b) : (b | 0x80000000u);
 }
 
+/* Inverse on the key's value class (key 0x80000000 gives +0.0f). */
 WMAR_HD float wmar_key_f32(uint32_t k) {
-    uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : (0u - k);
     float x;
     memcpy(&x, &b, 4);
     return x;

@@ -338,7 +338,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void k_sample_fused(SampArgs a) {
 #undef WMAR_PARK_Q
     kmax = block_max_u32(kmax, red_all[0]);
     const float m = wmar_key_f32(kmax);
-    const uint32_t NEG_INF_KEY = 0x007fffffu;  // wmar_f32_key(-inf)
+    const uint32_t NEG_INF_KEY = 0x00800000u;  // wmar_f32_key(-inf)
 
     // top-k: exact k-th largest key by 4 radix passes (count histograms)
     uint32_t thr_key = 0;
