@@ -503,6 +503,16 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 int wmar_augment(int32_t op, const float* in_dev, float* out_dev, const float* noise_dev, int64_t B, int32_t C, int32_t H,
                  int32_t W, int32_t pm1, double p0, double p1, void* stream);
 
+/* The vector-Jacobian product of wmar_augment as it is implemented, range change and clamp included (training through the transforms,
+ * finetune.py): grad_in = J^T grad_out at the forward input `in_dev`.  op, noise_dev, pm1, p0 and p1 mean what they mean to
+ * wmar_augment; all buffers are [B, C, H, W] fp32, contiguous.  The clamp passes the gradient where 0 <= t <= 1, both bounds included
+ * (as torch.clamp), with t recomputed by the forward's own arithmetic; the noise draws get no gradient.  Gather form, no atomics: two
+ * calls return the same bits.  `workspace_dev`: B * C * H * W floats, required for blur (two launches), NULL otherwise.  grad_in_dev
+ * may be grad_out_dev only for identity, noise, brightness and crop + pad.  Every argument is checked before the first launch. */
+int wmar_augment_backward(int32_t op, const float* in_dev, const float* grad_out_dev, float* grad_in_dev, const float* noise_dev,
+                          float* workspace_dev, int64_t B, int32_t C, int32_t H, int32_t W, int32_t pm1, double p0, double p1,
+                          void* stream);
+
 /* JPEG round trip at `quality` (1..100), valuemetric.py:30-75: bit for bit the pixels PIL's save(format="JPEG", quality=q) +
  * Image.open(...).convert("RGB") return (libjpeg-turbo's baseline path: 4:2:0, integer DCT, fancy upsampling), computed without a
  * bitstream.  [B, 3, H, W] fp32 in [0, 1] (clamped on entry), H and W multiples of 16; buffers 16-byte aligned, in != out.

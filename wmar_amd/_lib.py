@@ -24,7 +24,7 @@ SYMBOLS = [
     "wmar_cham_create", "wmar_cham_destroy", "wmar_cham_device_bytes", "wmar_cham_forward_tokens", "wmar_cham_generate_image",
     "wmar_cham_sample",
     "wmar_cfg_mix", "wmar_gpt_generate_hooked", "wmar_rar_generate_hooked", "wmar_cham_generate_image_hooked",
-    "wmar_augment", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
+    "wmar_augment", "wmar_augment_backward", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
     "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
@@ -131,6 +131,7 @@ def load():
     L.wmar_detect_num_ngrams.restype = i64
     L.wmar_detect_num_ngrams.argtypes = [i32, i32, i64]
     L.wmar_augment.argtypes = [i32, vp, vp, vp, i64, i32, i32, i32, i32, f64, f64, vp]
+    L.wmar_augment_backward.argtypes = [i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f64, f64, vp]
     L.wmar_jpeg_workspace_bytes.restype = i64
     L.wmar_jpeg_workspace_bytes.argtypes = [i64, i32, i32]
     L.wmar_jpeg.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp]

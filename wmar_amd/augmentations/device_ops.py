@@ -21,18 +21,56 @@ def eligible(image: torch.Tensor) -> bool:
     return image.is_cuda and image.dtype == torch.float32 and image.dim() in (3, 4)
 
 
-def run(op: int, image: torch.Tensor, p0: float = 0.0, p1: float = 0.0, noise: torch.Tensor = None, pm1: bool = False) -> torch.Tensor:
-    x = image.unsqueeze(0) if image.dim() == 3 else image
-    x = x.contiguous()
+def _launch(op: int, x: torch.Tensor, p0: float, p1: float, noise, pm1: bool) -> torch.Tensor:
     B, C, H, W = x.shape
     out = torch.empty_like(x)
-    if noise is not None:
-        noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
-        assert noise.numel() == x.numel()
     L = _lib.load()
     with torch.cuda.device(x.device):
         _lib.check(L.wmar_augment(int(op), x.data_ptr(), out.data_ptr(), noise.data_ptr() if noise is not None else None, B, C, H, W,
                                   1 if pm1 else 0, float(p0), float(p1), _lib.stream_ptr(x.device)))
+    return out
+
+
+class _Augment(torch.autograd.Function):
+    """``wmar_augment`` with its vector-Jacobian product ``wmar_augment_backward`` (csrc/augment.hip): the gradient of the launch as
+    it is implemented, range change and clamp included; the noise draws get none.  `x` is contiguous [B, C, H, W]."""
+
+    @staticmethod
+    def forward(ctx, x, op, p0, p1, noise, pm1):
+        ctx.save_for_backward(x, noise)
+        ctx.call = (op, p0, p1, pm1)
+        return _launch(op, x, p0, p1, noise, pm1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, noise = ctx.saved_tensors
+        op, p0, p1, pm1 = ctx.call
+        B, C, H, W = x.shape
+        g = grad_out.to(torch.float32).contiguous()
+        grad_in = torch.empty_like(x)
+        ws = torch.empty_like(x) if op == BLUR else None         # g * mask between the two blur launches
+        L = _lib.load()
+        with torch.cuda.device(x.device):
+            _lib.check(L.wmar_augment_backward(int(op), x.data_ptr(), g.data_ptr(), grad_in.data_ptr(),
+                                               noise.data_ptr() if noise is not None else None, ws.data_ptr() if ws is not None else None,
+                                               B, C, H, W, 1 if pm1 else 0, float(p0), float(p1), _lib.stream_ptr(x.device)))
+        return grad_in, None, None, None, None, None
+
+
+def run(op: int, image: torch.Tensor, p0: float = 0.0, p1: float = 0.0, noise: torch.Tensor = None, pm1: bool = False) -> torch.Tensor:
+    """One launch of transform `op` over the batch.  When a gradient is wanted of `image` the launch joins the autograd graph
+    (`_Augment`; unsqueeze / contiguous are torch's own differentiable steps, so the gradient returns in the shape and strides of the
+    original tensor); otherwise the launch alone."""
+    x = image.unsqueeze(0) if image.dim() == 3 else image
+    x = x.contiguous()
+    if noise is not None:
+        noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
+        assert noise.numel() == x.numel()
+    if torch.is_grad_enabled() and image.requires_grad:
+        out = _Augment.apply(x, int(op), float(p0), float(p1), noise.detach() if noise is not None else None, bool(pm1))
+    else:
+        out = _launch(op, x, p0, p1, noise, pm1)
     return out[0] if image.dim() == 3 else out
 
 

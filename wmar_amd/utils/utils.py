@@ -1,12 +1,37 @@
-"""Mirror of the pieces of ``wmar.utils.utils`` the generation harness uses
-(wmar/utils/utils.py:47-80): uint8 conversion and delta-checkpoint patching."""
+"""Mirror of the pieces of ``wmar.utils.utils`` the generation harness and a fine-tuning loop use
+(wmar/utils/utils.py:25-80): the random training augmentation, uint8 conversion and delta-checkpoint patching."""
 from __future__ import annotations
 
+import random
 from typing import Union
 
 import numpy as np
 import torch
 from PIL import Image
+
+
+def apply_random_augmentation(x, augmentations, p=0.5):
+    """One training-time augmentation of a [-1, 1] batch, behaving as the function of this name in wmar/utils/utils.py.
+
+    `augmentations` lists ``(module class, candidate parameters)`` pairs.  The host RNG is consulted in a fixed order -- a uniform
+    draw compared with `p`, then the pair, then the parameter -- and never more often than needed, so a seeded run picks what the
+    reference picks.  Returns ``(x, None)`` when nothing is applied (empty list, the draw is not below `p`, or the pair is
+    ``Identity``), else ``(augmented, (cls, parameter))``.  The modules work in [0, 1], so the batch is mapped there and back; the
+    gradient reaches `x` through the transform (on the MI355X through ``wmar_augment_backward``), except for ``JPEG``, whose
+    result only replaces the value of `x`: its gradient is the identity."""
+    from ..augmentations.geometric import Identity
+    from ..augmentations.valuemetric import JPEG
+    untouched = (x, None)
+    if not augmentations or random.random() >= p:
+        return untouched
+    module_cls, candidates = random.choice(augmentations)
+    if module_cls is Identity:
+        return untouched
+    chosen = random.choice(candidates)
+    augmented = 2.0 * module_cls()(0.5 * x + 0.5, chosen) - 1.0
+    if module_cls is JPEG:
+        augmented = x + (augmented - x).detach()
+    return augmented, (module_cls, chosen)
 
 
 def simple_rescale(x):
