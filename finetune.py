@@ -1,0 +1,155 @@
+"""Tokenizer fine-tuning (reverse-cycle-consistency) for ``--model taming`` on one MI355X: the reference's finetune.py flags, driving
+``wmar_amd.finetune.rcc_loss`` over the native trainable tokenizer.  Writes ``encoder_ft_delta.pth`` and ``decoder_ft_delta.pth`` into
+``--outdir`` in the form ``generate.py --encoder_ft_ckpt / --decoder_ft_ckpt`` accept.
+
+    python finetune.py --model taming --synthetic --synthetic_config harness --nb_epochs 1 --augs none --optimizer adam --lr 1e-4 \
+        --batch_size_per_gpu 2 --dataset_size 4 --idempotence_loss_weight 1.0 --idempotence_loss_weight_factor 1.0 --outdir out/
+
+Not built here, each rejected with a message: multi-GPU training (DDP), tensorboard logging, the validation pass, and the
+``chameleon7b`` / ``rar`` models."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import random
+import sys
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--model", type=str, default="taming", choices=["taming", "chameleon7b", "rar"])
+    p.add_argument("--modelpath", type=str, help="directory with configs/net2net.yaml and checkpoints/net2net.ckpt")
+    p.add_argument("--synthetic", action="store_true", help="random-init weights instead of --modelpath")
+    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "taming"])
+    p.add_argument("--datapath", type=str, help="int64 [N, S*S] codes, .pt or .npy (with --synthetic: random codes when absent)")
+    p.add_argument("--dataset_size", type=int, help="number of rows to use")
+    p.add_argument("--mode", type=str, default="newenc-dec")
+    p.add_argument("--nb_epochs", type=int, default=1)
+    p.add_argument("--augs", type=str, default="none", choices=["none", "all+geom"])
+    p.add_argument("--augs_schedule", type=str, default=None, help="epochs per augmentation stage, e.g. 1,1,4,4")
+    p.add_argument("--optimizer", type=str, default="adam")
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--batch_size_per_gpu", type=int, default=4)
+    p.add_argument("--idempotence_loss_weight", type=float, default=1.0)
+    p.add_argument("--idempotence_loss_weight_factor", type=float, default=1.0)
+    p.add_argument("--loss", type=str, default="hard-to-soft-with-ae")
+    p.add_argument("--outdir", type=str, required=True)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--max_steps", type=int, default=None, help="stop after this many optimizer steps")
+    p.add_argument("--local_rank", "--local-rank", type=int, default=-1)
+    p.add_argument("--tensorboard", action="store_true")
+    p.add_argument("--validate", action="store_true")
+    return p
+
+
+def check_args(args) -> None:
+    """Everything this CLI does not implement is refused here, before any model is built."""
+    if args.model != "taming":
+        raise SystemExit(f"finetune.py: --model {args.model} is not built: only the Taming tokenizer has a training engine")
+    if args.local_rank != -1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("finetune.py: multi-GPU training (DDP) is not built: run one process on one GPU")
+    if args.tensorboard:
+        raise SystemExit("finetune.py: tensorboard logging is not built: the log lines go to stdout as JSON")
+    if args.validate:
+        raise SystemExit("finetune.py: the validation pass is not built")
+    if args.mode != "newenc-dec":
+        raise SystemExit(f"finetune.py: --mode {args.mode} not supported (newenc-dec)")
+    if args.loss != "hard-to-soft-with-ae":
+        raise SystemExit(f"finetune.py: --loss {args.loss} not supported (hard-to-soft-with-ae)")
+    if args.optimizer != "adam":
+        raise SystemExit(f"finetune.py: --optimizer {args.optimizer} not supported (adam)")
+    if bool(args.modelpath) == bool(args.synthetic):
+        raise SystemExit("finetune.py: give exactly one of --modelpath and --synthetic")
+    if not args.synthetic and not args.datapath:
+        raise SystemExit("finetune.py: --datapath is required with --modelpath")
+
+
+def load_codes(path: str):
+    import numpy as np
+    import torch
+    codes = torch.from_numpy(np.load(path)) if path.endswith(".npy") else torch.load(path, map_location="cpu")
+    if codes.ndim != 2 or codes.dtype != torch.int64:
+        raise SystemExit(f"finetune.py: {path} must hold an int64 [N, S*S] tensor, got {codes.dtype} {tuple(codes.shape)}")
+    return codes
+
+
+def train(tok, orig, codes, args, log=print):
+    """Adam (0.9, 0.999) + StepLR(gamma 0.9 per epoch) over the encoder's and the decoder's weights; the idempotence weight is multiplied
+    by its factor after every epoch.  Returns the number of optimizer steps."""
+    import torch
+    from wmar_amd.augmentations import finetune_schedule
+    from wmar_amd.finetune import calculate_gradient_norm, rcc_loss
+    schedule = finetune_schedule(args.augs, args.augs_schedule, args.nb_epochs)
+    for k, prm in tok.named_parameters():
+        prm.requires_grad_(k.startswith(("encoder.", "decoder.")))          # the 1x1 quant convolutions stay as they are
+    params = list(tok.parameters(("encoder.", "decoder.")))
+    opt = torch.optim.Adam(params, lr=args.lr, betas=(0.9, 0.999))
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=1, gamma=0.9)
+    weight, steps, bs = args.idempotence_loss_weight, 0, args.batch_size_per_gpu
+    gen = torch.Generator().manual_seed(args.seed)
+    for epoch in range(args.nb_epochs):
+        order = torch.randperm(codes.shape[0], generator=gen)
+        for b0 in range(0, codes.shape[0], bs):
+            batch = codes[order[b0:b0 + bs]]
+            loss, _, log_dict, was_aug = rcc_loss(tok, batch, schedule[epoch], p=0.5, loss_weight=weight, orig=orig)
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            log_dict.update(epoch=epoch, step=steps, was_augmented=bool(was_aug), lr=sched.get_last_lr()[0],
+                            enc_grad_L2=calculate_gradient_norm(tok, "encoder."), dec_grad_L2=calculate_gradient_norm(tok, "decoder."))
+            opt.step()
+            steps += 1
+            log(json.dumps(log_dict))
+            if args.max_steps is not None and steps >= args.max_steps:
+                return steps
+        sched.step()
+        weight *= args.idempotence_loss_weight_factor
+    return steps
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    check_args(args)
+    import torch
+    from wmar_amd.finetune import save_delta
+    from wmar_amd.models.taming_wrapper import TamingARMMWrapper
+    from wmar_amd.models.tokenizer_train import TrainableTokenizer
+    from wmar_amd.utils import synth
+    random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    if args.synthetic:
+        g, v = ((synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)) if args.synthetic_config == "harness"
+                else (synth.TAMING_GPT, synth.TAMING_VQ))
+        model = TamingARMMWrapper.synthetic(g, v, seed=args.seed, max_batch=max(8, args.batch_size_per_gpu))
+    else:
+        model = TamingARMMWrapper(args.modelpath, max_batch=max(8, args.batch_size_per_gpu))
+    vcfg = model.model.vq_cfg
+    if args.datapath:
+        codes = load_codes(args.datapath)
+    else:
+        codes = torch.randint(0, vcfg.n_embed, (args.dataset_size or 4 * args.batch_size_per_gpu, vcfg.codes_size ** 2),
+                              generator=torch.Generator().manual_seed(args.seed))
+    if args.dataset_size:
+        codes = codes[:args.dataset_size]
+    if codes.shape[1] != vcfg.codes_size ** 2:
+        raise SystemExit(f"finetune.py: codes have {codes.shape[1]} columns, the tokenizer has {vcfg.codes_size ** 2}")
+    codes = codes.to(model.model.device)
+    tokenizer = model.get_image_tokenizer()
+    original = {k: v.detach().clone() for k, v in tokenizer.state_dict().items()}
+    orig = TrainableTokenizer(vcfg, {k: v.clone() for k, v in original.items()}, max_batch=args.batch_size_per_gpu, device=model.model.device)
+    for prm in orig.parameters():
+        prm.requires_grad_(False)
+    tok = model.trainable_tokenizer(max_batch=args.batch_size_per_gpu)
+    steps = train(tok, orig, codes, args)
+    os.makedirs(args.outdir, exist_ok=True)
+    for name in ("encoder", "decoder"):
+        handle = getattr(tokenizer, name)
+        n = len(name) + 1
+        save_delta(handle.state_dict(), {k[n:]: v for k, v in original.items() if k.startswith(name + ".")},
+                   os.path.join(args.outdir, f"{name}_ft_delta.pth"))
+    print(json.dumps({"steps": steps, "outdir": args.outdir, "device_bytes": tok.device_bytes}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -472,6 +472,55 @@ int wmar_vq_probe_attn(const float* q_dev, const float* k_dev, const float* v_de
 int wmar_vq_probe_argmin(const float* z_dev, int64_t P, int32_t E, const float* codebook_dev, int32_t n_embed, int64_t* codes_dev,
                          char* path_buf, int64_t buf_len, void* stream);
 
+/* Backward probes (wmar_amd/csrc/vq_grad.h): the backward of one layer alone, through the host functions a training engine would
+ * call (make_dgrad_conv / run_conv_dgrad / run_conv_wgrad, run_gn_backward, attn_backward), in the layout of the probes above.  No
+ * floating-point atomics anywhere: two calls on the same data give the same bits.
+ *
+ * Convolution (same four index maps as wmar_vq_probe_conv): w_dev [cout, cin, ks, ks], x_dev [B, Hs, Ws, cin_s] the conv's actual
+ * input, gy_dev [B, Ho, Wo, cout_s] the gradient of its output -> gx_dev [B, Hs, Ws, cin_s] (padding channels 0), gw_dev
+ * [cout, cin, ks, ks], gb_dev [cout].  The input gradient of a stride-1 conv is run_conv on the flipped, transposed weight (Hs, Ws --
+ * 2 Hs, 2 Ws with up -- multiples of 8, as for any conv here), followed by a 2 x 2 sum with up; stride 2 has a gather kernel.  The
+ * weight gradient is an fp32-input MFMA GEMM over K = B Ho Wo, split into K slices that a second launch adds in order.
+ * kernel_buf: "dgrad=<flip+conv kernel[+k_sum2x2] | k_dgrad_s2>;wgrad=<kernel>;splits=<K slices>;bgrad=<kernel>". */
+int wmar_vq_probe_conv_backward(const float* w_dev, int32_t cout, int32_t cin, int32_t ks, const float* x_dev, const float* gy_dev, int64_t B,
+                                int32_t Hs, int32_t Ws, int32_t stride, int32_t up, float* gx_dev, float* gw_dev, float* gb_dev,
+                                char* kernel_buf, int64_t buf_len, void* stream);
+/* GroupNorm(32, eps 1e-6), followed by swish when swish != 0: x_dev, gy_dev (gradient of the output), gx_dev [B, HW, C] (C a multiple
+ * of 32), mr_dev float [B, 32, 2] the forward's (mean, rstd), gamma_dev / beta_dev [C] -> gx_dev, dgamma_dev [C], dbeta_dev [C].
+ * path_buf: "path=<kernels>;chunks=<pixel chunks per image>". */
+int wmar_vq_probe_gn_backward(const float* x_dev, const float* gy_dev, const float* mr_dev, const float* gamma_dev, const float* beta_dev,
+                              int64_t B, int32_t HW, int32_t C, int32_t swish, float* gx_dev, float* dgamma_dev, float* dbeta_dev,
+                              char* path_buf, int64_t buf_len, void* stream);
+/* Attention core: runs the forward of wmar_vq_probe_attn (its softmax is the tape), then go_dev [B, H * W, C], the gradient of o ->
+ * gq_dev, gk_dev, gv_dev [B, H * W, C].  path_buf: "path=bf16_pipe|plain;forward=bf16_pipe|scalar". */
+int wmar_vq_probe_attn_backward(const float* q_dev, const float* k_dev, const float* v_dev, const float* go_dev, int64_t B, int32_t H, int32_t W,
+                                int32_t C, float* gq_dev, float* gk_dev, float* gv_dev, char* path_buf, int64_t buf_len, void* stream);
+
+/* Trainable Taming VQGAN (wmar_amd/csrc/vq_train.h): encoder + quant_conv and post_quant_conv + decoder with a forward that records a
+ * tape and a backward that delivers the input gradient and every conv / GroupNorm weight gradient (the codebook is frozen).  The
+ * forwards make the launches of wmar_vq_encode / wmar_vq_decode in their order and are bit-equal to them (decode: before the clamp,
+ * VQModel.decode).  Each half has a tape of its own -- one step can hold both -- sized at create time for cfg->max_batch images; no
+ * call allocates.  Same checkpoint keys as wmar_vq_create (quantize.* is not read).
+ *
+ * set_weights repacks every weight in place (after an optimizer step) and invalidates both tapes.  A backward needs the tape of its
+ * half: it returns WMAR_EINVAL (and leaves the engine usable) without a forward since create / set_weights or with a B other than the
+ * forward's.  grad_images_dev / grad_zq_dev may be NULL when only weight gradients are wanted.  get_grads copies (accumulate == 0) or
+ * adds (accumulate != 0) the torch-layout gradients of the named "<layer>.weight" / "<layer>.bias" tensors from the last backward of
+ * their half.  Reductions have a fixed order everywhere: two runs give the same bits. */
+typedef struct wmar_vq_train wmar_vq_train;
+int wmar_vq_train_create(const wmar_vq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                         wmar_vq_train** out);
+void wmar_vq_train_destroy(wmar_vq_train* t);
+int64_t wmar_vq_train_device_bytes(const wmar_vq_train* t);
+int wmar_vq_train_set_weights(wmar_vq_train* t, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream);
+/* images_dev [B, 3, R, R] -> prequant_dev [B*S*S, embed_dim] = quant_conv(encoder(x)) */
+int wmar_vq_train_encode(wmar_vq_train* t, const float* images_dev, int64_t B, float* prequant_dev, void* stream);
+int wmar_vq_train_encode_backward(wmar_vq_train* t, const float* grad_prequant_dev, int64_t B, float* grad_images_dev, void* stream);
+/* zq_dev [B*S*S, embed_dim] -> images_dev [B, 3, R, R], NOT clamped */
+int wmar_vq_train_decode(wmar_vq_train* t, const float* zq_dev, int64_t B, float* images_dev, void* stream);
+int wmar_vq_train_decode_backward(wmar_vq_train* t, const float* grad_images_dev, int64_t B, float* grad_zq_dev, void* stream);
+int wmar_vq_train_get_grads(wmar_vq_train* t, const char* const* names, void* const* grads_dev, int32_t n, int32_t accumulate, void* stream);
+
 /* --------------------------------------------------------------- MaskGIT-VQGAN (RAR's tokenizer)
  * deps/rar/modeling/modules/maskgit_vqgan.py + PretrainedTokenizer (deps/rar/modeling/titok.py:41-89).
  * Tensors by key name (encoder.*, decoder.*, quantize.embedding.weight).  Images cross this API in the

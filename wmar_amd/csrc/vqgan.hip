@@ -1999,3 +1999,7 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 }
 
 }  // extern "C"
+
+// ============================================================================ layer backward (tokenizer fine-tuning)
+#include "vq_grad.h"
+#include "vq_train.h"

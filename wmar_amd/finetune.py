@@ -1,0 +1,87 @@
+"""Reverse-cycle-consistency (RCC) fine-tuning of the Taming tokenizer: the loss of ``VQModel.forward``
+(deps/taming/models/vqgan.py:93-169) for the precomputed-codes input, and the helpers of the reference's finetune.py
+(``compute_and_save_delta``, ``calculate_gradient_norm``, wmar/utils/utils.py:189-227).
+
+``tok`` is anything with ``embed(indices)``, ``decode(z_q)``, ``encode_prequant(images)``, ``quantize(z)`` and
+``named_parameters(prefix)`` -- on the MI355X a ``TrainableTokenizer`` (wmar_amd/models/tokenizer_train.py)."""
+from __future__ import annotations
+
+import math
+from typing import Callable, Dict, Optional
+
+import torch
+
+from .utils.utils import apply_random_augmentation
+
+
+def idempotence_region(S: int, applied):
+    """The slice of the S x S code grid the idempotence loss is taken over (vqgan.py:141-150): the inner 6/8 for ``Rotate``, the
+    upper-left ``floor(S * param)`` for ``UpperLeftCropWithPadBack``, everything otherwise.  ``applied`` = (module class, parameter) or None."""
+    from .augmentations.geometric import Rotate, UpperLeftCropWithPadBack
+    if applied is not None and applied[0] is Rotate:
+        skip = S // 8
+        return slice(skip, S - skip)
+    if applied is not None and applied[0] is UpperLeftCropWithPadBack:
+        return slice(0, int(math.floor(S * applied[1])))
+    return slice(0, S)
+
+
+def rcc_loss(tok, z_indices: torch.Tensor, augmentations, p: float = 0.5, loss_weight: float = 1.0, orig=None,
+             rec_loss: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None):
+    """decode -> ``apply_random_augmentation`` -> re-encode -> quantize, loss ``hard-to-soft-with-ae``: the regulariser
+    ``rec_loss(xrec, orig.decode(z_q))`` plus ``loss_weight`` x the mean squared difference between the original (hard) code vectors
+    and the re-encoded (soft) ones over ``idempotence_region``.  ``orig``: a frozen tokenizer holding the original decoder (the
+    reference's ``orig_decoder``); None drops the regulariser.  ``rec_loss`` defaults to the mean absolute difference.  The reference
+    adds LPIPS to it; LPIPS needs VGG weights this project does not ship, so a perceptual term stays a caller-supplied callable.
+    Returns the reference's ``(loss, res_dict, log_dict, was_augmented)``."""
+    z_q = tok.embed(z_indices)
+    xrec = tok.decode(z_q)
+    log_dict: Dict[str, float] = {}
+    xrec_orig = None
+    reg = xrec.new_zeros(())
+    if orig is not None:
+        with torch.no_grad():
+            xrec_orig = orig.decode(z_q)
+        reg = rec_loss(xrec, xrec_orig) if rec_loss is not None else (xrec - xrec_orig).abs().mean()
+        log_dict["rec_loss"] = float(reg.detach())
+    applied = None
+    xaug = xrec
+    if augmentations is not None and len(augmentations) > 0:
+        xaug, applied = apply_random_augmentation(xrec, augmentations, p=p)
+    was_augmented = applied is not None
+    zrec = tok.encode_prequant(xaug)
+    zrec_q, zrec_indices = tok.quantize(zrec.detach())
+    assert zrec.shape == z_q.shape, f"zrec shape {tuple(zrec.shape)} != zq shape {tuple(z_q.shape)}"
+    r = idempotence_region(z_q.shape[2], applied)
+    idem = torch.mean((z_q[:, :, r, r] - zrec[:, :, r, r]) ** 2)
+    loss = reg + loss_weight * idem
+    log_dict["idem_loss"] = float(idem.detach())
+    log_dict["loss"] = float(loss.detach())
+    log_dict["loss_weight"] = loss_weight
+    res_dict = {"orig_z_q": z_q, "orig_z_indices": z_indices, "rec_x": xrec, "rec_x_maybe_augmented": xaug, "rec_x_orig_decoder": xrec_orig,
+                "rec_z": zrec, "rec_z_q": zrec_q, "rec_z_indices": zrec_indices}
+    return loss, res_dict, log_dict, was_augmented
+
+
+def save_delta(trained_state: Dict[str, torch.Tensor], original_state: Dict[str, torch.Tensor], path: str) -> Dict[str, torch.Tensor]:
+    """Writes ``{key: trained - original}`` (CPU tensors) for the keys both states hold: what ``update_weights(module, path, delta=True)``
+    adds back (``compute_and_save_delta``, wmar/utils/utils.py:215-227).  Keys are relative to the module the delta is for."""
+    diff = {}
+    for k, v in trained_state.items():
+        if k in original_state:
+            diff[k] = v.detach().cpu() - original_state[k].detach().cpu()
+        else:
+            print(f"Diffing Warning: Key {k} not found in original state dict")
+    torch.save(diff, path)
+    return diff
+
+
+def calculate_gradient_norm(tok, prefix: str) -> float:
+    """sqrt(sum |grad|^2 / parameter count) over the parameters under ``prefix`` (wmar/utils/utils.py:189-213); a parameter without a
+    gradient counts with norm 0."""
+    total, count = 0.0, 0
+    for _, prm in tok.named_parameters(prefix):
+        if prm.grad is not None:
+            total += float(torch.norm(prm.grad)) ** 2
+        count += prm.numel()
+    return math.sqrt(total / count) if count else 0.0
