@@ -1,12 +1,18 @@
-"""Tokenizer fine-tuning (reverse-cycle-consistency) for ``--model taming`` on one MI355X: the reference's finetune.py flags, driving
-``wmar_amd.finetune.rcc_loss`` over the native trainable tokenizer.  Writes ``encoder_ft_delta.pth`` and ``decoder_ft_delta.pth`` into
-``--outdir`` in the form ``generate.py --encoder_ft_ckpt / --decoder_ft_ckpt`` accept.
+"""Tokenizer fine-tuning (reverse-cycle-consistency) for ``--model taming`` and ``--model rar`` on one MI355X: the reference's
+finetune.py flags, driving ``wmar_amd.finetune.rcc_loss`` over the native trainable tokenizer (the Taming VQGAN, or RAR's
+MaskGIT-VQGAN).  Writes ``encoder_ft_delta.pth`` and ``decoder_ft_delta.pth`` into ``--outdir`` in the form
+``generate.py --encoder_ft_ckpt / --decoder_ft_ckpt`` accept.
 
     python finetune.py --model taming --synthetic --synthetic_config harness --nb_epochs 1 --augs none --optimizer adam --lr 1e-4 \
         --batch_size_per_gpu 2 --dataset_size 4 --idempotence_loss_weight 1.0 --idempotence_loss_weight_factor 1.0 --outdir out/
+    python finetune.py --model rar --synthetic --synthetic_config maskgit_small --nb_epochs 1 --augs none --batch_size_per_gpu 2 \
+        --dataset_size 4 --outdir out/
+
+``--synthetic_config`` names are bound to models: ``harness`` / ``taming`` are Taming shapes, ``maskgit_small`` / ``maskgit`` are
+MaskGIT shapes for ``--model rar``; ``--model rar --modelpath DIR`` loads ``RarARMMWrapper(DIR)``.
 
 Not built here, each rejected with a message: multi-GPU training (DDP), tensorboard logging, the validation pass, and the
-``chameleon7b`` / ``rar`` models."""
+``chameleon7b`` model."""
 from __future__ import annotations
 
 import argparse
@@ -19,9 +25,10 @@ import sys
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--model", type=str, default="taming", choices=["taming", "chameleon7b", "rar"])
-    p.add_argument("--modelpath", type=str, help="directory with configs/net2net.yaml and checkpoints/net2net.ckpt")
+    p.add_argument("--modelpath", type=str, help="taming: directory with configs/net2net.yaml and checkpoints/net2net.ckpt; "
+                                                 "rar: directory with maskgit-vqgan-imagenet-f16-256.bin and rar_xl.bin")
     p.add_argument("--synthetic", action="store_true", help="random-init weights instead of --modelpath")
-    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "taming"])
+    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "taming", "maskgit_small", "maskgit"])
     p.add_argument("--datapath", type=str, help="int64 [N, S*S] codes, .pt or .npy (with --synthetic: random codes when absent)")
     p.add_argument("--dataset_size", type=int, help="number of rows to use")
     p.add_argument("--mode", type=str, default="newenc-dec")
@@ -43,10 +50,17 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+# the synthetic shapes each trainable model takes
+SYNTHETIC_CONFIGS = {"taming": ("harness", "taming"), "rar": ("maskgit_small", "maskgit")}
+
+
 def check_args(args) -> None:
     """Everything this CLI does not implement is refused here, before any model is built."""
-    if args.model != "taming":
-        raise SystemExit(f"finetune.py: --model {args.model} is not built: only the Taming tokenizer has a training engine")
+    if args.model not in SYNTHETIC_CONFIGS:
+        raise SystemExit(f"finetune.py: --model {args.model} is not built: only the Taming and the RAR tokenizers have a training engine")
+    if args.synthetic and args.synthetic_config not in SYNTHETIC_CONFIGS[args.model]:
+        raise SystemExit(f"finetune.py: --synthetic_config {args.synthetic_config} is not a shape of --model {args.model}: "
+                         f"choose from {', '.join(SYNTHETIC_CONFIGS[args.model])}")
     if args.local_rank != -1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("finetune.py: multi-GPU training (DDP) is not built: run one process on one GPU")
     if args.tensorboard:
@@ -107,27 +121,52 @@ def train(tok, orig, codes, args, log=print):
     return steps
 
 
+def synthetic_rar_configs(name: str):
+    """(RARConfig, MaskgitVQConfig) of a ``--synthetic_config`` of ``--model rar``.  The transformer is not trained: a small one whose
+    sequence is the tokenizer's code grid."""
+    from wmar_amd.utils import synth
+    v = (synth.MaskgitVQConfig(hidden_channels=32, channel_mult=(1, 2, 2), num_res_blocks=1, resolution=32, z_channels=16, num_embeddings=512)
+         if name == "maskgit_small" else synth.MASKGIT_VQ)
+    r = synth.RARConfig(hidden_size=128, num_hidden_layers=2, num_attention_heads=4, intermediate_size=512, image_seq_len=v.codes_size ** 2,
+                        codebook_size=v.num_embeddings)
+    return r, v
+
+
+def load_model(args):
+    """The wrapper of ``--model``, its tokenizer config, the codebook size and the class of its trainable tokenizer."""
+    from wmar_amd.models import tokenizer_train as tt
+    from wmar_amd.utils import synth
+    mb = max(8, args.batch_size_per_gpu)
+    if args.model == "rar":
+        from wmar_amd.models.rar_wrapper import RarARMMWrapper
+        if args.synthetic:
+            r, v = synthetic_rar_configs(args.synthetic_config)
+            model = RarARMMWrapper.synthetic(r, v, seed=args.seed, max_batch=mb)
+        else:
+            model = RarARMMWrapper(args.modelpath, max_batch=mb)
+        return model, model._vq_cfg, model._vq_cfg.num_embeddings, tt.MaskgitTrainableTokenizer
+    from wmar_amd.models.taming_wrapper import TamingARMMWrapper
+    if args.synthetic:
+        g, v = ((synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)) if args.synthetic_config == "harness"
+                else (synth.TAMING_GPT, synth.TAMING_VQ))
+        model = TamingARMMWrapper.synthetic(g, v, seed=args.seed, max_batch=mb)
+    else:
+        model = TamingARMMWrapper(args.modelpath, max_batch=mb)
+    return model, model.model.vq_cfg, model.model.vq_cfg.n_embed, tt.TrainableTokenizer
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     check_args(args)
     import torch
     from wmar_amd.finetune import save_delta
-    from wmar_amd.models.taming_wrapper import TamingARMMWrapper
-    from wmar_amd.models.tokenizer_train import TrainableTokenizer
-    from wmar_amd.utils import synth
     random.seed(args.seed)
     torch.manual_seed(args.seed)
-    if args.synthetic:
-        g, v = ((synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)) if args.synthetic_config == "harness"
-                else (synth.TAMING_GPT, synth.TAMING_VQ))
-        model = TamingARMMWrapper.synthetic(g, v, seed=args.seed, max_batch=max(8, args.batch_size_per_gpu))
-    else:
-        model = TamingARMMWrapper(args.modelpath, max_batch=max(8, args.batch_size_per_gpu))
-    vcfg = model.model.vq_cfg
+    model, vcfg, n_codes, tok_class = load_model(args)
     if args.datapath:
         codes = load_codes(args.datapath)
     else:
-        codes = torch.randint(0, vcfg.n_embed, (args.dataset_size or 4 * args.batch_size_per_gpu, vcfg.codes_size ** 2),
+        codes = torch.randint(0, n_codes, (args.dataset_size or 4 * args.batch_size_per_gpu, vcfg.codes_size ** 2),
                               generator=torch.Generator().manual_seed(args.seed))
     if args.dataset_size:
         codes = codes[:args.dataset_size]
@@ -136,7 +175,7 @@ def main(argv=None) -> int:
     codes = codes.to(model.model.device)
     tokenizer = model.get_image_tokenizer()
     original = {k: v.detach().clone() for k, v in tokenizer.state_dict().items()}
-    orig = TrainableTokenizer(vcfg, {k: v.clone() for k, v in original.items()}, max_batch=args.batch_size_per_gpu, device=model.model.device)
+    orig = tok_class(vcfg, {k: v.clone() for k, v in original.items()}, max_batch=args.batch_size_per_gpu, device=model.model.device)
     for prm in orig.parameters():
         prm.requires_grad_(False)
     tok = model.trainable_tokenizer(max_batch=args.batch_size_per_gpu)

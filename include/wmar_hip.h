@@ -496,6 +496,18 @@ int wmar_vq_probe_gn_backward(const float* x_dev, const float* gy_dev, const flo
 int wmar_vq_probe_attn_backward(const float* q_dev, const float* k_dev, const float* v_dev, const float* go_dev, int64_t B, int32_t H, int32_t W,
                                 int32_t C, float* gq_dev, float* gk_dev, float* gv_dev, char* path_buf, int64_t buf_len, void* stream);
 
+/* Backward of the three layers only the MaskGIT-VQGAN plan has, each alone (no allocation, the stream is waited for, no engine path
+ * calls them).  All three are exact in fp32: bit-equal to torch's fp32 autograd.
+ * Average pool 2 x 2: gy_dev [B, Ho, Wo, C] (C a multiple of 4) -> gx_dev [B, 2 Ho, 2 Wo, C] = gy * 0.25 of the element's window. */
+int wmar_vq_probe_avgpool_backward(const float* gy_dev, int64_t B, int32_t Ho, int32_t Wo, int32_t C, float* gx_dev, void* stream);
+/* Decode edge, clamp(v, 0, 1) * 2 - 1: pre_dev [B, HW, Cs] the value v in front of the clamp (Cs >= C stored channels, a multiple of 4),
+ * g_nchw_dev [B, C, HW] the image gradient -> g_nhwc_dev [B, HW, Cs] = 2 g where 0 <= v <= 1 (bounds included), 0 elsewhere and in the
+ * padding channels. */
+int wmar_mvq_probe_image_backward(const float* pre_dev, const float* g_nchw_dev, int64_t B, int32_t C, int32_t HW, int32_t Cs, float* g_nhwc_dev,
+                                  void* stream);
+/* Encode edge, (x + 1) / 2: g_nhwc_dev [B, HW, Cs] -> g_nchw_dev [B, C, HW] = g * 0.5. */
+int wmar_mvq_probe_input_backward(const float* g_nhwc_dev, int64_t B, int32_t C, int32_t HW, int32_t Cs, float* g_nchw_dev, void* stream);
+
 /* Trainable Taming VQGAN (wmar_amd/csrc/vq_train.h): encoder + quant_conv and post_quant_conv + decoder with a forward that records a
  * tape and a backward that delivers the input gradient and every conv / GroupNorm weight gradient (the codebook is frozen).  The
  * forwards make the launches of wmar_vq_encode / wmar_vq_decode in their order and are bit-equal to them (decode: before the clamp,
@@ -541,6 +553,20 @@ int64_t wmar_mvq_device_bytes(const wmar_mvq* v);
 int wmar_mvq_decode(wmar_mvq* v, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream);
 int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* codes_dev, float* prequant_dev,
                     void* stream);
+
+/* Trainable MaskGIT-VQGAN (wmar_amd/csrc/vq_train.h): the plan of wmar_mvq_encode / wmar_mvq_decode as a wmar_vq_train handle, as RAR's
+ * fine-tuning differentiates it (deps/rar/modeling/titok.py:91-208).  Every wmar_vq_train_* entry above serves the handle; the taped
+ * forwards make the inference engine's launches in its order and are bit-equal to it.  For such a handle:
+ *   - images cross in the wrapper's [-1, 1] convention, as for wmar_mvq_*;
+ *   - wmar_vq_train_decode takes z_q rows [B*S*S, z_channels] and returns clamp(decoder(z_q), 0, 1) * 2 - 1; its backward passes the
+ *     gradient where the taped value in front of the clamp lies in [0, 1] (bounds included) and multiplies it by 2;
+ *   - wmar_vq_train_encode returns the encoder output rows [B*S*S, z_channels] of encoder((x + 1) / 2); its backward's image gradient
+ *     carries the factor 0.5;
+ *   - the convolutions inside the ResnetBlocks (conv1, conv2, nin_shortcut) and encoder.conv_in have no bias: set_weights needs none,
+ *     and wmar_vq_train_get_grads on such a "<layer>.bias" returns WMAR_EINVAL naming the tensor and leaves the engine usable.
+ * Same checkpoint keys as wmar_mvq_create (quantize.* is not read). */
+int wmar_mvq_train_create(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                          wmar_vq_train** out);
 
 /* ------------------------------------------------------------------------ evaluation transforms (harness)
  * wmar/augmentations/valuemetric.py:41-140, geometric.py:22-117 as applied by generate.py:142-164: one launch over the whole batch

@@ -20,6 +20,7 @@ SYMBOLS = [
     "wmar_gpt_set_timing", "wmar_gpt_set_attention_phases", "wmar_gpt_get_timing", "wmar_gpt_profile_role", "wmar_gpt_plan_info", "wmar_gpt_check", "wmar_rar_create", "wmar_rar_destroy",
     "wmar_rar_device_bytes", "wmar_rar_forward_position", "wmar_rar_generate", "wmar_vq_create", "wmar_vq_destroy", "wmar_vq_device_bytes",
     "wmar_vq_decode", "wmar_vq_encode", "wmar_vq_probe_conv", "wmar_vq_probe_attn", "wmar_vq_probe_argmin", "wmar_vq_probe_conv_backward", "wmar_vq_probe_gn_backward", "wmar_vq_probe_attn_backward",
+    "wmar_vq_probe_avgpool_backward", "wmar_mvq_probe_image_backward", "wmar_mvq_probe_input_backward", "wmar_mvq_train_create",
     "wmar_vq_train_create", "wmar_vq_train_destroy", "wmar_vq_train_device_bytes", "wmar_vq_train_set_weights", "wmar_vq_train_encode",
     "wmar_vq_train_encode_backward", "wmar_vq_train_decode", "wmar_vq_train_decode_backward", "wmar_vq_train_get_grads", "wmar_mvq_create", "wmar_mvq_destroy", "wmar_mvq_device_bytes", "wmar_mvq_decode",
     "wmar_mvq_encode", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
@@ -197,6 +198,10 @@ def load():
         L.wmar_vq_probe_conv_backward.argtypes = [vp, i32, i32, i32, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, C.c_char_p, i64, vp]
         L.wmar_vq_probe_gn_backward.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, C.c_char_p, i64, vp]
         L.wmar_vq_probe_attn_backward.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, C.c_char_p, i64, vp]
+        L.wmar_vq_probe_avgpool_backward.argtypes = [vp, i64, i32, i32, i32, vp, vp]
+        L.wmar_mvq_probe_image_backward.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp]
+        L.wmar_mvq_probe_input_backward.argtypes = [vp, i64, i32, i32, i32, vp, vp]
+        L.wmar_mvq_train_create.argtypes = [C.POINTER(MvqConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
         L.wmar_vq_train_create.argtypes = [C.POINTER(VqConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
         L.wmar_vq_train_destroy.argtypes = [vp]
         L.wmar_vq_train_destroy.restype = None

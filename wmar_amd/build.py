@@ -84,7 +84,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         with ThreadPoolExecutor(max_workers=4) as ex:
             list(ex.map(run, jobs))
     objs = [os.path.join(objdir, s + ".o") for s, _ in srcs]
-    if jobs or not os.path.exists(LIB):
+    # an interrupted build can leave fresh objects behind an old library
+    if jobs or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
         if verbose:
             print(" ".join(cmd), flush=True)

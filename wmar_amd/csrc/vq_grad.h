@@ -22,6 +22,9 @@
 //   attention  dV = P^T dO, dP = dO V^T, dS = scale P o (dP - rowsum(dP o P)), dQ = dS K, dK = dS^T Q with the taped softmax P.
 //           The four products run as 1 x 1 convolutions with per-image packed weights (as attn_core's do) where that path takes the
 //           shape, else through k_bmm_plain.
+//   MaskGIT-VQGAN (RAR's tokenizer) adds three elementwise adjoints, all exact in fp32: the 2 x 2 average pool (k_avgpool2_bwd), and
+//           the two image edges its fine-tuning differentiates -- clamp(v, 0, 1) * 2 - 1 behind the decoder (k_mvq_image_bwd) and
+//           (x + 1) / 2 in front of the encoder (k_mvq_input_bwd).
 #pragma once
 
 namespace wmar {
@@ -53,6 +56,54 @@ __global__ void k_sum2x2(const float* __restrict__ in, float* __restrict__ out, 
     const float4 c2 = *(const float4*)(p + 2LL * W * C), d = *(const float4*)(p + 2LL * W * C + C);
     *(float4*)(out + pix * C + c) = make_float4((a.x + b2.x) + (c2.x + d.x), (a.y + b2.y) + (c2.y + d.y), (a.z + b2.z) + (c2.z + d.z),
                                                 (a.w + b2.w) + (c2.w + d.w));
+}
+
+// Adjoint of k_avgpool2 (MaskGIT-VQGAN downsampling), gather form: gy [B][Ho][Wo][C] -> gx [B][2Ho][2Wo][C], every input element
+// takes a quarter of its window's gradient (g * 0.25f == g / 4 in fp32, what avg_pool2d's backward computes).
+__global__ void k_avgpool2_bwd(const float* __restrict__ gy, float* __restrict__ gx, int Ho, int Wo, int C) {
+    const long long q4 = C >> 2;
+    const long long total = (long long)(2 * Ho) * (2 * Wo) * q4;
+    const long long b = blockIdx.y;
+    const float* gb = gy + b * (long long)Ho * Wo * C;
+    float* xb = gx + b * (long long)(2 * Ho) * (2 * Wo) * C;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(e % q4) * 4;
+        const long long pix = e / q4;
+        const int ix = (int)(pix % (2 * Wo)), iy = (int)(pix / (2 * Wo));
+        const float4 g = *(const float4*)(gb + ((long long)(iy >> 1) * Wo + (ix >> 1)) * C + c);
+        *(float4*)(xb + pix * C + c) = make_float4(g.x * 0.25f, g.y * 0.25f, g.z * 0.25f, g.w * 0.25f);
+    }
+}
+
+// Adjoint of k_nhwc_to_nchw_01 (clamp(v, 0, 1) * 2 - 1 on the decoder output): pre [B][HW][Cs] the taped value v in front of the clamp,
+// g [B][C][HW] the image gradient -> out [B][HW][Cs] = 2 g where 0 <= v <= 1 (both bounds included, as torch.clamp's backward), else 0;
+// padding channels 0.  One thread per pixel: the reads of g are coalesced per channel, pre and out move as float4.
+__global__ void k_mvq_image_bwd(const float* __restrict__ pre, const float* __restrict__ g, float* __restrict__ out, int C, int HW, int Cs) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long b = blockIdx.y;
+    if (idx >= HW) return;
+    const float* p = pre + (b * HW + idx) * Cs;
+    float* o = out + (b * HW + idx) * Cs;
+    for (int c0 = 0; c0 < Cs; c0 += 4) {
+        const float4 v4 = *(const float4*)(p + c0);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+        float r[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = c0 + i;
+            const float gv = c < C ? g[(b * C + c) * HW + idx] : 0.0f;
+            r[i] = (c < C && v[i] >= 0.0f && v[i] <= 1.0f) ? 2.0f * gv : 0.0f;
+        }
+        *(float4*)(o + c0) = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
+// Adjoint of k_nchw_to_nhwc01 ((x + 1) / 2 in front of the encoder): g [B][HW][Cs] -> out [B][C][HW] = g * 0.5f
+__global__ void k_mvq_input_bwd(const float* __restrict__ g, float* __restrict__ out, int C, int HW, int Cs) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long b = blockIdx.y;
+    if (idx >= HW) return;
+    for (int c = 0; c < C; ++c) out[(b * C + c) * HW + idx] = g[(b * HW + idx) * Cs + c] * 0.5f;
 }
 
 // Adjoint of the 3 x 3 stride-2 convolution with zero pad (0, 1, 0, 1) (Downsample.forward): out[oy][ox] reads x[2 oy + dy][2 ox + dx],
@@ -465,6 +516,28 @@ int run_gn_backward(const float* x, const float* gy, const float2* mr, const flo
     return launch_status("k_gnb");
 }
 
+// 2 x 2 average pool backward: gy [B][Ho][Wo][C] -> gx [B][2Ho][2Wo][C]; the grid is k_avgpool2's rule on the input-sized tensor
+int run_avgpool_backward(const float* gy, float* gx, int B, int Ho, int Wo, int C, hipStream_t st) {
+    WMAR_REQUIRE(C % 4 == 0, "average pool backward: channel count %d is not a multiple of 4", C);
+    const long long total = (long long)(2 * Ho) * (2 * Wo) * (C / 4);
+    int gx_ = (int)((total + 255) / 256);
+    if (gx_ > 8192) gx_ = 8192;
+    hipLaunchKernelGGL(k_avgpool2_bwd, dim3(gx_, (unsigned)B), dim3(256), 0, st, gy, gx, Ho, Wo, C);
+    return launch_status("k_avgpool2_bwd");
+}
+
+// the two image edges of the MaskGIT-VQGAN halves (k_mvq_image_bwd, k_mvq_input_bwd)
+int run_mvq_image_backward(const float* pre, const float* g_nchw, float* g_nhwc, int B, int C, int HW, int Cs, hipStream_t st) {
+    WMAR_REQUIRE(Cs % 4 == 0 && C <= Cs, "image backward: %d channels stored as %d", C, Cs);
+    hipLaunchKernelGGL(k_mvq_image_bwd, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, pre, g_nchw, g_nhwc, C, HW, Cs);
+    return launch_status("k_mvq_image_bwd");
+}
+int run_mvq_input_backward(const float* g_nhwc, float* g_nchw, int B, int C, int HW, int Cs, hipStream_t st) {
+    WMAR_REQUIRE(C <= Cs, "input backward: %d channels stored as %d", C, Cs);
+    hipLaunchKernelGGL(k_mvq_input_bwd, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, g_nhwc, g_nchw, C, HW, Cs);
+    return launch_status("k_mvq_input_bwd");
+}
+
 // Backward of attn_core with the taped softmax P [B][N][N]: dO -> dQ, dK, dV (all [B][N][C]).  dp, tr: [B][N][N] floats of scratch
 // each; s.attk / s.attv / s.zbias as attn_core takes them.
 int attn_backward(const AttnScratch& s, float* dp, float* tr, const float* q, const float* k, const float* vv, const float* P, const float* dO,
@@ -597,6 +670,29 @@ int wmar_vq_probe_attn_backward(const float* q_dev, const float* k_dev, const fl
         if (!(n > 0 && n < buf_len)) { set_error("vq_probe_attn_backward: buffer of %lld bytes too small", (long long)buf_len); rc = WMAR_EINVAL; }
     }
     return probe_finish(rc, st);
+}
+
+int wmar_vq_probe_avgpool_backward(const float* gy_dev, int64_t B, int32_t Ho, int32_t Wo, int32_t C, float* gx_dev, void* stream) {
+    WMAR_REQUIRE(gy_dev && gx_dev, "vq_probe_avgpool_backward: null argument");
+    WMAR_REQUIRE(B >= 1 && B <= 1024 && Ho >= 1 && Wo >= 1 && C >= 4 && C % 4 == 0 && (long long)B * Ho * Wo * C < (1LL << 38),
+                 "vq_probe_avgpool_backward: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    return probe_finish(run_avgpool_backward(gy_dev, gx_dev, (int)B, Ho, Wo, C, st), st);
+}
+
+int wmar_mvq_probe_image_backward(const float* pre_dev, const float* g_nchw_dev, int64_t B, int32_t C, int32_t HW, int32_t Cs, float* g_nhwc_dev,
+                                  void* stream) {
+    WMAR_REQUIRE(pre_dev && g_nchw_dev && g_nhwc_dev, "mvq_probe_image_backward: null argument");
+    WMAR_REQUIRE(B >= 1 && B <= 1024 && C >= 1 && HW >= 1 && Cs >= C && Cs % 4 == 0, "mvq_probe_image_backward: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    return probe_finish(run_mvq_image_backward(pre_dev, g_nchw_dev, g_nhwc_dev, (int)B, C, HW, Cs, st), st);
+}
+
+int wmar_mvq_probe_input_backward(const float* g_nhwc_dev, int64_t B, int32_t C, int32_t HW, int32_t Cs, float* g_nchw_dev, void* stream) {
+    WMAR_REQUIRE(g_nhwc_dev && g_nchw_dev, "mvq_probe_input_backward: null argument");
+    WMAR_REQUIRE(B >= 1 && B <= 1024 && C >= 1 && HW >= 1 && Cs >= C, "mvq_probe_input_backward: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    return probe_finish(run_mvq_input_backward(g_nhwc_dev, g_nchw_dev, (int)B, C, HW, Cs, st), st);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Trainable Taming VQGAN (gfx950): a forward that records a tape, and the backward of encoder + quant_conv and of post_quant_conv +
+// Trainable VQGAN tokenizers (gfx950; Taming first, MaskGIT below): a forward that records a tape, and the backward of encoder + quant_conv and of post_quant_conv +
 // decoder, built from the layer functions of vq_grad.h.  Included at the end of vqgan.hip behind vq_grad.h.
 //
 // Reference: deps/taming/models/vqgan.py:64-73 (encode / decode) under torch.autograd, as finetune.py trains them
@@ -12,6 +12,11 @@
 // AttnBlock: residual + q, k, v) gets the next one through a scratch buffer and an elementwise add -- stream order, no atomics.
 // The convs behind one norm (q, k, v) add their input gradients into one buffer first; the norm's backward then runs once.
 // All memory is allocated at create time for max_batch images.
+//
+// wmar_mvq_train_create builds the same handle for RAR's MaskGIT-VQGAN (deps/rar/modeling/modules/maskgit_vqgan.py, titok.py:91-208):
+// a second pair of op lists in wmar_mvq_encode's / wmar_mvq_decode's order -- bias-free block convs, the 1 x 1 shortcut on the block
+// output, average pools, no attention, no quant convs -- with the [-1, 1] <-> [0, 1] range change and the clamp differentiated at the
+// image edges.
 #pragma once
 
 namespace wmar {
@@ -70,9 +75,10 @@ struct TConv {
     float *w = nullptr, *wt = nullptr;  // raw weight (the stride-2 gather reads it), flipped weight
     float *gw = nullptr, *gb = nullptr;
     int cin = 0, cout = 0, ks = 1, stride = 1;
+    bool bias = true;                  // false: a bias-free conv (MaskGIT-VQGAN blocks, encoder.conv_in) -- no gb, no ".bias" gradient
     std::string name;
 };
-enum { T_GN = 0, T_CONV = 1, T_ATTN = 2 };
+enum { T_GN = 0, T_CONV = 1, T_ATTN = 2, T_POOL = 3 };
 struct TOp { int kind = 0, in = -1, out = -1, res = -1, conv = -1, norm = -1, swish = 0, up = 0, q = -1, k = -1, v = -1; float* P = nullptr; };
 struct THalf { std::vector<TOp> ops; int first = -1, last = -1, B = 0; bool tape = false, grads = false; };
 struct TGrad { float* p; size_t n; int half; };
@@ -83,6 +89,7 @@ struct wmar_vq_train {
     wmar_vq_config cfg{};
     DeviceArena mem;
     int Bmax = 0, S = 0;
+    bool mvq = false;                   // MaskGIT-VQGAN plan: images cross in [-1, 1], the range change and the clamp are differentiated
     std::vector<TTensor> t;
     std::vector<TNorm> norms;
     std::vector<TConv> convs;
@@ -148,14 +155,14 @@ struct TrainBuilder {
         e->norms.push_back(n);
         return (int)e->norms.size() - 1;
     }
-    int conv(const std::string& name, int cin, int cout, int ks, int stride, int hidx) {
-        TConv c; c.name = name; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride;
+    int conv(const std::string& name, int cin, int cout, int ks, int stride, int hidx, bool bias = true) {
+        TConv c; c.name = name; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride; c.bias = bias;
         const size_t nw = (size_t)cout * cin * ks * ks;
-        ld.conv(name, cin, cout, ks, c.fw);
+        ld.conv(name, cin, cout, ks, c.fw, bias);
         const float* W = ld.need(name + ".weight");
         WMAR_TRY(e->mem.alloc(&c.w, nw));
         WMAR_TRY(e->mem.alloc(&c.gw, nw));
-        WMAR_TRY(e->mem.alloc(&c.gb, (size_t)cout));
+        if (bias) WMAR_TRY(e->mem.alloc(&c.gb, (size_t)cout));
         if (rc == WMAR_OK && hipMemcpyAsync(c.w, W, nw * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("weight copy failed"); rc = WMAR_EHIP; }
         if (stride == 1 && rc == WMAR_OK) {
             WMAR_TRY(e->mem.alloc(&c.wt, nw));
@@ -169,17 +176,18 @@ struct TrainBuilder {
             }
         }
         e->grad_of[name + ".weight"] = TGrad{c.gw, nw, hidx};
-        e->grad_of[name + ".bias"] = TGrad{c.gb, (size_t)cout, hidx};
+        if (bias) e->grad_of[name + ".bias"] = TGrad{c.gb, (size_t)cout, hidx};
         e->convs.push_back(c);
         return (int)e->convs.size() - 1;
     }
     void op_gn(THalf& h, int in, int n, int swish) { TOp o; o.kind = T_GN; o.in = in; o.norm = n; o.swish = swish; h.ops.push_back(o); }
     // returns the output tensor
-    int op_conv(THalf& h, int hidx, const std::string& name, int cin, int cout, int ks, int in, int res, int n, int swish, int stride, int up) {
+    int op_conv(THalf& h, int hidx, const std::string& name, int cin, int cout, int ks, int in, int res, int n, int swish, int stride, int up,
+                bool bias = true) {
         const int Hin = e->t[in].H;
         const int Ho = up ? 2 * Hin : (stride == 2 ? Hin / 2 : Hin);
         TOp o; o.kind = T_CONV; o.in = in; o.res = res; o.norm = n; o.swish = swish; o.up = up;
-        o.conv = conv(name, cin, cout, ks, stride, hidx);
+        o.conv = conv(name, cin, cout, ks, stride, hidx, bias);
         o.out = tensor(cout, Ho);
         h.ops.push_back(o);
         if (up) { const size_t u = (size_t)e->Bmax * Ho * Ho * pad8(cin); if (u > e->ups_elems) e->ups_elems = u; }
@@ -199,6 +207,29 @@ struct TrainBuilder {
         int shortcut = X;
         if (cin != cout) shortcut = op_conv(h, hidx, p + "nin_shortcut", cin, cout, 1, X, -1, -1, 0, 1, 0);
         return op_conv(h, hidx, p + "conv2", cout, cout, 3, T, shortcut, n2, 1, 1, 0);
+    }
+    // run_mres: bias-free convs; out = h + nin_shortcut(h) with h = conv2(...) when cin != cout (a 1 x 1 conv whose input and residual
+    // are the same tensor), else h + x
+    int mres(THalf& h, int hidx, const std::string& p, int cin, int cout, int X) {
+        const int H = e->t[X].H;
+        const int n1 = norm(p + "norm1", cin, hidx);
+        note_norm(cin, H);
+        op_gn(h, X, n1, 1);
+        const int T = op_conv(h, hidx, p + "conv1", cin, cout, 3, X, -1, n1, 1, 1, 0, false);
+        const int n2 = norm(p + "norm2", cout, hidx);
+        note_norm(cout, H);
+        op_gn(h, T, n2, 1);
+        if (cin != cout) {
+            const int A = op_conv(h, hidx, p + "conv2", cout, cout, 3, T, -1, n2, 1, 1, 0, false);
+            return op_conv(h, hidx, p + "nin_shortcut", cout, cout, 1, A, A, -1, 0, 1, 0, false);
+        }
+        return op_conv(h, hidx, p + "conv2", cout, cout, 3, T, X, n2, 1, 1, 0, false);
+    }
+    int op_pool(THalf& h, int in) {                                                          // k_avgpool2
+        TOp o; o.kind = T_POOL; o.in = in;
+        o.out = tensor(e->t[in].C, e->t[in].H / 2);
+        h.ops.push_back(o);
+        return o.out;
     }
     int attn(THalf& h, int hidx, const std::string& p, int c, int X) {                      // run_attn
         const int H = e->t[X].H;
@@ -223,6 +254,24 @@ struct TrainBuilder {
     }
 };
 
+// the buffers every plan shares, sized by what the builder noted; zbias_elems: the zeros attention reads as a bias
+void train_scratch(wmar_vq_train* e, int& rc, size_t zbias_elems, hipStream_t st) {
+    WMAR_TRY(e->mem.alloc(&e->ybuf, e->max_elems));
+    WMAR_TRY(e->mem.alloc(&e->ngy, e->max_elems));
+    WMAR_TRY(e->mem.alloc(&e->gtmp, e->max_elems));
+    WMAR_TRY(e->mem.alloc(&e->ups, e->ups_elems));
+    WMAR_TRY(e->mem.alloc(&e->ws, e->ws_elems));
+    WMAR_TRY(e->mem.alloc(&e->gnb, e->gnb_doubles));
+    WMAR_TRY(e->mem.alloc(&e->dp, e->attn_nn));
+    WMAR_TRY(e->mem.alloc(&e->tr, e->attn_nn));
+    WMAR_TRY(e->mem.alloc(&e->attk, e->attn_nc * 3 / 8 + 1));
+    WMAR_TRY(e->mem.alloc(&e->attv, e->attn_nc * 3 / 8 + 1));
+    WMAR_TRY(e->mem.alloc_zero(&e->zbias, zbias_elems, st));
+    WMAR_TRY(e->mem.alloc(&e->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)e->Bmax * GN_CHUNKS_MAX * 32 * 2));
+    e->gn_tiles_cap = (long long)e->Bmax * (e->cfg.resolution / 8) * (e->cfg.resolution / 8) * 64;
+    WMAR_TRY(e->mem.alloc(&e->gn_tiles, (size_t)e->gn_tiles_cap));
+}
+
 int train_forward(wmar_vq_train* e, THalf& h, int B, hipStream_t st) {
     int rc;
     g_trk = GnTrack{};
@@ -238,6 +287,15 @@ int train_forward(wmar_vq_train* e, THalf& h, int B, hipStream_t st) {
             const TTensor& x = e->t[o.in];
             if ((rc = run_conv(e->convs[o.conv].fw, x.d, e->t[o.out].d, o.res >= 0 ? e->t[o.res].d : nullptr, B, x.H, x.H, e->convs[o.conv].stride,
                                o.up, st, o.norm >= 0 ? &gn : nullptr))) return rc;
+        } else if (o.kind == T_POOL) {                          // wmar_mvq_encode's launch
+            const TTensor& x = e->t[o.in];
+            const TTensor& y = e->t[o.out];
+            const long long total = (long long)y.H * y.H * (x.C / 4);
+            int gx = (int)((total + 255) / 256);
+            if (gx > 8192) gx = 8192;
+            hipLaunchKernelGGL(k_avgpool2, dim3(gx, (unsigned)B), dim3(256), 0, st, (const float*)x.d, y.d, y.H, y.H, x.C);
+            if (g_trk.src == y.d) g_trk.src = nullptr;
+            if ((rc = launch_status("k_avgpool2"))) return rc;
         } else {
             const TTensor& q = e->t[o.q];
             if ((rc = attn_core(AttnScratch{o.P, e->attk, e->attv, e->zbias}, q.d, e->t[o.k].d, e->t[o.v].d, e->t[o.out].d, B, q.H, q.H, q.C, st)))
@@ -312,6 +370,12 @@ int train_backward(wmar_vq_train* e, THalf& h, int B, bool want_input_grad, hipS
             if ((rc = run_gn_backward(x.d, e->ngy, n.mr, n.n.g, n.n.b, n.n.C, B, x.H * x.H, o.swish, e->gnb, grad_target(e, x), n.dg, n.db, st))) return rc;
             if ((rc = grad_commit(e, x, B, st))) return rc;
             e->ngy_set = false;
+        } else if (o.kind == T_POOL) {
+            TTensor& x = e->t[o.in];
+            const TTensor& y = e->t[o.out];
+            WMAR_REQUIRE(y.gset, "vq_train backward: no gradient reached the output of an average pool");
+            if ((rc = run_avgpool_backward(y.g, grad_target(e, x), B, y.H, y.H, x.C, st))) return rc;
+            if ((rc = grad_commit(e, x, B, st))) return rc;
         } else {
             const TTensor& out = e->t[o.out];
             TTensor &q = e->t[o.q], &k = e->t[o.k], &v = e->t[o.v];
@@ -416,29 +480,84 @@ int wmar_vq_train_create(const wmar_vq_config* cfg, const char* const* names, co
         x = b.op_conv(h, 1, "decoder.conv_out", block_in, cfg->out_ch, 3, x, -1, no, 1, 1, 0);
         h.last = x;
     }
-    // ---- scratch
-    WMAR_TRY(e->mem.alloc(&e->ybuf, e->max_elems));
-    WMAR_TRY(e->mem.alloc(&e->ngy, e->max_elems));
-    WMAR_TRY(e->mem.alloc(&e->gtmp, e->max_elems));
-    WMAR_TRY(e->mem.alloc(&e->ups, e->ups_elems));
-    WMAR_TRY(e->mem.alloc(&e->ws, e->ws_elems));
-    WMAR_TRY(e->mem.alloc(&e->gnb, e->gnb_doubles));
-    WMAR_TRY(e->mem.alloc(&e->dp, e->attn_nn));
-    WMAR_TRY(e->mem.alloc(&e->tr, e->attn_nn));
-    WMAR_TRY(e->mem.alloc(&e->attk, e->attn_nc * 3 / 8 + 1));
-    WMAR_TRY(e->mem.alloc(&e->attv, e->attn_nc * 3 / 8 + 1));
     {
         int amax = S;
         for (int i = 0; i < cfg->n_attn_res; ++i) amax = cfg->attn_resolutions[i] > amax ? cfg->attn_resolutions[i] : amax;
         int cam = 0;
         for (int lvl = 0; lvl < L; ++lvl) cam = ch * cfg->ch_mult[lvl] > cam ? ch * cfg->ch_mult[lvl] : cam;
-        const size_t nz = (size_t)amax * amax > (size_t)cam ? (size_t)amax * amax : (size_t)cam;
-        WMAR_TRY(e->mem.alloc_zero(&e->zbias, nz, st));
+        train_scratch(e, rc, (size_t)amax * amax > (size_t)cam ? (size_t)amax * amax : (size_t)cam, st);
     }
-    WMAR_TRY(e->mem.alloc(&e->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)e->Bmax * GN_CHUNKS_MAX * 32 * 2));
-    e->gn_tiles_cap = (long long)e->Bmax * (cfg->resolution / 8) * (cfg->resolution / 8) * 64;
-    WMAR_TRY(e->mem.alloc(&e->gn_tiles, (size_t)e->gn_tiles_cap));
     if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("vq_train_create: sync failed"); rc = WMAR_EHIP; }
+    if (rc != WMAR_OK) { const int r = rc; delete e; return r; }
+    *out = e;
+    return WMAR_OK;
+}
+
+// The MaskGIT-VQGAN plan (RAR's tokenizer) through the same machinery, written in the order wmar_mvq_encode / wmar_mvq_decode make their
+// calls.  Reference: deps/rar/modeling/modules/maskgit_vqgan.py and titok.py:91-208 (decode_like_taming, encode_like_taming_prequant).
+int wmar_mvq_train_create(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                          wmar_vq_train** out) {
+    WMAR_REQUIRE(cfg && names && tensors_dev && out, "mvq_train_create: null argument");
+    WMAR_REQUIRE(cfg->n_levels >= 1 && cfg->n_levels <= 8 && cfg->max_batch >= 1, "mvq_train_create: bad config");
+    WMAR_REQUIRE(cfg->z_channels % 8 == 0 && cfg->hidden_channels % 32 == 0, "z_channels %% 8 and hidden_channels %% 32 must be 0");
+    const int R = cfg->n_levels, hc = cfg->hidden_channels, z = cfg->z_channels;
+    const int S = cfg->resolution >> (R - 1);
+    WMAR_REQUIRE(S >= 8 && S % 8 == 0 && (S << (R - 1)) == cfg->resolution, "latent size %d must be a multiple of 8", S);
+    auto* e = new wmar_vq_train();
+    e->mvq = true; e->Bmax = cfg->max_batch; e->S = S;
+    e->cfg.ch = hc; e->cfg.num_res_blocks = cfg->num_res_blocks; e->cfg.resolution = cfg->resolution;
+    e->cfg.in_channels = e->cfg.out_ch = cfg->num_channels; e->cfg.z_channels = e->cfg.embed_dim = z;
+    e->cfg.n_embed = cfg->num_embeddings; e->cfg.n_levels = R; e->cfg.max_batch = cfg->max_batch;
+    for (int i = 0; i < R; ++i) e->cfg.ch_mult[i] = cfg->channel_mult[i];
+    hipStream_t st = (hipStream_t)stream;
+    Loader ld(names, tensors_dev, n_tensors, &e->mem, st);
+    int& rc = ld.rc;
+    TrainBuilder b{e, ld, st, rc};
+    const int mid = hc * cfg->channel_mult[R - 1];
+    // ---- encoder, in wmar_mvq_encode's order
+    {
+        THalf& h = e->half[0];
+        int x = b.tensor(cfg->num_channels, cfg->resolution);
+        h.first = x;
+        x = b.op_conv(h, 0, "encoder.conv_in", cfg->num_channels, hc, 3, x, -1, -1, 0, 1, 0, false);
+        for (int lvl = 0; lvl < R; ++lvl) {
+            int bi = hc * (lvl == 0 ? 1 : cfg->channel_mult[lvl - 1]);
+            const int bo = hc * cfg->channel_mult[lvl];
+            for (int i = 0; i < cfg->num_res_blocks; ++i) {
+                x = b.mres(h, 0, "encoder.down." + std::to_string(lvl) + ".block." + std::to_string(i) + ".", bi, bo, x);
+                bi = bo;
+            }
+            if (lvl != R - 1) x = b.op_pool(h, x);
+        }
+        for (int i = 0; i < cfg->num_res_blocks; ++i) x = b.mres(h, 0, "encoder.mid." + std::to_string(i) + ".", mid, mid, x);
+        const int no = b.norm("encoder.norm_out", mid, 0);
+        b.note_norm(mid, S);
+        b.op_gn(h, x, no, 1);
+        h.last = b.op_conv(h, 0, "encoder.conv_out", mid, z, 1, x, -1, no, 1, 1, 0);
+    }
+    // ---- decoder, in wmar_mvq_decode's order
+    {
+        THalf& h = e->half[1];
+        int x = b.tensor(z, S);
+        h.first = x;
+        x = b.op_conv(h, 1, "decoder.conv_in", z, mid, 3, x, -1, -1, 0, 1, 0);
+        for (int i = 0; i < cfg->num_res_blocks; ++i) x = b.mres(h, 1, "decoder.mid." + std::to_string(i) + ".", mid, mid, x);
+        for (int lvl = R - 1; lvl >= 0; --lvl) {
+            int bi = lvl == R - 1 ? mid : hc * cfg->channel_mult[lvl + 1];
+            const int bo = hc * cfg->channel_mult[lvl];
+            for (int i = 0; i < cfg->num_res_blocks; ++i) {
+                x = b.mres(h, 1, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(i) + ".", bi, bo, x);
+                bi = bo;
+            }
+            if (lvl != 0) x = b.op_conv(h, 1, "decoder.up." + std::to_string(lvl) + ".upsample_conv", bo, bo, 3, x, -1, -1, 0, 1, 1);
+        }
+        const int no = b.norm("decoder.norm_out", hc * cfg->channel_mult[0], 1);
+        b.note_norm(hc * cfg->channel_mult[0], cfg->resolution);
+        b.op_gn(h, x, no, 1);
+        h.last = b.op_conv(h, 1, "decoder.conv_out", hc * cfg->channel_mult[0], cfg->num_channels, 3, x, -1, no, 1, 1, 0);
+    }
+    train_scratch(e, rc, 1, st);                               // no attention in this network
+    if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("mvq_train_create: sync failed"); rc = WMAR_EHIP; }
     if (rc != WMAR_OK) { const int r = rc; delete e; return r; }
     *out = e;
     return WMAR_OK;
@@ -452,12 +571,12 @@ int wmar_vq_train_set_weights(wmar_vq_train* e, const char* const* names, const 
     hipStream_t st = (hipStream_t)stream;
     TensorMap tm(names, tensors_dev, n_tensors);
     // every name is looked up before anything is written
-    for (const TConv& c : e->convs) { (void)(const float*)tm.need(c.name + ".weight"); (void)(const float*)tm.need(c.name + ".bias"); }
+    for (const TConv& c : e->convs) { (void)(const float*)tm.need(c.name + ".weight"); if (c.bias) (void)(const float*)tm.need(c.name + ".bias"); }
     for (const TNorm& n : e->norms) { (void)(const float*)tm.need(n.name + ".weight"); (void)(const float*)tm.need(n.name + ".bias"); }
     if (tm.rc) return tm.rc;
     e->half[0].tape = e->half[1].tape = false;
     for (TConv& c : e->convs)
-        if (int rc = repack_conv(c, tm.get(c.name + ".weight"), tm.get(c.name + ".bias"), st)) return rc;
+        if (int rc = repack_conv(c, tm.get(c.name + ".weight"), c.bias ? (const float*)tm.get(c.name + ".bias") : nullptr, st)) return rc;
     for (TNorm& n : e->norms) {
         WMAR_HIP_CHECK(hipMemcpyAsync(n.n.g, tm.get(n.name + ".weight"), (size_t)n.n.C * 4, hipMemcpyDeviceToDevice, st));
         WMAR_HIP_CHECK(hipMemcpyAsync(n.n.b, tm.get(n.name + ".bias"), (size_t)n.n.C * 4, hipMemcpyDeviceToDevice, st));
@@ -473,7 +592,8 @@ int wmar_vq_train_encode(wmar_vq_train* e, const float* images_dev, int64_t B, f
     h.tape = false; h.grads = false;
     const int R = e->cfg.resolution;
     const TTensor& x0 = e->t[h.first];
-    hipLaunchKernelGGL(k_nchw_to_nhwc, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, images_dev, x0.d, e->cfg.in_channels, R * R, x0.C);
+    hipLaunchKernelGGL(e->mvq ? k_nchw_to_nhwc01 : k_nchw_to_nhwc, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, images_dev, x0.d,
+                       e->cfg.in_channels, R * R, x0.C);
     if (int rc = launch_status("k_nchw_to_nhwc")) return rc;
     if (int rc = train_forward(e, h, (int)B, st)) return rc;
     const TTensor& zo = e->t[h.last];
@@ -497,9 +617,13 @@ int wmar_vq_train_encode_backward(wmar_vq_train* e, const float* grad_prequant_d
     if (grad_images_dev) {
         const int R = e->cfg.resolution;
         const TTensor& x0 = e->t[h.first];
-        hipLaunchKernelGGL(k_nhwc_to_nchw, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, (const float*)x0.g, grad_images_dev,
-                           e->cfg.in_channels, R * R, x0.C);
-        if (int rc = launch_status("k_nhwc_to_nchw")) return rc;
+        if (e->mvq) {                                           // through (x + 1) / 2
+            if (int rc = run_mvq_input_backward(x0.g, grad_images_dev, (int)B, e->cfg.in_channels, R * R, x0.C, st)) return rc;
+        } else {
+            hipLaunchKernelGGL(k_nhwc_to_nchw, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, (const float*)x0.g, grad_images_dev,
+                               e->cfg.in_channels, R * R, x0.C);
+            if (int rc = launch_status("k_nhwc_to_nchw")) return rc;
+        }
     }
     h.grads = true;
     return WMAR_OK;
@@ -516,7 +640,8 @@ int wmar_vq_train_decode(wmar_vq_train* e, const float* zq_dev, int64_t B, float
     if (int rc = train_forward(e, h, (int)B, st)) return rc;
     const int R = e->cfg.resolution;
     const TTensor& yo = e->t[h.last];
-    hipLaunchKernelGGL(k_nhwc_to_nchw, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, (const float*)yo.d, images_dev, e->cfg.out_ch, R * R, yo.C);
+    hipLaunchKernelGGL(e->mvq ? k_nhwc_to_nchw_01 : k_nhwc_to_nchw, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, (const float*)yo.d,
+                       images_dev, e->cfg.out_ch, R * R, yo.C);
     if (int rc = launch_status("k_nhwc_to_nchw")) return rc;
     h.tape = true; h.B = (int)B;
     return WMAR_OK;
@@ -532,8 +657,12 @@ int wmar_vq_train_decode_backward(wmar_vq_train* e, const float* grad_images_dev
     train_clear_grads(e, h);
     const int R = e->cfg.resolution;
     TTensor& yo = e->t[h.last];
-    hipLaunchKernelGGL(k_nchw_to_nhwc, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, grad_images_dev, yo.g, e->cfg.out_ch, R * R, yo.C);
-    if (int rc = launch_status("k_nchw_to_nhwc")) return rc;
+    if (e->mvq) {                                               // through clamp(v, 0, 1) * 2 - 1 on the taped v
+        if (int rc = run_mvq_image_backward(yo.d, grad_images_dev, yo.g, (int)B, e->cfg.out_ch, R * R, yo.C, st)) return rc;
+    } else {
+        hipLaunchKernelGGL(k_nchw_to_nhwc, dim3((R * R + 255) / 256, (unsigned)B), dim3(256), 0, st, grad_images_dev, yo.g, e->cfg.out_ch, R * R, yo.C);
+        if (int rc = launch_status("k_nchw_to_nhwc")) return rc;
+    }
     yo.gset = true;
     if (int rc = train_backward(e, h, (int)B, grad_zq_dev != nullptr, st)) return rc;
     if (grad_zq_dev) {

@@ -1,9 +1,12 @@
-"""Reverse-cycle-consistency (RCC) fine-tuning of the Taming tokenizer: the loss of ``VQModel.forward``
-(deps/taming/models/vqgan.py:93-169) for the precomputed-codes input, and the helpers of the reference's finetune.py
-(``compute_and_save_delta``, ``calculate_gradient_norm``, wmar/utils/utils.py:189-227).
+"""Reverse-cycle-consistency (RCC) fine-tuning of an image tokenizer: the loss of ``VQModel.forward``
+(deps/taming/models/vqgan.py:93-169) and of RAR's ``PretrainedTokenizer.forward`` (deps/rar/modeling/titok.py:125-208) for the
+precomputed-codes input -- the two are the same computation over ``decode`` / ``encode_prequant`` -- and the helpers of the
+reference's finetune.py (``compute_and_save_delta``, ``calculate_gradient_norm``, wmar/utils/utils.py:189-227).
 
 ``tok`` is anything with ``embed(indices)``, ``decode(z_q)``, ``encode_prequant(images)``, ``quantize(z)`` and
-``named_parameters(prefix)`` -- on the MI355X a ``TrainableTokenizer`` (wmar_amd/models/tokenizer_train.py)."""
+``named_parameters(prefix)`` -- on the MI355X a ``TrainableTokenizer`` or a ``MaskgitTrainableTokenizer``
+(wmar_amd/models/tokenizer_train.py).  For RAR ``decode`` is ``decode_like_taming`` (clamped, [-1, 1]) and ``encode_prequant`` takes
+[-1, 1] images (titok.py:91-123), so the loss below needs no RAR branch."""
 from __future__ import annotations
 
 import math
@@ -15,7 +18,8 @@ from .utils.utils import apply_random_augmentation
 
 
 def idempotence_region(S: int, applied):
-    """The slice of the S x S code grid the idempotence loss is taken over (vqgan.py:141-150): the inner 6/8 for ``Rotate``, the
+    """The slice of the S x S code grid the idempotence loss is taken over (vqgan.py:141-150; titok.py:180-189 has the same three
+    cases): the inner 6/8 for ``Rotate``, the
     upper-left ``floor(S * param)`` for ``UpperLeftCropWithPadBack``, everything otherwise.  ``applied`` = (module class, parameter) or None."""
     from .augmentations.geometric import Rotate, UpperLeftCropWithPadBack
     if applied is not None and applied[0] is Rotate:

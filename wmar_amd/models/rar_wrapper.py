@@ -93,6 +93,13 @@ class RarARMMWrapper(AutoregressiveMultimodalModelWrapper):
     def get_vq(self):
         return self.tokenizer.quantize
 
+    def trainable_tokenizer(self, max_batch: int = 4):
+        """The image tokenizer as a trainable module on this wrapper's own weights (wmar_amd/models/tokenizer_train.py): what it trains
+        is what ``get_image_tokenizer().state_dict()`` returns, and the packed inference engine is rebuilt after every change."""
+        from .tokenizer_train import MaskgitTrainableTokenizer
+        return MaskgitTrainableTokenizer(self._vq_cfg, self._vq_state, max_batch=max_batch, device=self.model.device,
+                                         on_change=self._drop_vq_engine)
+
     def get_total_vocab_size(self):
         return self.get_vq().num_embeddings
 

@@ -1,5 +1,6 @@
-"""Trainable Taming VQGAN on the MI355X: ``quant_conv(encoder(x))`` and ``decoder(post_quant_conv(z_q))`` as autograd functions
-over the native taped engine (``wmar_vq_train_*``, include/wmar_hip.h; wmar_amd/csrc/vq_train.h).
+"""Trainable VQGAN tokenizers on the MI355X: ``quant_conv(encoder(x))`` and ``decoder(post_quant_conv(z_q))`` as autograd functions
+over the native taped engine (``wmar_vq_train_*``, include/wmar_hip.h; wmar_amd/csrc/vq_train.h).  ``TrainableTokenizer`` is the Taming
+network; ``MaskgitTrainableTokenizer`` is RAR's MaskGIT-VQGAN through the same engine and the same class, with another create call.
 
 What the reference trains with ``VQModel.encode`` / ``VQModel.decode`` under torch.autograd (deps/taming/models/vqgan.py:64-73,
 86-169; finetune.py).  The parameters ARE the tensors of the wrapper's ``{checkpoint key: tensor}`` state, made leaves with
@@ -9,7 +10,12 @@ drops its packed inference engine) is called whenever a forward finds the weight
 The two forwards are ``torch.autograd.Function``s.  Their backward returns the input gradient and ADDS the weight gradients into the
 parameters' ``.grad`` itself (the engine hands over all gradients of a half in one call).  Each half has one tape: a backward must
 belong to the LAST forward of its half, anything else raises.  Under ``torch.no_grad()``, or when nothing requires a gradient, the
-forwards run on a second engine (created on first use) and leave the tapes alone.  There is no PyTorch fallback."""
+forwards run on a second engine (created on first use) and leave the tapes alone.  There is no PyTorch fallback.
+
+The MaskGIT flavour is what the reference's RAR fine-tuning differentiates (deps/rar/modeling/titok.py:91-208): ``decode`` is
+``decode_like_taming`` -- ``clamp(decoder(z_q), 0, 1) * 2 - 1``, images in [-1, 1] -- and ``encode_prequant`` is
+``encoder((x + 1) / 2)``; the range changes and the clamp are inside the engine's forward and backward.  There is no ``quant_conv`` /
+``post_quant_conv`` (``embed_dim == z_channels``), and the block convolutions and ``encoder.conv_in`` have no bias."""
 from __future__ import annotations
 
 import ctypes as C
@@ -45,16 +51,27 @@ def _vq_config(cfg, max_batch: int) -> "_lib.VqConfig":
     return c
 
 
-class _TrainEngine:
-    """Owner of one wmar_vq_train handle."""
+def _mvq_config(cfg, max_batch: int) -> "_lib.MvqConfig":
+    c = _lib.MvqConfig()
+    c.hidden_channels, c.num_res_blocks, c.resolution = cfg.hidden_channels, cfg.num_res_blocks, cfg.resolution
+    c.num_channels, c.z_channels, c.num_embeddings = cfg.num_channels, cfg.z_channels, cfg.num_embeddings
+    c.n_levels = len(cfg.channel_mult)
+    for i, m in enumerate(cfg.channel_mult):
+        c.channel_mult[i] = m
+    c.max_batch = int(max_batch)
+    return c
 
-    def __init__(self, cfg, tensors: Dict[str, torch.Tensor], max_batch: int, device):
+
+class _TrainEngine:
+    """Owner of one wmar_vq_train handle; ``create`` names the entry that builds it, ``abi_cfg`` is that entry's config struct."""
+
+    def __init__(self, create: str, abi_cfg, tensors: Dict[str, torch.Tensor], device):
         self._L = _lib.load()
         self.device = device
         names, ptrs, n = _lib.tensor_table(tensors)
         h = C.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(self._L.wmar_vq_train_create(C.byref(_vq_config(cfg, max_batch)), names, ptrs, n, _lib.stream_ptr(device), C.byref(h)))
+            _lib.check(getattr(self._L, create)(C.byref(abi_cfg), names, ptrs, n, _lib.stream_ptr(device), C.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -99,8 +116,20 @@ class _Decode(torch.autograd.Function):
 
 
 class TrainableTokenizer:
+    # what a flavour of the network supplies: the create entry, its config struct, and (code width, image channels in, out)
+    _create = "wmar_vq_train_create"
+    _abi_config = staticmethod(_vq_config)
+
+    @staticmethod
+    def _dims(cfg) -> Tuple[int, int, int]:
+        return cfg.embed_dim, cfg.in_channels, cfg.out_ch
+
+    def _engine(self) -> _TrainEngine:
+        return _TrainEngine(self._create, self._abi_config(self.cfg, self.max_batch), self._tensors(), self.device)
+
     def __init__(self, cfg, state: Dict[str, torch.Tensor], max_batch: int = 4, device="cuda", on_change: Optional[Callable[[], None]] = None):
         self.cfg, self.state, self.max_batch = cfg, state, int(max_batch)
+        self._E, self._Cin, self._Cout = self._dims(cfg)
         self.device = torch.device(device)
         self._on_change = on_change
         self._keys = [k for k in state if _half_of(k) is not None]
@@ -110,7 +139,7 @@ class TrainableTokenizer:
             if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_leaf:
                 raise ValueError(f"TrainableTokenizer: {k} must be a contiguous float32 leaf tensor")
             t.requires_grad_(True)
-        self._train = _TrainEngine(cfg, self._tensors(), self.max_batch, self.device)
+        self._train = self._engine()
         self._eval: Optional[_TrainEngine] = None
         self._versions = self._current_versions()
         self._tape = [0, 0]            # serial number of the forward each half's tape belongs to
@@ -153,18 +182,18 @@ class TrainableTokenizer:
 
     # ------------------------------------------------------------------ forwards / backwards
     def _run(self, engine: _TrainEngine, half: int, x: torch.Tensor) -> torch.Tensor:
-        c, S, R, B = self.cfg, self.cfg.codes_size, self.cfg.resolution, x.shape[0]
+        S, R, B = self.cfg.codes_size, self.cfg.resolution, x.shape[0]
         if half == 0:
-            out = torch.empty(B, S, S, c.embed_dim, dtype=torch.float32, device=self.device)
+            out = torch.empty(B, S, S, self._E, dtype=torch.float32, device=self.device)
             engine.call("encode", x.data_ptr(), B, out.data_ptr())
             return out.permute(0, 3, 1, 2)
-        out = torch.empty(B, c.out_ch, R, R, dtype=torch.float32, device=self.device)
+        out = torch.empty(B, self._Cout, R, R, dtype=torch.float32, device=self.device)
         engine.call("decode", x.data_ptr(), B, out.data_ptr())
         return out
 
     def _prepare(self, half: int, x: torch.Tensor) -> torch.Tensor:
-        c, S, R = self.cfg, self.cfg.codes_size, self.cfg.resolution
-        want = (c.in_channels, R, R) if half == 0 else (c.embed_dim, S, S)
+        S, R = self.cfg.codes_size, self.cfg.resolution
+        want = (self._Cin, R, R) if half == 0 else (self._E, S, S)
         _require_cuda(x, "images" if half == 0 else "z_q")
         if x.ndim != 4 or tuple(x.shape[1:]) != want:
             raise ValueError(f"expected [B, {want[0]}, {want[1]}, {want[2]}], got {tuple(x.shape)}")
@@ -183,13 +212,13 @@ class TrainableTokenizer:
         if self._tape[half] != tape or self._current_versions() != self._versions:
             raise RuntimeError("TrainableTokenizer: this backward does not belong to the last forward of its half (a later forward or a "
                                "weight change replaced the tape)")
-        c, S, R, B = self.cfg, self.cfg.codes_size, self.cfg.resolution, g.shape[0]
+        S, R, B = self.cfg.codes_size, self.cfg.resolution, g.shape[0]
         g = g.to(torch.float32).contiguous()
         if half == 0:
-            gi = torch.empty(B, c.in_channels, R, R, dtype=torch.float32, device=self.device) if want_input else None
+            gi = torch.empty(B, self._Cin, R, R, dtype=torch.float32, device=self.device) if want_input else None
             self._train.call("encode_backward", g.data_ptr(), B, gi.data_ptr() if want_input else None)
         else:
-            gi = torch.empty(B, S, S, c.embed_dim, dtype=torch.float32, device=self.device) if want_input else None
+            gi = torch.empty(B, S, S, self._E, dtype=torch.float32, device=self.device) if want_input else None
             self._train.call("decode_backward", g.data_ptr(), B, gi.data_ptr() if want_input else None)
             gi = gi.permute(0, 3, 1, 2) if want_input else None
         keys = [k for k in self._keys if _half_of(k) == half and self.state[k].requires_grad]
@@ -208,7 +237,7 @@ class TrainableTokenizer:
         if torch.is_grad_enabled() and (x.requires_grad or params):
             return fn.apply(self, x, *params)
         if self._eval is None:
-            self._eval = _TrainEngine(self.cfg, self._tensors(), self.max_batch, self.device)
+            self._eval = self._engine()
         return self._run(self._eval, half, self._prepare(half, x))
 
     def encode_prequant(self, images: torch.Tensor) -> torch.Tensor:
@@ -225,13 +254,13 @@ class TrainableTokenizer:
         """codes [B, S*S] -> z_q [B, E, S, S] (quantize.embedding, vqgan.py:94-99); no gradient: the codebook is frozen."""
         S = self.cfg.codes_size
         z = self.state["quantize.embedding.weight"].detach()[indices.to(self.device).reshape(-1, S * S)]
-        return z.view(-1, S, S, self.cfg.embed_dim).permute(0, 3, 1, 2).contiguous()
+        return z.view(-1, S, S, self._E).permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
     def quantize(self, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """z [B, E, S, S] -> (z_q [B, E, S, S], indices [B, S*S]): the engine's nearest-code search (first minimum of |z|^2 + |e|^2 - 2 z.e,
         quantize.py:277-285) on the rows of z; no gradient."""
-        S, E = self.cfg.codes_size, self.cfg.embed_dim
+        S, E = self.cfg.codes_size, self._E
         rows = z.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(-1, E).contiguous()
         emb = self.state["quantize.embedding.weight"].detach().contiguous()
         codes = torch.empty(rows.shape[0], dtype=torch.int64, device=self.device)
@@ -241,3 +270,16 @@ class TrainableTokenizer:
                                                         _lib.stream_ptr(self.device)))
         codes = codes.view(-1, S * S)
         return self.embed(codes), codes
+
+
+class MaskgitTrainableTokenizer(TrainableTokenizer):
+    """RAR's MaskGIT-VQGAN (``MaskgitVQConfig``): parameters under ``encoder.`` and ``decoder.`` only.  ``encode_prequant`` takes
+    [-1, 1] images to ``encoder((x + 1) / 2)`` [B, z_channels, S, S]; ``decode`` takes z_q to ``clamp(decoder(z_q), 0, 1) * 2 - 1``
+    (titok.py:91-123)."""
+
+    _create = "wmar_mvq_train_create"
+    _abi_config = staticmethod(_mvq_config)
+
+    @staticmethod
+    def _dims(cfg) -> Tuple[int, int, int]:
+        return cfg.z_channels, cfg.num_channels, cfg.num_channels
