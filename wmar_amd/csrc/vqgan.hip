@@ -18,12 +18,15 @@
 // (Downsample.forward) are folded into the patch gather; bias and the residual add are
 // folded into the epilogue.  GroupNorm(32, eps 1e-6)+swish is a statistics pass
 // (fp64 partial sums, fixed order) plus an elementwise pass.
+#include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "bx_split.h"
+#include "vq_plan.h"
 
 namespace wmar {
 
@@ -1003,7 +1006,7 @@ __global__ void k_nhwc_to_nchw_clamp(const float* __restrict__ src, float* __res
 
 using namespace wmar;
 
-// ------------------------------------------------------------------------------ engine
+// ------------------------------------------------------------------------------ weights and dispatch
 struct ConvW {
     float4* wp = nullptr;
     u32x4* wq = nullptr;     // bf16 pieces for k_conv_bx (input channels a multiple of 32)
@@ -1012,46 +1015,11 @@ struct ConvW {
     int cin = 0, cout = 0, cin_s = 0, cout_s = 0, ks = 1, CT = 0, KBc = 0;
 };
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
-struct ResW { NormW n1, n2; ConvW c1, c2, nin; bool has_nin = false; };
-struct AttnW { NormW n; ConvW q, k, v, proj; };
-
-struct wmar_vq {
-    wmar_vq_config cfg{};
-    DeviceArena mem;
-    int Bmax = 0, S = 0;
-    // decoder
-    ConvW post_quant, d_conv_in, d_conv_out;
-    ResW d_mid1, d_mid2; AttnW d_midattn;
-    std::vector<std::vector<ResW>> d_up;        // [level][block]
-    std::vector<std::vector<AttnW>> d_upattn;   // [level][block]
-    std::vector<ConvW> d_upsample;              // [level]
-    NormW d_norm_out;
-    // encoder
-    ConvW quant, e_conv_in, e_conv_out;
-    ResW e_mid1, e_mid2; AttnW e_midattn;
-    std::vector<std::vector<ResW>> e_down;
-    std::vector<std::vector<AttnW>> e_downattn;
-    std::vector<ConvW> e_downsample;
-    NormW e_norm_out;
-    // quantizer
-    float* emb = nullptr; float4* emb_p = nullptr; float* enorm = nullptr;
-    // workspaces
-    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t buf_elems = 0;
-    float *aq = nullptr, *ak = nullptr, *av = nullptr, *ao = nullptr, *asc = nullptr;
-    u32x4 *attk = nullptr, *attv = nullptr;   // per-image K and V^T as bf16-piece conv weights (MFMA attention)
-    float* zbias = nullptr;                    // zeros, max(tokens, channels) long
-    double* gn_partial = nullptr;
-    double* gn_tiles = nullptr; long long gn_tiles_cap = 0;   // per-tile GroupNorm partial sums written by conv epilogues
-    float* znorm = nullptr;
-    unsigned long long* vqbest = nullptr;      // packed (distance, code) winners of k_vq_argmin_split
-};
 
 namespace {
 
 constexpr int GN_CHUNKS_MAX = 64;
 constexpr int GN_MR_DOUBLES = 32768;   // head of the GroupNorm scratch: (mean, rstd) float2 per [image][32 groups], up to 1024 images
-inline int pad8(int c) { return (c + 7) & ~7; }
 
 // Loads convolutions and norms of a checkpoint into the owning engine's arena; shares the lookup's sticky `rc`.
 struct Loader : TensorMap {
@@ -1099,28 +1067,7 @@ struct Loader : TensorMap {
             set_error("norm copy failed"); rc = WMAR_EHIP;
         }
     }
-    void res(const std::string& p, int cin, int cout, ResW& r) {
-        norm(p + "norm1", cin, r.n1);
-        conv(p + "conv1", cin, cout, 3, r.c1);
-        norm(p + "norm2", cout, r.n2);
-        conv(p + "conv2", cout, cout, 3, r.c2);
-        r.has_nin = cin != cout;
-        if (r.has_nin) conv(p + "nin_shortcut", cin, cout, 1, r.nin);
-    }
-    void attn(const std::string& p, int c, AttnW& a) {
-        norm(p + "norm", c, a.n);
-        conv(p + "q", c, c, 1, a.q);
-        conv(p + "k", c, c, 1, a.k);
-        conv(p + "v", c, c, 1, a.v);
-        conv(p + "proj_out", c, c, 1, a.proj);
-    }
 };
-
-bool in_attn_res(const wmar_vq_config& c, int res) {
-    for (int i = 0; i < c.n_attn_res; ++i)
-        if (c.attn_resolutions[i] == res) return true;
-    return false;
-}
 
 // WMAR_CONV_NO_BX=1 (read once, any build): keep every convolution on the fp32-input MFMA.  The bf16-piece split turns an infinite
 // operand into NaN (inf - inf) where fp32 arithmetic gives +-inf (bx_split.h): a model with non-finite activations can opt out.
@@ -1277,33 +1224,7 @@ int run_gn(double* gn_partial, const NormW& n, const float* x, int B, int HW, in
     return launch_status("k_gn");
 }
 
-// x (buf X) -> result left in returned buffer index; uses the 4 rotating buffers
-struct Bufs {
-    float** buf;
-    int x = 0;          // index of the current activation
-    float* X() { return buf[x]; }
-    float* other(int k) { return buf[(x + k) & 3]; }
-    void advance(int k) { x = (x + k) & 3; }
-};
-
-int run_res(wmar_vq* v, const ResW& r, Bufs& bf, int B, int H, int W, hipStream_t st) {
-    int rc;
-    float *X = bf.X(), *A = bf.other(1), *T = bf.other(2), *C = bf.other(3);
-    GnRef gn{};
-    if ((rc = run_gn(v->gn_partial, r.n1, X, B, H * W, 1, st, &gn))) return rc;
-    if ((rc = run_conv(r.c1, X, T, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-    if ((rc = run_gn(v->gn_partial, r.n2, T, B, H * W, 1, st, &gn))) return rc;
-    const float* shortcut = X;
-    if (r.has_nin) {
-        if ((rc = run_conv(r.nin, X, C, nullptr, B, H, W, 1, 0, st))) return rc;
-        shortcut = C;
-    }
-    if ((rc = run_conv(r.c2, T, A, shortcut, B, H, W, 1, 0, st, &gn))) return rc;
-    bf.advance(1);
-    return WMAR_OK;
-}
-
-// softmax(q k^T C^-1/2) v for q, k, v [B][N = H W][C] -> o: the middle of an AttnBlock (model.py:176-189), shared by run_attn and
+// softmax(q k^T C^-1/2) v for q, k, v [B][N = H W][C] -> o: the middle of an AttnBlock (model.py:176-189), shared by vq_forward and
 // wmar_vq_probe_attn.  asc: [B][N][N] floats; attk / attv (nullable: the scalar kernels then): 3 B N C / 8 16-byte words each; zbias:
 // max(N, C) zeros.
 struct AttnScratch { float* asc; u32x4* attk; u32x4* attv; float* zbias; };
@@ -1341,21 +1262,6 @@ int attn_core(const AttnScratch& s, const float* q, const float* k, const float*
     return WMAR_OK;
 }
 
-int run_attn(wmar_vq* v, const AttnW& w, Bufs& bf, int B, int H, int W, hipStream_t st) {
-    int rc;
-    const int N = H * W, C = w.n.C;
-    float *X = bf.X(), *T = bf.other(2);
-    GnRef gn{};
-    if ((rc = run_gn(v->gn_partial, w.n, X, B, N, 0, st, &gn))) return rc;
-    if ((rc = run_conv(w.q, X, v->aq, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-    if ((rc = run_conv(w.k, X, v->ak, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-    if ((rc = run_conv(w.v, X, v->av, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-    if ((rc = attn_core(AttnScratch{v->asc, v->attk, v->attv, v->zbias}, v->aq, v->ak, v->av, v->ao, B, H, W, C, st))) return rc;
-    if ((rc = run_conv(w.proj, v->ao, T, X, B, H, W, 1, 0, st))) return rc;
-    bf.advance(2);
-    return WMAR_OK;
-}
-
 // the codebook as a 1x1 "conv" weight [n_embed][E] (same fragment packing) and its squared row norms
 int pack_codebook(const float* emb, float4* emb_p, float* enorm, int n_embed, int E, hipStream_t st) {
     const size_t n = (size_t)(n_embed / 32) * (E / 8) * 64;
@@ -1365,236 +1271,6 @@ int pack_codebook(const float* emb, float4* emb_p, float* enorm, int n_embed, in
 }
 
 }  // namespace
-
-extern "C" {
-
-int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const void* const* tensors_dev,
-                   int32_t n_tensors, void* stream, wmar_vq** out) {
-    WMAR_REQUIRE(cfg && names && tensors_dev && out, "vq_create: null argument");
-    WMAR_REQUIRE(cfg->n_levels >= 1 && cfg->n_levels <= 8, "vq_create: bad ch_mult length");
-    WMAR_REQUIRE(cfg->max_batch >= 1, "vq_create: max_batch");
-    WMAR_REQUIRE(cfg->embed_dim % 8 == 0 && cfg->n_embed % 32 == 0, "embed_dim %% 8 and n_embed %% 32 must be 0");
-    WMAR_REQUIRE(cfg->ch % 32 == 0, "ch must be a multiple of 32 (GroupNorm has 32 groups)");
-    const int L = cfg->n_levels;
-    const int S = cfg->resolution >> (L - 1);
-    WMAR_REQUIRE(S >= 8 && S % 8 == 0 && (S << (L - 1)) == cfg->resolution, "latent size %d must be a multiple of 8", S);
-    auto* v = new wmar_vq();
-    v->cfg = *cfg; v->Bmax = cfg->max_batch; v->S = S;
-    Loader ld(names, tensors_dev, n_tensors, &v->mem, (hipStream_t)stream);
-    const int ch = cfg->ch, z = cfg->z_channels, E = cfg->embed_dim;
-
-    // ---- decoder (model.py:437-505)
-    int block_in = ch * cfg->ch_mult[L - 1];
-    int res = S;
-    ld.conv("post_quant_conv", E, z, 1, v->post_quant);
-    ld.conv("decoder.conv_in", z, block_in, 3, v->d_conv_in);
-    ld.res("decoder.mid.block_1.", block_in, block_in, v->d_mid1);
-    ld.attn("decoder.mid.attn_1.", block_in, v->d_midattn);
-    ld.res("decoder.mid.block_2.", block_in, block_in, v->d_mid2);
-    v->d_up.resize(L); v->d_upattn.resize(L); v->d_upsample.resize(L);
-    for (int lvl = L - 1; lvl >= 0; --lvl) {
-        const int block_out = ch * cfg->ch_mult[lvl];
-        v->d_up[lvl].resize(cfg->num_res_blocks + 1);
-        for (int b = 0; b <= cfg->num_res_blocks; ++b) {
-            const std::string p = "decoder.up." + std::to_string(lvl) + ".";
-            ld.res(p + "block." + std::to_string(b) + ".", block_in, block_out, v->d_up[lvl][b]);
-            block_in = block_out;
-            if (in_attn_res(*cfg, res)) {
-                v->d_upattn[lvl].emplace_back();
-                ld.attn(p + "attn." + std::to_string(b) + ".", block_in, v->d_upattn[lvl].back());
-            }
-        }
-        if (lvl != 0) {
-            ld.conv("decoder.up." + std::to_string(lvl) + ".upsample.conv", block_in, block_in, 3, v->d_upsample[lvl]);
-            res *= 2;
-        }
-    }
-    ld.norm("decoder.norm_out", block_in, v->d_norm_out);
-    ld.conv("decoder.conv_out", block_in, cfg->out_ch, 3, v->d_conv_out);
-
-    // ---- encoder (model.py:343-404)
-    ld.conv("encoder.conv_in", cfg->in_channels, ch, 3, v->e_conv_in);
-    v->e_down.resize(L); v->e_downattn.resize(L); v->e_downsample.resize(L);
-    res = cfg->resolution;
-    block_in = ch;
-    for (int lvl = 0; lvl < L; ++lvl) {
-        block_in = ch * (lvl == 0 ? 1 : cfg->ch_mult[lvl - 1]);
-        const int block_out = ch * cfg->ch_mult[lvl];
-        v->e_down[lvl].resize(cfg->num_res_blocks);
-        for (int b = 0; b < cfg->num_res_blocks; ++b) {
-            const std::string p = "encoder.down." + std::to_string(lvl) + ".";
-            ld.res(p + "block." + std::to_string(b) + ".", block_in, block_out, v->e_down[lvl][b]);
-            block_in = block_out;
-            if (in_attn_res(*cfg, res)) {
-                v->e_downattn[lvl].emplace_back();
-                ld.attn(p + "attn." + std::to_string(b) + ".", block_in, v->e_downattn[lvl].back());
-            }
-        }
-        if (lvl != L - 1) {
-            ld.conv("encoder.down." + std::to_string(lvl) + ".downsample.conv", block_in, block_in, 3, v->e_downsample[lvl]);
-            res /= 2;
-        }
-    }
-    ld.res("encoder.mid.block_1.", block_in, block_in, v->e_mid1);
-    ld.attn("encoder.mid.attn_1.", block_in, v->e_midattn);
-    ld.res("encoder.mid.block_2.", block_in, block_in, v->e_mid2);
-    ld.norm("encoder.norm_out", block_in, v->e_norm_out);
-    ld.conv("encoder.conv_out", block_in, z, 3, v->e_conv_out);
-    ld.conv("quant_conv", z, E, 1, v->quant);
-
-    // ---- quantizer
-    const float* emb = ld.need("quantize.embedding.weight");
-    int& rc = ld.rc;
-    hipStream_t st = (hipStream_t)stream;
-    WMAR_TRY(v->mem.alloc(&v->emb, (size_t)cfg->n_embed * E));
-    if (rc == WMAR_OK && hipMemcpyAsync(v->emb, emb, (size_t)cfg->n_embed * E * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        set_error("embedding copy failed"); rc = WMAR_EHIP;
-    }
-    WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)cfg->n_embed * E / 4));
-    WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)cfg->n_embed));
-    if (rc == WMAR_OK) rc = pack_codebook(v->emb, v->emb_p, v->enorm, cfg->n_embed, E, st);
-    // ---- workspaces: the largest activation any layer produces
-    size_t maxel = 0;
-    {
-        int r = cfg->resolution;
-        for (int lvl = 0; lvl < L; ++lvl) {
-            int cmax = ch * cfg->ch_mult[lvl];
-            if (lvl > 0 && ch * cfg->ch_mult[lvl - 1] > cmax) cmax = ch * cfg->ch_mult[lvl - 1];
-            if (lvl + 1 < L && ch * cfg->ch_mult[lvl + 1] > cmax) cmax = ch * cfg->ch_mult[lvl + 1];
-            size_t el = (size_t)r * r * pad8(cmax);
-            if (el > maxel) maxel = el;
-            r /= 2;
-        }
-        size_t el0 = (size_t)cfg->resolution * cfg->resolution * pad8(cfg->in_channels > cfg->out_ch ? cfg->in_channels : cfg->out_ch);
-        if (el0 > maxel) maxel = el0;
-    }
-    v->buf_elems = maxel * v->Bmax;
-    for (int i = 0; i < 4; ++i) WMAR_TRY(v->mem.alloc(&v->buf[i], v->buf_elems));
-    const int cattn = ch * cfg->ch_mult[L - 1];
-    // attention scratch sized for the largest attention resolution
-    int amax = 0;
-    for (int i = 0; i < cfg->n_attn_res; ++i) amax = cfg->attn_resolutions[i] > amax ? cfg->attn_resolutions[i] : amax;
-    if (amax < S) amax = S;
-    const size_t ntok = (size_t)amax * amax;
-    int cam = 0;
-    for (int lvl = 0; lvl < L; ++lvl) cam = ch * cfg->ch_mult[lvl] > cam ? ch * cfg->ch_mult[lvl] : cam;
-    (void)cattn;
-    WMAR_TRY(v->mem.alloc(&v->aq, (size_t)v->Bmax * ntok * cam));
-    WMAR_TRY(v->mem.alloc(&v->ak, (size_t)v->Bmax * ntok * cam));
-    WMAR_TRY(v->mem.alloc(&v->av, (size_t)v->Bmax * ntok * cam));
-    WMAR_TRY(v->mem.alloc(&v->ao, (size_t)v->Bmax * ntok * cam));
-    WMAR_TRY(v->mem.alloc(&v->asc, (size_t)v->Bmax * ntok * ntok));
-    if (ntok % 32 == 0 && cam % 32 == 0) {
-        WMAR_TRY(v->mem.alloc(&v->attk, (size_t)v->Bmax * ntok * cam * 3 / 8));     // 3 pieces x 2 bytes per element, in 16-byte units
-        WMAR_TRY(v->mem.alloc(&v->attv, (size_t)v->Bmax * ntok * cam * 3 / 8));
-        const size_t nz = ntok > (size_t)cam ? ntok : (size_t)cam;
-        WMAR_TRY(v->mem.alloc_zero(&v->zbias, nz, st));
-    }
-    WMAR_TRY(v->mem.alloc(&v->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)v->Bmax * GN_CHUNKS_MAX * 32 * 2));
-    v->gn_tiles_cap = (long long)v->Bmax * (cfg->resolution / 8) * (cfg->resolution / 8) * 64;
-    WMAR_TRY(v->mem.alloc(&v->gn_tiles, (size_t)v->gn_tiles_cap));
-    WMAR_TRY(v->mem.alloc(&v->znorm, (size_t)v->Bmax * S * S));
-    WMAR_TRY(v->mem.alloc(&v->vqbest, (size_t)v->Bmax * S * S));
-    if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("vq_create: sync failed"); rc = WMAR_EHIP; }
-    if (rc != WMAR_OK) { delete v; return rc; }
-    *out = v;
-    return WMAR_OK;
-}
-
-void wmar_vq_destroy(wmar_vq* v) { delete v; }
-int64_t wmar_vq_device_bytes(const wmar_vq* v) { return v ? v->mem.bytes : 0; }
-
-int wmar_vq_decode(wmar_vq* v, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream) {
-    WMAR_REQUIRE(v && codes_dev && images_dev, "vq_decode: null argument");
-    WMAR_REQUIRE(B >= 1 && B <= v->Bmax, "vq_decode: batch %lld outside 1..%d", (long long)B, v->Bmax);
-    hipStream_t st = (hipStream_t)stream;
-    const wmar_vq_config& c = v->cfg;
-    const int L = c.n_levels, S = v->S, E = c.embed_dim;
-    int rc;
-    Bufs bf{v->buf};
-    g_trk = GnTrack{};
-    g_trk.part = v->gn_tiles; g_trk.cap = v->gn_tiles_cap;
-    // get_codebook_entry (quantize.py:316-331): z_q in NHWC is just the gathered rows
-    const long long npix = (long long)B * S * S;
-    hipLaunchKernelGGL(k_codebook_gather, dim3((unsigned)((npix * (E / 4) + 255) / 256)), dim3(256), 0, st,
-                       (const long long*)codes_dev, v->emb, bf.X(), npix, E, c.n_embed);
-    if ((rc = launch_status("k_codebook_gather"))) return rc;
-    if ((rc = run_conv(v->post_quant, bf.X(), bf.other(1), nullptr, (int)B, S, S, 1, 0, st))) return rc;
-    bf.advance(1);
-    if ((rc = run_conv(v->d_conv_in, bf.X(), bf.other(1), nullptr, (int)B, S, S, 1, 0, st))) return rc;
-    bf.advance(1);
-    int H = S;
-    if ((rc = run_res(v, v->d_mid1, bf, (int)B, H, H, st))) return rc;
-    if ((rc = run_attn(v, v->d_midattn, bf, (int)B, H, H, st))) return rc;
-    if ((rc = run_res(v, v->d_mid2, bf, (int)B, H, H, st))) return rc;
-    for (int lvl = L - 1; lvl >= 0; --lvl) {
-        for (int b = 0; b <= c.num_res_blocks; ++b) {
-            if ((rc = run_res(v, v->d_up[lvl][b], bf, (int)B, H, H, st))) return rc;
-            if (!v->d_upattn[lvl].empty())
-                if ((rc = run_attn(v, v->d_upattn[lvl][b], bf, (int)B, H, H, st))) return rc;
-        }
-        if (lvl != 0) {
-            if ((rc = run_conv(v->d_upsample[lvl], bf.X(), bf.other(1), nullptr, (int)B, H, H, 1, 1, st))) return rc;
-            bf.advance(1);
-            H *= 2;
-        }
-    }
-    GnRef gno{};
-    if ((rc = run_gn(v->gn_partial, v->d_norm_out, bf.X(), (int)B, H * H, 1, st, &gno))) return rc;
-    if ((rc = run_conv(v->d_conv_out, bf.X(), bf.other(2), nullptr, (int)B, H, H, 1, 0, st, &gno))) return rc;
-    const int HW = H * H;
-    hipLaunchKernelGGL(k_nhwc_to_nchw_clamp, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, bf.other(2), images_dev,
-                       c.out_ch, HW, v->d_conv_out.cout_s);
-    return launch_status("k_nhwc_to_nchw_clamp");
-}
-
-int wmar_vq_encode(wmar_vq* v, const float* images_dev, int64_t B, int64_t* codes_dev, float* prequant_dev,
-                   void* stream) {
-    WMAR_REQUIRE(v && images_dev && codes_dev, "vq_encode: null argument");
-    WMAR_REQUIRE(B >= 1 && B <= v->Bmax, "vq_encode: batch %lld outside 1..%d", (long long)B, v->Bmax);
-    hipStream_t st = (hipStream_t)stream;
-    const wmar_vq_config& c = v->cfg;
-    const int L = c.n_levels, S = v->S, E = c.embed_dim;
-    int rc;
-    Bufs bf{v->buf};
-    g_trk = GnTrack{};
-    g_trk.part = v->gn_tiles; g_trk.cap = v->gn_tiles_cap;
-    int H = c.resolution;
-    hipLaunchKernelGGL(k_nchw_to_nhwc, dim3((H * H + 255) / 256, (unsigned)B), dim3(256), 0, st, images_dev, bf.X(),
-                       c.in_channels, H * H, v->e_conv_in.cin_s);
-    if ((rc = launch_status("k_nchw_to_nhwc"))) return rc;
-    if ((rc = run_conv(v->e_conv_in, bf.X(), bf.other(1), nullptr, (int)B, H, H, 1, 0, st))) return rc;
-    bf.advance(1);
-    for (int lvl = 0; lvl < L; ++lvl) {
-        for (int b = 0; b < c.num_res_blocks; ++b) {
-            if ((rc = run_res(v, v->e_down[lvl][b], bf, (int)B, H, H, st))) return rc;
-            if (!v->e_downattn[lvl].empty())
-                if ((rc = run_attn(v, v->e_downattn[lvl][b], bf, (int)B, H, H, st))) return rc;
-        }
-        if (lvl != L - 1) {
-            if ((rc = run_conv(v->e_downsample[lvl], bf.X(), bf.other(1), nullptr, (int)B, H, H, 2, 0, st))) return rc;
-            bf.advance(1);
-            H /= 2;
-        }
-    }
-    if ((rc = run_res(v, v->e_mid1, bf, (int)B, H, H, st))) return rc;
-    if ((rc = run_attn(v, v->e_midattn, bf, (int)B, H, H, st))) return rc;
-    if ((rc = run_res(v, v->e_mid2, bf, (int)B, H, H, st))) return rc;
-    GnRef gne{};
-    if ((rc = run_gn(v->gn_partial, v->e_norm_out, bf.X(), (int)B, H * H, 1, st, &gne))) return rc;
-    if ((rc = run_conv(v->e_conv_out, bf.X(), bf.other(2), nullptr, (int)B, H, H, 1, 0, st, &gne))) return rc;
-    if ((rc = run_conv(v->quant, bf.other(2), bf.other(3), nullptr, (int)B, H, H, 1, 0, st))) return rc;
-    float* zq = bf.other(3);   // [B*S*S][E] (E is a multiple of 8: no channel padding)
-    const long long P = (long long)B * S * S;
-    if (prequant_dev) WMAR_HIP_CHECK(hipMemcpyAsync(prequant_dev, zq, (size_t)P * E * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_row_sqnorm, dim3((unsigned)P), dim3(64), 0, st, zq, v->znorm, E);
-    VqArgs a{};
-    a.z = zq; a.ep = v->emb_p; a.enorm = v->enorm; a.znorm = v->znorm; a.codes = (long long*)codes_dev; a.P = P;
-    a.E = E; a.n_embed = c.n_embed;
-    return run_vq_argmin(a, v->vqbest, st);
-}
-
-}  // extern "C"
 
 // ------------------------------------------------------------------------------ probes (tests, debugging)
 // One layer at a time through the engines' own loader and dispatch (Loader::conv, run_gn, run_conv, attn_core, pack_codebook,
@@ -1623,7 +1299,7 @@ int probe_conv_run(DeviceArena& mem, const float* w, const float* bias, int cout
     }
     GnRef gin{};
     const char* gn_in = "none";
-    if (gamma) {                // run_res: statistics first, the normalisation inside the conv's patch loader
+    if (gamma) {                // as in a ResnetBlock: statistics first, the normalisation inside the conv's patch loader
         double* part = nullptr;
         if ((rc = mem.alloc(&part, gn_doubles))) return rc;
         NormW n; n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta); n.C = c.cin_s;
@@ -1731,9 +1407,9 @@ int wmar_vq_probe_argmin(const float* z_dev, int64_t P, int32_t E, const float* 
 
 // ============================================================================ MaskGIT-VQGAN
 // RAR's tokenizer (deps/rar/modeling/modules/maskgit_vqgan.py, deps/rar/modeling/titok.py:41-89):
-// the same conv / GroupNorm / quantizer kernels with a different plan -- no attention, bias-free
+// the same conv / GroupNorm / quantizer kernels with a different plan (plan_mvq, vq_plan.h) -- no attention, bias-free
 // 3x3 convs inside the ResnetBlocks, the 1x1 shortcut applied to the block OUTPUT, average-pool
-// downsampling, images in [0, 1] on the tokenizer side and [-1, 1] on the wrapper side.
+// downsampling, images in [0, 1] on the tokenizer side and [-1, 1] on the wrapper side.  The kernels only this network launches:
 namespace wmar {
 
 // 2x2 average pool, NHWC (DownsamplingBlock.forward, maskgit_vqgan.py:118-119)
@@ -1780,222 +1456,223 @@ __global__ void k_nhwc_to_nchw_01(const float* __restrict__ src, float* __restri
 
 }  // namespace wmar
 
-struct wmar_mvq {
-    wmar_mvq_config cfg{};
-    DeviceArena mem;
-    int Bmax = 0, S = 0;
-    ConvW d_conv_in, d_conv_out, e_conv_in, e_conv_out;
-    std::vector<ResW> d_mid, e_mid;
-    std::vector<std::vector<ResW>> d_up, e_down;
-    std::vector<ConvW> d_upconv;
-    NormW d_norm_out, e_norm_out;
-    float* emb = nullptr; float4* emb_p = nullptr; float* enorm = nullptr;
-    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
+// ============================================================================ the engines
+// A plan (vq_plan.h) with its weights loaded and a place for every tensor: what the one forward executor walks.  The inference engines
+// put tensor i into the buffer of its slot; the training engine (vq_train.h) gives every tensor memory of its own and passes a tape.
+namespace {
+
+struct VqNet {
+    VqPlan plan;
+    std::vector<ConvW> cw;               // by plan.convs index
+    std::vector<NormW> nw;               // by plan.norms index
+    std::vector<float*> at;              // by plan.t index: where the tensor lives
+    AttnScratch att{};                   // asc: the softmax buffer the inference engines share between attentions
     double* gn_partial = nullptr;
     double* gn_tiles = nullptr; long long gn_tiles_cap = 0;   // per-tile GroupNorm partial sums written by conv epilogues
+};
+
+// what a training forward keeps besides the tensors
+struct VqTape {
+    std::vector<float2*> mr;             // by norm: its (mean, rstd), copied out of the shared table
+    std::vector<float*> P;               // by tensor, null except at the output tensor of a VQ_ATTN op (its o.out): the softmax behind it
+};
+
+// the weights of every conv and norm in op order (decoder half first, as the inference engines always loaded them)
+void net_load(VqNet& n, Loader& ld) {
+    const VqPlan& p = n.plan;
+    n.cw.resize(p.convs.size()); n.nw.resize(p.norms.size());
+    for (int hi = 1; hi >= 0; --hi)
+        for (const VqOp& o : p.half[hi].ops) {
+            if (o.kind == VQ_GN) ld.norm(p.norms[o.norm].name, p.norms[o.norm].C, n.nw[o.norm]);
+            if (o.kind == VQ_CONV) { const VqConvDesc& c = p.convs[o.conv]; ld.conv(c.name, c.cin, c.cout, c.ks, n.cw[o.conv], c.bias); }
+        }
+}
+
+// the scratch of a forward; allocated behind the activations, where the engines always had it
+void net_scratch(VqNet& n, DeviceArena& mem, int& rc, hipStream_t st) {
+    const VqPlan& p = n.plan;
+    const size_t B = (size_t)p.max_batch;
+    if (p.attn_nn) {                     // per-image K and V^T as bf16-piece conv weights (3 pieces x 2 bytes per element, in 16-byte units)
+        WMAR_TRY(mem.alloc(&n.att.attk, B * p.att_elems * 3 / 8));
+        WMAR_TRY(mem.alloc(&n.att.attv, B * p.att_elems * 3 / 8));
+        WMAR_TRY(mem.alloc_zero(&n.att.zbias, p.zbias_elems, st));
+    }
+    WMAR_TRY(mem.alloc(&n.gn_partial, (size_t)GN_MR_DOUBLES + B * GN_CHUNKS_MAX * 32 * 2));
+    n.gn_tiles_cap = (long long)B * (p.resolution / 8) * (p.resolution / 8) * 64;
+    WMAR_TRY(mem.alloc(&n.gn_tiles, (size_t)n.gn_tiles_cap));
+}
+
+// One half of the network on B images: the run_gn / run_conv / k_avgpool2 / attn_core calls of its op list, in order.  With a tape every
+// norm's (mean, rstd) is copied out and every attention keeps its softmax; the launches are the same either way.
+int vq_forward(VqNet& n, const VqHalf& h, int B, hipStream_t st, const VqTape* tape = nullptr) {
+    int rc;
+    const VqPlan& p = n.plan;
+    g_trk = GnTrack{};
+    g_trk.part = n.gn_tiles; g_trk.cap = n.gn_tiles_cap;
+    GnRef gn{};
+    for (const VqOp& o : h.ops) {
+        const VqTensor& x = p.t[o.in];
+        if (o.kind == VQ_GN) {
+            if ((rc = run_gn(n.gn_partial, n.nw[o.norm], n.at[o.in], B, x.H * x.H, o.swish, st, &gn))) return rc;
+            if (tape) WMAR_HIP_CHECK(hipMemcpyAsync(tape->mr[o.norm], gn.mr, (size_t)B * 32 * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        } else if (o.kind == VQ_CONV) {
+            if ((rc = run_conv(n.cw[o.conv], n.at[o.in], n.at[o.out], o.res >= 0 ? n.at[o.res] : nullptr, B, x.H, x.H, p.convs[o.conv].stride, o.up, st,
+                               o.norm >= 0 ? &gn : nullptr))) return rc;
+        } else if (o.kind == VQ_POOL) {
+            const VqTensor& y = p.t[o.out];
+            const long long total = (long long)y.H * y.H * (x.C / 4);
+            int gx = (int)((total + 255) / 256);
+            if (gx > 8192) gx = 8192;
+            hipLaunchKernelGGL(k_avgpool2, dim3(gx, (unsigned)B), dim3(256), 0, st, (const float*)n.at[o.in], n.at[o.out], y.H, y.H, x.C);
+            if (g_trk.src == n.at[o.out]) g_trk.src = nullptr;
+            if ((rc = launch_status("k_avgpool2"))) return rc;
+        } else {
+            const VqTensor& q = p.t[o.q];
+            if ((rc = attn_core(AttnScratch{tape ? tape->P[o.out] : n.att.asc, n.att.attk, n.att.attv, n.att.zbias}, n.at[o.q], n.at[o.k], n.at[o.v],
+                                n.at[o.out], B, q.H, q.H, q.C, st))) return rc;
+        }
+    }
+    g_trk = GnTrack{};
+    return WMAR_OK;
+}
+
+// An inference engine: the net in eight slot buffers (vq_plan.h) and the quantizer.
+struct VqEngine {
+    DeviceArena mem;
+    VqNet net;
+    int E = 0, n_embed = 0;                    // codebook [n_embed][E]
+    float* emb = nullptr; float4* emb_p = nullptr; float* enorm = nullptr;
     float* znorm = nullptr;
     unsigned long long* vqbest = nullptr;      // packed (distance, code) winners of k_vq_argmin_split
 };
 
+}  // namespace
+
+struct wmar_vq : VqEngine {};
+struct wmar_mvq : VqEngine {};
+
 namespace {
 
-void mres_load(Loader& ld, const std::string& p, int cin, int cout, ResW& r) {
-    ld.norm(p + "norm1", cin, r.n1);
-    ld.conv(p + "conv1", cin, cout, 3, r.c1, false);
-    ld.norm(p + "norm2", cout, r.n2);
-    ld.conv(p + "conv2", cout, cout, 3, r.c2, false);
-    r.has_nin = cin != cout;
-    if (r.has_nin) ld.conv(p + "nin_shortcut", cout, cout, 1, r.nin, false);
+template <class Handle>
+int engine_create(VqPlan plan, const char* who, int n_embed, const char* const* names, const void* const* tensors_dev, int32_t n_tensors,
+                  void* stream, Handle** out) {
+    WMAR_REQUIRE(names && tensors_dev && out, "%s: null argument", who);
+    WMAR_REQUIRE(plan.err.empty(), "%s", plan.err.c_str());
+    std::unique_ptr<Handle> v(new Handle());
+    VqNet& n = v->net;
+    n.plan = std::move(plan);
+    const VqPlan& p = n.plan;
+    hipStream_t st = (hipStream_t)stream;
+    Loader ld(names, tensors_dev, n_tensors, &v->mem, st);
+    int& rc = ld.rc;
+    net_load(n, ld);
+    // ---- quantizer
+    const int E = v->E = p.t[p.half[1].first].C;
+    v->n_embed = n_embed;
+    const float* emb = ld.need("quantize.embedding.weight");
+    WMAR_TRY(v->mem.alloc(&v->emb, (size_t)n_embed * E));
+    if (rc == WMAR_OK && hipMemcpyAsync(v->emb, emb, (size_t)n_embed * E * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        set_error("embedding copy failed"); rc = WMAR_EHIP;
+    }
+    WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)n_embed * E / 4));
+    WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)n_embed));
+    if (rc == WMAR_OK) rc = pack_codebook(v->emb, v->emb_p, v->enorm, n_embed, E, st);
+    // ---- one buffer per slot, as large as the largest tensor the plan puts there
+    const size_t B = (size_t)p.max_batch;
+    float* slot[VQ_SLOTS] = {};
+    for (int s = 0; s < VQ_SLOTS; ++s)
+        if (s < 4 || p.att_elems) WMAR_TRY(v->mem.alloc(&slot[s], B * (s < 4 ? p.rot_elems : p.att_elems)));
+    for (const VqTensor& t : p.t) n.at.push_back(slot[t.slot]);
+    if (p.attn_nn) WMAR_TRY(v->mem.alloc(&n.att.asc, B * p.attn_nn));
+    net_scratch(n, v->mem, rc, st);
+    WMAR_TRY(v->mem.alloc(&v->znorm, B * p.S * p.S));
+    WMAR_TRY(v->mem.alloc(&v->vqbest, B * p.S * p.S));
+    if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("%s: sync failed", who); rc = WMAR_EHIP; }
+    if (rc != WMAR_OK) return rc;
+    *out = v.release();
+    return WMAR_OK;
 }
 
-// ResnetBlock.forward (maskgit_vqgan.py:69-87): out = h + (cin != cout ? nin(h) : x),  h = conv2(...)
-int run_mres(wmar_mvq* v, const ResW& r, Bufs& bf, int B, int H, int W, hipStream_t st) {
+// codes int64 [B, S*S] -> images [B, C, R, R] (NCHW) in [-1, 1]
+int engine_decode(VqEngine* v, const char* who, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream) {
+    WMAR_REQUIRE(v && codes_dev && images_dev, "%s: null argument", who);
+    VqNet& n = v->net;
+    const VqPlan& p = n.plan;
+    WMAR_REQUIRE(B >= 1 && B <= p.max_batch, "%s: batch %lld outside 1..%d", who, (long long)B, p.max_batch);
+    hipStream_t st = (hipStream_t)stream;
+    const VqHalf& h = p.half[1];
     int rc;
-    float *X = bf.X(), *A = bf.other(1), *T = bf.other(2), *C = bf.other(3);
-    GnRef gn{};
-    if ((rc = run_gn(v->gn_partial, r.n1, X, B, H * W, 1, st, &gn))) return rc;
-    if ((rc = run_conv(r.c1, X, T, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-    if ((rc = run_gn(v->gn_partial, r.n2, T, B, H * W, 1, st, &gn))) return rc;
-    if (r.has_nin) {
-        if ((rc = run_conv(r.c2, T, A, nullptr, B, H, W, 1, 0, st, &gn))) return rc;
-        if ((rc = run_conv(r.nin, A, C, A, B, H, W, 1, 0, st))) return rc;      // nin(h) + h
-        bf.advance(3);
-    } else {
-        if ((rc = run_conv(r.c2, T, A, X, B, H, W, 1, 0, st, &gn))) return rc;   // h + x
-        bf.advance(1);
-    }
-    return WMAR_OK;
+    // get_codebook_entry (quantize.py:316-331): z_q in NHWC is just the gathered rows
+    const long long npix = (long long)B * p.S * p.S;
+    hipLaunchKernelGGL(k_codebook_gather, dim3((unsigned)((npix * (v->E / 4) + 255) / 256)), dim3(256), 0, st, (const long long*)codes_dev, v->emb,
+                       n.at[h.first], npix, v->E, v->n_embed);
+    if ((rc = launch_status("k_codebook_gather"))) return rc;
+    if ((rc = vq_forward(n, h, (int)B, st))) return rc;
+    const int HW = p.resolution * p.resolution;
+    hipLaunchKernelGGL(p.unit_range ? k_nhwc_to_nchw_01 : k_nhwc_to_nchw_clamp, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st,
+                       (const float*)n.at[h.last], images_dev, p.out_ch, HW, p.t[h.last].C);
+    return launch_status(p.unit_range ? "k_nhwc_to_nchw_01" : "k_nhwc_to_nchw_clamp");
+}
+
+// images [B, C, R, R] in [-1, 1] -> codes int64 [B, S*S]; prequant_dev (nullable): the [B*S*S, E] vectors handed to the quantizer
+int engine_encode(VqEngine* v, const char* who, const float* images_dev, int64_t B, int64_t* codes_dev, float* prequant_dev, void* stream) {
+    WMAR_REQUIRE(v && images_dev && codes_dev, "%s: null argument", who);
+    VqNet& n = v->net;
+    const VqPlan& p = n.plan;
+    WMAR_REQUIRE(B >= 1 && B <= p.max_batch, "%s: batch %lld outside 1..%d", who, (long long)B, p.max_batch);
+    hipStream_t st = (hipStream_t)stream;
+    const VqHalf& h = p.half[0];
+    int rc;
+    const int HW = p.resolution * p.resolution;
+    hipLaunchKernelGGL(p.unit_range ? k_nchw_to_nhwc01 : k_nchw_to_nhwc, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, images_dev,
+                       n.at[h.first], p.in_channels, HW, p.t[h.first].C);
+    if ((rc = launch_status(p.unit_range ? "k_nchw_to_nhwc01" : "k_nchw_to_nhwc"))) return rc;
+    if ((rc = vq_forward(n, h, (int)B, st))) return rc;
+    const float* zq = n.at[h.last];            // [B*S*S][E] (E is a multiple of 8: no channel padding)
+    const long long P = (long long)B * p.S * p.S;
+    if (prequant_dev) WMAR_HIP_CHECK(hipMemcpyAsync(prequant_dev, zq, (size_t)P * v->E * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_row_sqnorm, dim3((unsigned)P), dim3(64), 0, st, zq, v->znorm, v->E);
+    VqArgs a{};
+    a.z = zq; a.ep = v->emb_p; a.enorm = v->enorm; a.znorm = v->znorm; a.codes = (long long*)codes_dev; a.P = P;
+    a.E = v->E; a.n_embed = v->n_embed;
+    return run_vq_argmin(a, v->vqbest, st);
 }
 
 }  // namespace
 
 extern "C" {
 
-int wmar_mvq_create(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev,
-                    int32_t n_tensors, void* stream, wmar_mvq** out) {
-    WMAR_REQUIRE(cfg && names && tensors_dev && out, "mvq_create: null argument");
-    WMAR_REQUIRE(cfg->n_levels >= 1 && cfg->n_levels <= 8 && cfg->max_batch >= 1, "mvq_create: bad config");
+// TamingARMMWrapper.codes_to_images / images_to_codes (wmar/models/taming_wrapper.py:79-92)
+int wmar_vq_create(const wmar_vq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                   wmar_vq** out) {
+    WMAR_REQUIRE(cfg, "vq_create: null argument");
+    WMAR_REQUIRE(cfg->embed_dim % 8 == 0 && cfg->n_embed % 32 == 0, "embed_dim %% 8 and n_embed %% 32 must be 0");      // n_embed: the codebook packing
+    return engine_create(plan_taming(*cfg, "vq_create"), "vq_create", cfg->n_embed, names, tensors_dev, n_tensors, stream, out);
+}
+void wmar_vq_destroy(wmar_vq* v) { delete v; }
+int64_t wmar_vq_device_bytes(const wmar_vq* v) { return v ? v->mem.bytes : 0; }
+int wmar_vq_decode(wmar_vq* v, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream) {
+    return engine_decode(v, "vq_decode", codes_dev, B, images_dev, stream);
+}
+int wmar_vq_encode(wmar_vq* v, const float* images_dev, int64_t B, int64_t* codes_dev, float* prequant_dev, void* stream) {
+    return engine_encode(v, "vq_encode", images_dev, B, codes_dev, prequant_dev, stream);
+}
+
+// RAR's tokenizer (deps/rar/modeling/titok.py:41-89, rar_wrapper.py:113-124)
+int wmar_mvq_create(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                    wmar_mvq** out) {
+    WMAR_REQUIRE(cfg, "mvq_create: null argument");
     WMAR_REQUIRE(cfg->z_channels % 8 == 0 && cfg->num_embeddings % 32 == 0 && cfg->hidden_channels % 32 == 0,
                  "z_channels %% 8, num_embeddings %% 32 and hidden_channels %% 32 must be 0");
-    const int R = cfg->n_levels, hc = cfg->hidden_channels, z = cfg->z_channels;
-    const int S = cfg->resolution >> (R - 1);
-    WMAR_REQUIRE(S >= 8 && S % 8 == 0 && (S << (R - 1)) == cfg->resolution, "latent size %d must be a multiple of 8", S);
-    auto* v = new wmar_mvq();
-    v->cfg = *cfg; v->Bmax = cfg->max_batch; v->S = S;
-    Loader ld(names, tensors_dev, n_tensors, &v->mem, (hipStream_t)stream);
-    const int mid = hc * cfg->channel_mult[R - 1];
-    // decoder (maskgit_vqgan.py:197-245)
-    ld.conv("decoder.conv_in", z, mid, 3, v->d_conv_in);
-    v->d_mid.resize(cfg->num_res_blocks);
-    for (int b = 0; b < cfg->num_res_blocks; ++b) mres_load(ld, "decoder.mid." + std::to_string(b) + ".", mid, mid, v->d_mid[b]);
-    v->d_up.resize(R); v->d_upconv.resize(R);
-    for (int lvl = 0; lvl < R; ++lvl) {
-        int bi = lvl == R - 1 ? hc * cfg->channel_mult[R - 1] : hc * cfg->channel_mult[lvl + 1];
-        const int bo = hc * cfg->channel_mult[lvl];
-        v->d_up[lvl].resize(cfg->num_res_blocks);
-        for (int b = 0; b < cfg->num_res_blocks; ++b) {
-            mres_load(ld, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(b) + ".", bi, bo, v->d_up[lvl][b]);
-            bi = bo;
-        }
-        if (lvl != 0) ld.conv("decoder.up." + std::to_string(lvl) + ".upsample_conv", bo, bo, 3, v->d_upconv[lvl]);
-    }
-    ld.norm("decoder.norm_out", hc * cfg->channel_mult[0], v->d_norm_out);
-    ld.conv("decoder.conv_out", hc * cfg->channel_mult[0], cfg->num_channels, 3, v->d_conv_out);
-    // encoder (maskgit_vqgan.py:157-194)
-    ld.conv("encoder.conv_in", cfg->num_channels, hc, 3, v->e_conv_in, false);
-    v->e_down.resize(R);
-    for (int lvl = 0; lvl < R; ++lvl) {
-        int bi = hc * (lvl == 0 ? 1 : cfg->channel_mult[lvl - 1]);
-        const int bo = hc * cfg->channel_mult[lvl];
-        v->e_down[lvl].resize(cfg->num_res_blocks);
-        for (int b = 0; b < cfg->num_res_blocks; ++b) {
-            mres_load(ld, "encoder.down." + std::to_string(lvl) + ".block." + std::to_string(b) + ".", bi, bo, v->e_down[lvl][b]);
-            bi = bo;
-        }
-    }
-    v->e_mid.resize(cfg->num_res_blocks);
-    for (int b = 0; b < cfg->num_res_blocks; ++b) mres_load(ld, "encoder.mid." + std::to_string(b) + ".", mid, mid, v->e_mid[b]);
-    ld.norm("encoder.norm_out", mid, v->e_norm_out);
-    ld.conv("encoder.conv_out", mid, z, 1, v->e_conv_out);
-    const float* emb = ld.need("quantize.embedding.weight");
-    int& rc = ld.rc;
-    hipStream_t st = (hipStream_t)stream;
-    WMAR_TRY(v->mem.alloc(&v->emb, (size_t)cfg->num_embeddings * z));
-    if (rc == WMAR_OK && hipMemcpyAsync(v->emb, emb, (size_t)cfg->num_embeddings * z * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        set_error("embedding copy failed"); rc = WMAR_EHIP;
-    }
-    WMAR_TRY(v->mem.alloc(&v->emb_p, (size_t)cfg->num_embeddings * z / 4));
-    WMAR_TRY(v->mem.alloc(&v->enorm, (size_t)cfg->num_embeddings));
-    if (rc == WMAR_OK) rc = pack_codebook(v->emb, v->emb_p, v->enorm, cfg->num_embeddings, z, st);
-    size_t maxel = 0;
-    {
-        int r = cfg->resolution;
-        for (int lvl = 0; lvl < R; ++lvl) {
-            int cmax = hc * cfg->channel_mult[lvl];
-            if (lvl > 0 && hc * cfg->channel_mult[lvl - 1] > cmax) cmax = hc * cfg->channel_mult[lvl - 1];
-            if (lvl + 1 < R && hc * cfg->channel_mult[lvl + 1] > cmax) cmax = hc * cfg->channel_mult[lvl + 1];
-            if (z > cmax && lvl == R - 1) cmax = z;
-            size_t el = (size_t)r * r * pad8(cmax);
-            if (el > maxel) maxel = el;
-            r /= 2;
-        }
-    }
-    for (int i = 0; i < 4; ++i) WMAR_TRY(v->mem.alloc(&v->buf[i], maxel * v->Bmax));
-    WMAR_TRY(v->mem.alloc(&v->gn_partial, (size_t)GN_MR_DOUBLES + (size_t)v->Bmax * GN_CHUNKS_MAX * 32 * 2));
-    v->gn_tiles_cap = (long long)v->Bmax * (cfg->resolution / 8) * (cfg->resolution / 8) * 64;
-    WMAR_TRY(v->mem.alloc(&v->gn_tiles, (size_t)v->gn_tiles_cap));
-    WMAR_TRY(v->mem.alloc(&v->znorm, (size_t)v->Bmax * S * S));
-    WMAR_TRY(v->mem.alloc(&v->vqbest, (size_t)v->Bmax * S * S));
-    if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("mvq_create: sync failed"); rc = WMAR_EHIP; }
-    if (rc != WMAR_OK) { delete v; return rc; }
-    *out = v;
-    return WMAR_OK;
+    return engine_create(plan_mvq(*cfg, "mvq_create"), "mvq_create", cfg->num_embeddings, names, tensors_dev, n_tensors, stream, out);
 }
-
 void wmar_mvq_destroy(wmar_mvq* v) { delete v; }
 int64_t wmar_mvq_device_bytes(const wmar_mvq* v) { return v ? v->mem.bytes : 0; }
-
 int wmar_mvq_decode(wmar_mvq* v, const int64_t* codes_dev, int64_t B, float* images_dev, void* stream) {
-    WMAR_REQUIRE(v && codes_dev && images_dev, "mvq_decode: null argument");
-    WMAR_REQUIRE(B >= 1 && B <= v->Bmax, "mvq_decode: batch %lld outside 1..%d", (long long)B, v->Bmax);
-    hipStream_t st = (hipStream_t)stream;
-    const wmar_mvq_config& c = v->cfg;
-    const int R = c.n_levels, S = v->S, z = c.z_channels;
-    int rc;
-    Bufs bf{v->buf};
-    g_trk = GnTrack{};
-    g_trk.part = v->gn_tiles; g_trk.cap = v->gn_tiles_cap;
-    const long long npix = (long long)B * S * S;
-    hipLaunchKernelGGL(k_codebook_gather, dim3((unsigned)((npix * (z / 4) + 255) / 256)), dim3(256), 0, st,
-                       (const long long*)codes_dev, v->emb, bf.X(), npix, z, c.num_embeddings);
-    if ((rc = launch_status("k_codebook_gather"))) return rc;
-    if ((rc = run_conv(v->d_conv_in, bf.X(), bf.other(1), nullptr, (int)B, S, S, 1, 0, st))) return rc;
-    bf.advance(1);
-    int H = S;
-    for (auto& r : v->d_mid)
-        if ((rc = run_mres(v, r, bf, (int)B, H, H, st))) return rc;
-    for (int lvl = R - 1; lvl >= 0; --lvl) {
-        for (auto& r : v->d_up[lvl])
-            if ((rc = run_mres(v, r, bf, (int)B, H, H, st))) return rc;
-        if (lvl != 0) {
-            if ((rc = run_conv(v->d_upconv[lvl], bf.X(), bf.other(1), nullptr, (int)B, H, H, 1, 1, st))) return rc;
-            bf.advance(1);
-            H *= 2;
-        }
-    }
-    GnRef gno{};
-    if ((rc = run_gn(v->gn_partial, v->d_norm_out, bf.X(), (int)B, H * H, 1, st, &gno))) return rc;
-    if ((rc = run_conv(v->d_conv_out, bf.X(), bf.other(2), nullptr, (int)B, H, H, 1, 0, st, &gno))) return rc;
-    const int HW = H * H;
-    hipLaunchKernelGGL(k_nhwc_to_nchw_01, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, bf.other(2), images_dev,
-                       c.num_channels, HW, v->d_conv_out.cout_s);
-    return launch_status("k_nhwc_to_nchw_01");
+    return engine_decode(v, "mvq_decode", codes_dev, B, images_dev, stream);
 }
-
 int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* codes_dev, float* prequant_dev, void* stream) {
-    WMAR_REQUIRE(v && images_dev && codes_dev, "mvq_encode: null argument");
-    WMAR_REQUIRE(B >= 1 && B <= v->Bmax, "mvq_encode: batch %lld outside 1..%d", (long long)B, v->Bmax);
-    hipStream_t st = (hipStream_t)stream;
-    const wmar_mvq_config& c = v->cfg;
-    const int R = c.n_levels, S = v->S, z = c.z_channels;
-    int rc;
-    Bufs bf{v->buf};
-    g_trk = GnTrack{};
-    g_trk.part = v->gn_tiles; g_trk.cap = v->gn_tiles_cap;
-    int H = c.resolution;
-    hipLaunchKernelGGL(k_nchw_to_nhwc01, dim3((H * H + 255) / 256, (unsigned)B), dim3(256), 0, st, images_dev, bf.X(),
-                       c.num_channels, H * H, v->e_conv_in.cin_s);
-    if ((rc = launch_status("k_nchw_to_nhwc01"))) return rc;
-    if ((rc = run_conv(v->e_conv_in, bf.X(), bf.other(1), nullptr, (int)B, H, H, 1, 0, st))) return rc;
-    bf.advance(1);
-    for (int lvl = 0; lvl < R; ++lvl) {
-        for (auto& r : v->e_down[lvl])
-            if ((rc = run_mres(v, r, bf, (int)B, H, H, st))) return rc;
-        if (lvl != R - 1) {
-            const int C = c.hidden_channels * c.channel_mult[lvl];
-            const long long total = (long long)(H / 2) * (H / 2) * (C / 4);
-            int gx = (int)((total + 255) / 256);
-            if (gx > 8192) gx = 8192;
-            hipLaunchKernelGGL(k_avgpool2, dim3(gx, (unsigned)B), dim3(256), 0, st, bf.X(), bf.other(1), H / 2, H / 2, C);
-            if (g_trk.src == bf.other(1)) g_trk.src = nullptr;
-            if ((rc = launch_status("k_avgpool2"))) return rc;
-            bf.advance(1);
-            H /= 2;
-        }
-    }
-    for (auto& r : v->e_mid)
-        if ((rc = run_mres(v, r, bf, (int)B, H, H, st))) return rc;
-    GnRef gne{};
-    if ((rc = run_gn(v->gn_partial, v->e_norm_out, bf.X(), (int)B, H * H, 1, st, &gne))) return rc;
-    if ((rc = run_conv(v->e_conv_out, bf.X(), bf.other(2), nullptr, (int)B, H, H, 1, 0, st, &gne))) return rc;
-    float* zq = bf.other(2);
-    const long long P = (long long)B * S * S;
-    if (prequant_dev) WMAR_HIP_CHECK(hipMemcpyAsync(prequant_dev, zq, (size_t)P * z * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_row_sqnorm, dim3((unsigned)P), dim3(64), 0, st, zq, v->znorm, z);
-    VqArgs a{};
-    a.z = zq; a.ep = v->emb_p; a.enorm = v->enorm; a.znorm = v->znorm; a.codes = (long long*)codes_dev; a.P = P;
-    a.E = z; a.n_embed = c.num_embeddings;
-    return run_vq_argmin(a, v->vqbest, st);
+    return engine_encode(v, "mvq_encode", images_dev, B, codes_dev, prequant_dev, stream);
 }
 
 }  // extern "C"
