@@ -23,7 +23,8 @@ def index_image(H, W, dtype=torch.float32):
 
 
 def torch_index_map(H, W, quarters, rest):
-    """the index map of the torch restatement (Rotate.forward's CPU path): what the CPU tests use; the GPU tests take the kernel's"""
+    """the index map of the torch restatement (Rotate.forward's CPU path): what the CPU tests use; the GPU tests take the kernel's,
+    which tests/test_gpu_augment_forward.py holds to a float64 map pixel by pixel"""
     img = index_image(H, W, torch.float64)
     if quarters % 4:
         img = torch.rot90(img, quarters % 4, dims=(-2, -1))

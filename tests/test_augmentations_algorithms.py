@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.augment_forward_reference import aa_weights, check_rotation, undecidable_count
 from wmar_amd.augmentations.geometric import HorizontalFlip, Rotate, UpperLeftCropWithPadBack, UpperLeftCropWithResizeBack
 from wmar_amd.augmentations.valuemetric import Brightness, GaussianBlur
 
@@ -74,22 +75,13 @@ def test_rotate_equals_published_algorithm(dev, angle):
     x = _img(H=16, W=16, seed=3)
     got = Rotate()(x.to(dev), angle).cpu().numpy()
     ref = _rotate_ref(x.numpy(), angle)
-    # nearest sampling: identical pixels, except where a source coordinate sits within float rounding of a .5 boundary
-    assert (got != ref).mean() < 0.01, (angle, float((got != ref).mean()))
     assert got.shape == ref.shape
-
-
-def _aa_weights(n_in, n_out):
-    scale = n_in / n_out
-    support = max(scale, 1.0)
-    W = np.zeros((n_out, n_in))
-    for i in range(n_out):
-        center = scale * (i + 0.5)
-        lo = max(int(center - support + 0.5), 0)
-        hi = min(int(center + support + 0.5), n_in)
-        ws = [max(0.0, 1.0 - abs((j - center + 0.5) / max(scale, 1.0))) for j in range(lo, hi)]
-        W[i, lo:hi] = np.array(ws) / sum(ws)
-    return W
+    # nearest sampling: every pixel whose float64 source coordinate is not within float rounding of a .5 boundary equals the float64
+    # map, and 16 x 16 has no other pixel at these angles (tests/augment_forward_reference.py); the restated loop obeys the same rule
+    quarters, rest = divmod(angle, 90)
+    assert undecidable_count(16, 16, quarters % 4, rest) == 0
+    for out in (got, ref):
+        check_rotation(out, x.numpy(), 0.0, 16, 16, quarters % 4, rest)
 
 
 @pytest.mark.parametrize("dev", DEVICES)
@@ -99,7 +91,7 @@ def test_crop_resize_back_equals_published_algorithm(dev, factor):
     got = UpperLeftCropWithResizeBack()(x.to(dev), factor).cpu().numpy()
     n = int(factor * 20)
     crop = x.numpy().astype(np.float64)[:, :, :n, :n]
-    Wm = _aa_weights(n, 20)
+    Wm = aa_weights(n, 20)                      # the numpy restatement of the triangle filter (tests/augment_forward_reference.py)
     ref = np.einsum("oi,bcij,pj->bcop", Wm, crop, Wm)
     np.testing.assert_allclose(got, ref, rtol=0, atol=3e-6)
 

@@ -147,6 +147,7 @@ extern "C" int wmar_augment(int32_t op, const float* in_dev, float* out_dev, con
             const int k = (int)p0;
             WMAR_REQUIRE(k >= 1 && k <= AUG_MAX_K && (k & 1), "augment: blur kernel size %d (odd, 1..%d)", k, AUG_MAX_K);
             WMAR_REQUIRE(k / 2 < H && k / 2 < W, "augment: blur kernel %d does not fit a %d x %d image (reflect padding)", k, H, W);
+            WMAR_REQUIRE(B * C <= 65535, "augment: blur of %lld planes (the launch takes at most 65535)", (long long)(B * C));      // planes are gridDim.z
             // gaussian_blur's weights: x = -(k-1)/2 .. (k-1)/2, exp(-x^2 / 2 sigma^2), normalised (float, as torchvision computes them in the image dtype)
             const float sigma = 0.3f * ((float)(k - 1) * 0.5f - 1.f) + 0.8f;
             float sum = 0.f;
@@ -446,6 +447,7 @@ extern "C" int wmar_augment_backward(int32_t op, const float* in_dev, const floa
             const int k = (int)p0;
             WMAR_REQUIRE(k >= 1 && k <= AUG_MAX_K && (k & 1), "augment_backward: blur kernel size %d (odd, 1..%d)", k, AUG_MAX_K);
             WMAR_REQUIRE(k / 2 < H && k / 2 < W, "augment_backward: blur kernel %d does not fit a %d x %d image (reflect padding)", k, H, W);
+            WMAR_REQUIRE(B * C <= 65535, "augment_backward: blur of %lld planes (the launches take at most 65535)", (long long)(B * C));
             WMAR_REQUIRE(workspace_dev, "augment_backward: blur needs a workspace of B * C * H * W floats");
             WMAR_REQUIRE(workspace_dev != grad_in_dev && workspace_dev != grad_out_dev && workspace_dev != in_dev,
                          "augment_backward: the workspace overlaps another buffer");
