@@ -407,6 +407,39 @@ int wmar_cham_generate_image_hooked(wmar_cham* g, const int64_t* prompt_tokens_h
                                     float* logits_io_dev, int64_t* past_io_dev, int64_t past_stride, wmar_logits_hook hook,
                                     void* user, void* stream);
 
+/* Test-only stage access to a live engine (no engine path calls these; tests/test_gpu_cham_kernels.py holds every launch of a
+ * decode step to a float64 reference on its own).  A decode step is EMBED, then per block QKV .. RESID_FFN, then HEAD:
+ *   EMBED       k_cham_resid<true>     x = tok_embeddings[tok] (packed bf16), ssq = per-64-feature sums of squares of x (fp64)
+ *   QKV         k_bgemm<MT,SLAB>       big_slabs = stream-K pieces of (wqkv * attention_norm.weight) x        (fp32, no 1/rms yet)
+ *   ATTN        k_cham_attn<HD,NWA>    1/rms, qk LayerNorm, RoPE, K/V row appended at pos, softmax(q K^T) V -> y (packed bf16)
+ *   WO          k_bgemm<MT,SLAB>       slabs = pieces of wo y
+ *   RESID_ATTN  k_cham_resid<false>    x = bf16(x + bf16(sum of the pieces in piece order)), ssq of the new x
+ *   W13         k_bgemm<MT,SLAB>       big_slabs = pieces of (w13 * ffn_norm.weight) x, x1 / x3 interleaved 16 features at a time
+ *   SWIGLU      k_cham_swiglu          hbuf = bf16(bf16(silu(u1)) * u3), u = bf16(1/rms * sum of pieces)     (packed bf16)
+ *   W2          k_bgemm<MT,SLAB>       slabs = pieces of w2 hbuf
+ *   RESID_FFN   k_cham_resid<false>    as RESID_ATTN
+ *   HEAD        k_bgemm<MT,LOGITS>     logits = bf16(1/rms * (output.weight * norm.weight) x) as fp32 [M, vocab]
+ * wmar_cham_probe_run runs stages first_stage..last_stage of block `layer` with the engine's own plan and buffers and waits for
+ * the stream; tok_dev / pos_dev are copied in only when EMBED is among them, logits_dev is needed only for HEAD.
+ * wmar_cham_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine):
+ *   x, y [D/16][MT][64][8] bf16; hbuf [F/16][MT][64][8] bf16; slabs [16][D/16][MT][64][8] fp32;
+ *   big_slabs [16][max(D + 2 Dkv, 2 F)/16][MT][64][8] fp32 (a piece's stride is the producing GEMM's own width);
+ *   ssq [ceil(D/64)][32 MT] fp64; kcache, vcache [max_rows][Hkv][max_seq_len][head_dim] bf16 of block `layer`;
+ *   rope [max_seq_len][head_dim/2] (cos, sin) fp32; wqkv, wo, w13, w2 (block `layer`), whead: packed weights [N/32][K/16][64][8] bf16.
+ * It returns the buffer's size in bytes (also with ptr_dev null: a size query) or a negative status; `bytes` must equal that size.
+ * wmar_cham_probe_plan writes "MT=.. sk_qkv=C,U,G sk_o=.. sk_13=.. sk_2=.. sk_head=.. kernels=k_bgemm<MT,SLAB>;k_bgemm<MT,LOGITS>;
+ * k_cham_attn<HD,NWA>" for a step of M rows: the stream-K decomposition (chunks per group, units, workgroups) and the kernel
+ * instantiations the dispatch launches. */
+enum {
+    WMAR_CHAM_STAGE_EMBED = 0, WMAR_CHAM_STAGE_QKV, WMAR_CHAM_STAGE_ATTN, WMAR_CHAM_STAGE_WO, WMAR_CHAM_STAGE_RESID_ATTN,
+    WMAR_CHAM_STAGE_W13, WMAR_CHAM_STAGE_SWIGLU, WMAR_CHAM_STAGE_W2, WMAR_CHAM_STAGE_RESID_FFN, WMAR_CHAM_STAGE_HEAD
+};
+int wmar_cham_probe_run(wmar_cham* g, const int64_t* tok_dev, const int32_t* pos_dev, int64_t M, int32_t layer, int32_t first_stage,
+                        int32_t last_stage, float* logits_dev, void* stream);
+int64_t wmar_cham_probe_copy(wmar_cham* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine,
+                             void* stream);
+int wmar_cham_probe_plan(wmar_cham* g, int64_t M, char* buf, int64_t buf_len);
+
 /* The ImageDecoder logits pipeline of one step as ONE launch (chameleon.py:313-327, generation.py:84-93):
  * logits3_dev float [3B, V] = [full | image-conditioned | unconditioned] rows; guidance mix
  * (logits_processor.py:312-336) -> watermark bias (called positionally on the input rows,

@@ -80,36 +80,43 @@ class Cache:
         self.v: List[List[Optional[T]]] = [[None] * rows for _ in range(n_layers)]
 
 
+def attention_stage(sd: Dict[str, T], cfg, l: int, x: T, pos: T, cache: Cache, fold: bool = False) -> T:
+    """The attention of block `l` in front of wo (transformer.py:112-155 with q_seqlen = 1): x fp32 [M, D] holding bf16 values ->
+    the bf16 attention output [M, H * hd] (as fp32 values); appends K / V of position pos[m] to row m's cache."""
+    M = x.shape[0]
+    H, Hkv, hd = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+    p = f"layers.{l}."
+    qkv = _norm_linear(x, sd[p + "attention_norm.weight"], sd[p + "attention.wqkv.weight"], cfg.norm_eps, fold)
+    q = qkv[:, : H * hd].view(M, H, hd)
+    k, v = qkv[:, H * hd:].chunk(2, 1)
+    k, v = k.reshape(M, Hkv, hd), v.reshape(M, Hkv, hd)
+    if cfg.qk_normalization:
+        q = bf(F.layer_norm(q, (hd,), sd[p + "attention.q_normalization.weight"].float(),
+                            sd[p + "attention.q_normalization.bias"].float(), 1e-5))
+        k = bf(F.layer_norm(k, (hd,), sd[p + "attention.k_normalization.weight"].float(),
+                            sd[p + "attention.k_normalization.bias"].float(), 1e-5))
+    q, k = _rope(q, pos, cfg.rope_theta), _rope(k, pos, cfg.rope_theta)
+    out = torch.empty(M, H, hd)
+    for m in range(M):
+        P = int(pos[m])
+        kc, vc = cache.k[l][m], cache.v[l][m]
+        kc = k[m][None] if kc is None or P == 0 else torch.cat([kc[:P], k[m][None]])
+        vc = v[m][None] if vc is None or P == 0 else torch.cat([vc[:P], v[m][None]])
+        cache.k[l][m], cache.v[l][m] = kc, vc
+        kk = kc.repeat_interleave(H // Hkv, dim=1)           # [t, H, hd]
+        vv = vc.repeat_interleave(H // Hkv, dim=1)
+        s = torch.einsum("hd,thd->ht", q[m], kk) / hd ** 0.5
+        out[m] = torch.einsum("ht,thd->hd", torch.softmax(s, dim=-1), vv)
+    return bf(out).view(M, H * hd)
+
+
 def forward_tokens(sd: Dict[str, T], cfg, tok: T, pos: T, cache: Cache, fold: bool = False, want_logits: bool = True) -> Optional[T]:
     """One token per row (transformer.py:316-337 with q_seqlen = 1): tok int64 [M], pos int [M]; row m's cache must hold
     positions 0..pos[m]-1 (entries at >= pos[m] are overwritten, as rope_padded does).  Returns fp32 logits [M, V]."""
-    M = tok.shape[0]
-    H, Hkv, hd, D = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.dim
     x = sd["tok_embeddings.weight"][tok].float()
     for l in range(cfg.n_layers):
         p = f"layers.{l}."
-        qkv = _norm_linear(x, sd[p + "attention_norm.weight"], sd[p + "attention.wqkv.weight"], cfg.norm_eps, fold)
-        q = qkv[:, : H * hd].view(M, H, hd)
-        k, v = qkv[:, H * hd:].chunk(2, 1)
-        k, v = k.reshape(M, Hkv, hd), v.reshape(M, Hkv, hd)
-        if cfg.qk_normalization:
-            q = bf(F.layer_norm(q, (hd,), sd[p + "attention.q_normalization.weight"].float(),
-                                sd[p + "attention.q_normalization.bias"].float(), 1e-5))
-            k = bf(F.layer_norm(k, (hd,), sd[p + "attention.k_normalization.weight"].float(),
-                                sd[p + "attention.k_normalization.bias"].float(), 1e-5))
-        q, k = _rope(q, pos, cfg.rope_theta), _rope(k, pos, cfg.rope_theta)
-        out = torch.empty(M, H, hd)
-        for m in range(M):
-            P = int(pos[m])
-            kc, vc = cache.k[l][m], cache.v[l][m]
-            kc = k[m][None] if kc is None or P == 0 else torch.cat([kc[:P], k[m][None]])
-            vc = v[m][None] if vc is None or P == 0 else torch.cat([vc[:P], v[m][None]])
-            cache.k[l][m], cache.v[l][m] = kc, vc
-            kk = kc.repeat_interleave(H // Hkv, dim=1)           # [t, H, hd]
-            vv = vc.repeat_interleave(H // Hkv, dim=1)
-            s = torch.einsum("hd,thd->ht", q[m], kk) / hd ** 0.5
-            out[m] = torch.einsum("ht,thd->hd", torch.softmax(s, dim=-1), vv)
-        attn = _linear(bf(out).view(M, H * hd), sd[p + "attention.wo.weight"])
+        attn = _linear(attention_stage(sd, cfg, l, x, pos, cache, fold), sd[p + "attention.wo.weight"])
         h = bf(x + attn)
         x13 = _norm_linear(h, sd[p + "ffn_norm.weight"], sd[p + "feed_forward.w13.weight"], cfg.norm_eps, fold)
         x1, x3 = x13.chunk(2, -1)

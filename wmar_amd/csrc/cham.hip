@@ -144,44 +144,68 @@ struct ChamPlan {
         hipLaunchKernelGGL((k_cham_resid<false>), dim3((unsigned)(nch * MT)), dim3(256), 0, st, r);
         return launch_status("k_cham_resid");
     }
-    int layer(int l) {
-        const ChamLayer& w = g->layers[l];
-        int rc;
+    // the launches of one block, one member per stage (wmar_cham_probe_run runs them one at a time; layer() is their sequence)
+    long long qkv_stride() const { return (long long)(g->D + 2 * g->Dkv) * MT * 32; }
+    long long w13_stride() const { return (long long)2 * g->F * MT * 32; }
+    int qkv(int l) {
         const int Nqkv = g->D + 2 * g->Dkv;
         BGemmArgs q = base();
-        q.Wp = w.wqkv; q.Xp = g->x; q.KB = KBD; q.NT = Nqkv / 32; q.sk = sk_qkv; q.slabs = g->big_slabs;
-        q.slab_stride = (long long)Nqkv * MT * 32;
-        if ((rc = launch_bgemm<BEPI_SLAB>(q, MT, st))) return rc;
+        q.Wp = g->layers[l].wqkv; q.Xp = g->x; q.KB = KBD; q.NT = Nqkv / 32; q.sk = sk_qkv; q.slabs = g->big_slabs;
+        q.slab_stride = qkv_stride();
+        return launch_bgemm<BEPI_SLAB>(q, MT, st);
+    }
+    static int att_nw() {
+        static const int nw = getenv("WMAR_CHAM_NWA") ? atoi(getenv("WMAR_CHAM_NWA")) : 2;     // dev A/B: waves per (sequence, head)
+        return nw;
+    }
+    int attn(int l) {
+        const ChamLayer& w = g->layers[l];
         ChamAttnArgs t{};
         const long long lstride = (long long)g->Mmax * g->Hkv * g->T * g->hd;
-        t.qkv_slabs = g->big_slabs; t.slab_stride = q.slab_stride; t.sk = sk_qkv; t.ssq = g->ssq; t.n_chunks = nch; t.K = g->D;
+        t.qkv_slabs = g->big_slabs; t.slab_stride = qkv_stride(); t.sk = sk_qkv; t.ssq = g->ssq; t.n_chunks = nch; t.K = g->D;
         t.eps = g->cfg.norm_eps; t.qn_w = w.qnw; t.qn_b = w.qnb; t.kn_w = w.knw; t.kn_b = w.knb;
         t.kcache = g->kcache + l * lstride; t.vcache = g->vcache + l * lstride; t.y = g->y; t.pos = g->pos;
         t.D = g->D; t.H = g->H; t.Hkv = g->Hkv; t.Tmax = g->T; t.MT = MT; t.scale = 1.0f / sqrtf((float)g->hd);
         t.rope = g->rope;
         const dim3 grid((unsigned)(M * g->H));
-        static const int att_nw = getenv("WMAR_CHAM_NWA") ? atoi(getenv("WMAR_CHAM_NWA")) : 2;     // dev A/B: waves per (sequence, head)
-        if (g->hd == 128 && att_nw == 1) hipLaunchKernelGGL((k_cham_attn<128, 1>), grid, dim3(64), 0, st, t);
-        else if (g->hd == 128 && att_nw == 4) hipLaunchKernelGGL((k_cham_attn<128, 4>), grid, dim3(256), 0, st, t);
+        if (g->hd == 128 && att_nw() == 1) hipLaunchKernelGGL((k_cham_attn<128, 1>), grid, dim3(64), 0, st, t);
+        else if (g->hd == 128 && att_nw() == 4) hipLaunchKernelGGL((k_cham_attn<128, 4>), grid, dim3(256), 0, st, t);
         else if (g->hd == 128) hipLaunchKernelGGL((k_cham_attn<128, 2>), grid, dim3(128), 0, st, t);
         else hipLaunchKernelGGL((k_cham_attn<64, 2>), grid, dim3(128), 0, st, t);
-        if ((rc = launch_status("k_cham_attn"))) return rc;
+        return launch_status("k_cham_attn");
+    }
+    int wo(int l) {
         BGemmArgs o = base();
-        o.Wp = w.wo; o.Xp = g->y; o.KB = KBD; o.NT = g->D / 32; o.sk = sk_o; o.slabs = g->slabs; o.slab_stride = act8;
-        if ((rc = launch_bgemm<BEPI_SLAB>(o, MT, st))) return rc;
-        if ((rc = resid(sk_o))) return rc;
+        o.Wp = g->layers[l].wo; o.Xp = g->y; o.KB = KBD; o.NT = g->D / 32; o.sk = sk_o; o.slabs = g->slabs; o.slab_stride = act8;
+        return launch_bgemm<BEPI_SLAB>(o, MT, st);
+    }
+    int w13(int l) {
         BGemmArgs f = base();
-        f.Wp = w.w13; f.Xp = g->x; f.KB = KBD; f.NT = g->F / 16; f.sk = sk_13; f.slabs = g->big_slabs;
-        f.slab_stride = (long long)2 * g->F * MT * 32;
-        if ((rc = launch_bgemm<BEPI_SLAB>(f, MT, st))) return rc;
+        f.Wp = g->layers[l].w13; f.Xp = g->x; f.KB = KBD; f.NT = g->F / 16; f.sk = sk_13; f.slabs = g->big_slabs;
+        f.slab_stride = w13_stride();
+        return launch_bgemm<BEPI_SLAB>(f, MT, st);
+    }
+    int swiglu() {
         SwigluArgs sw{};
-        sw.slabs = g->big_slabs; sw.slab_stride = f.slab_stride; sw.sk = sk_13; sw.out = g->hbuf; sw.ssq = g->ssq; sw.n_chunks = nch;
+        sw.slabs = g->big_slabs; sw.slab_stride = w13_stride(); sw.sk = sk_13; sw.out = g->hbuf; sw.ssq = g->ssq; sw.n_chunks = nch;
         sw.K = g->D; sw.eps = g->cfg.norm_eps; sw.NT = g->F / 16; sw.MT = MT;
         hipLaunchKernelGGL(k_cham_swiglu, dim3((unsigned)((sw.NT + 3) / 4), (unsigned)MT), dim3(256), 0, st, sw);
-        if ((rc = launch_status("k_cham_swiglu"))) return rc;
+        return launch_status("k_cham_swiglu");
+    }
+    int w2(int l) {
         BGemmArgs d = base();
-        d.Wp = w.w2; d.Xp = g->hbuf; d.KB = KBF; d.NT = g->D / 32; d.sk = sk_2; d.slabs = g->slabs; d.slab_stride = act8;
-        if ((rc = launch_bgemm<BEPI_SLAB>(d, MT, st))) return rc;
+        d.Wp = g->layers[l].w2; d.Xp = g->hbuf; d.KB = KBF; d.NT = g->D / 32; d.sk = sk_2; d.slabs = g->slabs; d.slab_stride = act8;
+        return launch_bgemm<BEPI_SLAB>(d, MT, st);
+    }
+    int layer(int l) {
+        int rc;
+        if ((rc = qkv(l))) return rc;
+        if ((rc = attn(l))) return rc;
+        if ((rc = wo(l))) return rc;
+        if ((rc = resid(sk_o))) return rc;
+        if ((rc = w13(l))) return rc;
+        if ((rc = swiglu())) return rc;
+        if ((rc = w2(l))) return rc;
         return resid(sk_2);
     }
     int head(float* logits_out) {
@@ -314,6 +338,90 @@ int wmar_cham_forward_tokens(wmar_cham* g, const int64_t* tok_dev, const int32_t
     WMAR_HIP_CHECK(hipMemcpyAsync(g->pos, pos_dev, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
     ChamPlan p(g, (int)M, st);
     return p.step(logits_dev != nullptr, logits_dev);
+}
+
+// ---------------------------------------------------------------------------------------------- test-only stage access
+int wmar_cham_probe_run(wmar_cham* g, const int64_t* tok_dev, const int32_t* pos_dev, int64_t M, int32_t layer, int32_t first_stage,
+                        int32_t last_stage, float* logits_dev, void* stream) {
+    WMAR_REQUIRE(g, "cham_probe_run: null engine");
+    WMAR_REQUIRE(M >= 1 && M <= g->Mmax, "cham_probe_run: rows %lld outside 1..%d", (long long)M, g->Mmax);
+    WMAR_REQUIRE(layer >= 0 && layer < g->L, "cham_probe_run: layer %d outside 0..%d", layer, g->L - 1);
+    WMAR_REQUIRE(first_stage >= WMAR_CHAM_STAGE_EMBED && last_stage <= WMAR_CHAM_STAGE_HEAD && first_stage <= last_stage,
+                 "cham_probe_run: stages %d..%d", first_stage, last_stage);
+    WMAR_REQUIRE(last_stage < WMAR_CHAM_STAGE_HEAD || logits_dev, "cham_probe_run: the HEAD stage needs logits_dev");
+    hipStream_t st = (hipStream_t)stream;
+    if (first_stage == WMAR_CHAM_STAGE_EMBED) {
+        WMAR_REQUIRE(tok_dev && pos_dev, "cham_probe_run: the EMBED stage needs tok_dev and pos_dev");
+        WMAR_HIP_CHECK(hipMemcpyAsync(g->tok, tok_dev, (size_t)M * 8, hipMemcpyDeviceToDevice, st));
+        WMAR_HIP_CHECK(hipMemcpyAsync(g->pos, pos_dev, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+    }
+    ChamPlan p(g, (int)M, st);
+    int rc = WMAR_OK;
+    for (int s = first_stage; s <= last_stage && rc == WMAR_OK; ++s) {
+        switch (s) {
+            case WMAR_CHAM_STAGE_EMBED: rc = p.embed(); break;
+            case WMAR_CHAM_STAGE_QKV: rc = p.qkv(layer); break;
+            case WMAR_CHAM_STAGE_ATTN: rc = p.attn(layer); break;
+            case WMAR_CHAM_STAGE_WO: rc = p.wo(layer); break;
+            case WMAR_CHAM_STAGE_RESID_ATTN: rc = p.resid(p.sk_o); break;
+            case WMAR_CHAM_STAGE_W13: rc = p.w13(layer); break;
+            case WMAR_CHAM_STAGE_SWIGLU: rc = p.swiglu(); break;
+            case WMAR_CHAM_STAGE_W2: rc = p.w2(layer); break;
+            case WMAR_CHAM_STAGE_RESID_FFN: rc = p.resid(p.sk_2); break;
+            default: rc = p.head(logits_dev); break;
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc == WMAR_OK && e != hipSuccess) { set_error("cham_probe_run: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
+    return rc;
+}
+
+int64_t wmar_cham_probe_copy(wmar_cham* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine,
+                             void* stream) {
+    if (!g || !name) { set_error("cham_probe_copy: null argument"); return WMAR_EINVAL; }
+    if (layer < 0 || layer >= g->L) { set_error("cham_probe_copy: layer %d outside 0..%d", layer, g->L - 1); return WMAR_EINVAL; }
+    const std::string n = name;
+    const size_t Mpad = (size_t)g->MT * 32, D = g->D, F = g->F, Nqkv = (size_t)g->D + 2 * g->Dkv;
+    const size_t lkv = (size_t)g->Mmax * g->Hkv * g->T * g->hd;
+    const ChamLayer& w = g->layers[layer];
+    void* p = nullptr;
+    size_t sz = 0;
+    if (n == "x") { p = g->x; sz = Mpad * D * 2; }
+    else if (n == "y") { p = g->y; sz = Mpad * D * 2; }
+    else if (n == "hbuf") { p = g->hbuf; sz = Mpad * F * 2; }
+    else if (n == "slabs") { p = g->slabs; sz = (size_t)BG_MAXP * Mpad * D * 4; }
+    else if (n == "big_slabs") { p = g->big_slabs; sz = (size_t)BG_MAXP * Mpad * std::max(Nqkv, 2 * F) * 4; }
+    else if (n == "ssq") { p = g->ssq; sz = (size_t)((D / 16 + CHAM_STAT_KB - 1) / CHAM_STAT_KB) * Mpad * 8; }
+    else if (n == "kcache") { p = g->kcache + (size_t)layer * lkv; sz = lkv * 2; }
+    else if (n == "vcache") { p = g->vcache + (size_t)layer * lkv; sz = lkv * 2; }
+    else if (n == "rope") { p = g->rope; sz = (size_t)g->T * (g->hd / 2) * 8; }
+    else if (n == "wqkv") { p = w.wqkv; sz = Nqkv * D * 2; }
+    else if (n == "wo") { p = w.wo; sz = D * D * 2; }
+    else if (n == "w13") { p = w.w13; sz = 2 * F * D * 2; }
+    else if (n == "w2") { p = w.w2; sz = D * F * 2; }
+    else if (n == "whead") { p = g->whead; sz = (size_t)g->V * D * 2; }
+    else { set_error("cham_probe_copy: unknown buffer '%s'", name); return WMAR_EINVAL; }
+    if (!ptr_dev) return (int64_t)sz;
+    if (bytes != (int64_t)sz) { set_error("cham_probe_copy: '%s' holds %zu bytes, caller passed %lld", name, sz, (long long)bytes); return WMAR_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = to_engine ? hipMemcpyAsync(p, ptr_dev, sz, hipMemcpyDeviceToDevice, st)
+                             : hipMemcpyAsync(ptr_dev, p, sz, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("cham_probe_copy: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+    return (int64_t)sz;
+}
+
+int wmar_cham_probe_plan(wmar_cham* g, int64_t M, char* buf, int64_t buf_len) {
+    WMAR_REQUIRE(g && buf && buf_len > 0, "cham_probe_plan: null argument");
+    WMAR_REQUIRE(M >= 1 && M <= g->Mmax, "cham_probe_plan: rows %lld outside 1..%d", (long long)M, g->Mmax);
+    ChamPlan p(g, (int)M, nullptr);
+    const int nw = g->hd == 128 && (ChamPlan::att_nw() == 1 || ChamPlan::att_nw() == 4) ? ChamPlan::att_nw() : 2;
+    auto sk = [](const SkInfo& k) { return std::to_string(k.C) + "," + std::to_string(k.U) + "," + std::to_string(k.G); };
+    const std::string t = "MT=" + std::to_string(p.MT) + " sk_qkv=" + sk(p.sk_qkv) + " sk_o=" + sk(p.sk_o) + " sk_13=" + sk(p.sk_13) +
+                          " sk_2=" + sk(p.sk_2) + " sk_head=" + sk(p.sk_head) + " kernels=k_bgemm<" + std::to_string(p.MT) + ",SLAB>;k_bgemm<" +
+                          std::to_string(p.MT) + ",LOGITS>;k_cham_attn<" + std::to_string(g->hd) + "," + std::to_string(nw) + ">";
+    snprintf(buf, (size_t)buf_len, "%s", t.c_str());
+    return WMAR_OK;
 }
 
 static int cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_t* prompt_tokens_host,
