@@ -231,6 +231,58 @@ int wmar_gpt_plan_info(wmar_gpt* g, int64_t B, char* buf, int64_t buf_len);
 /* total_us[c], calls[c] for each class; *step_ms = average wall time of one decode step (any mode). */
 int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* step_ms);
 
+/* Test-only stage access to a live engine (no engine path calls these; tests/test_gpu_gpt_kernels.py holds the launches of a decode
+ * step to a float64 reference one at a time).  A decode step IS the sequence of stages below, one launch each; the engine walks it,
+ * the probe runs parts of it.  Matrix-core plan (13..128 rows, or any row count on an engine without the small-batch weights):
+ *   EMBED       k_resid_stats<embed>     x = tok_emb[tok] + pos_emb[pos] (packed fp32), stats = per-chunk (sum, sum of squares) in fp64
+ *   RESID_IN    k_resid_stats            layer > 0 and QKV does not fold (S_qx == 0): x += bfc2[l-1] + (FC2 slabs of layer l-1), stats
+ *   QKV         k_qkvx / k_qkvx_bx       (S_qx > 0) x' = x + bfc2[l-1] + slabs into the OTHER of x / x2 (layer 0: a copy), stats_q, and the
+ *                                        K slices of (Wqkv * ln1.weight) x' into qkv_slabs;  or k_gemm<EPI_PACKED> (S_qkv pieces of x)
+ *   ATTN        k_attn_decode<HD,NW>     LN1 algebra + bias on the summed pieces, K / V row appended at pos, softmax(q K^T) V -> y (and yq)
+ *   PROJ        k_gemm / k_bx / k_bx_xr  slabs = K slices of Wproj y; k_bx_xr also folds them: x += bproj + slabs, stats (16 chunks)
+ *   RESID_ATTN  k_resid_stats            x += bproj + slabs, stats                          (absent behind k_bx_xr)
+ *   FC1         k_fc1x / k_gemm<GELU>    hbuf = gelu(LN2 algebra on (Wfc1 * ln2.weight) x + bfc1)
+ *   FC2         k_gemm<EPI_PACKED>       slabs = S_fc2 K slices of Wfc2 hbuf (+ 1 for the first fc2_hi column tiles)
+ *   RESID_OUT   k_resid_stats            behind the last layer: x += bfc2[L-1] + slabs, stats
+ *   HEAD        k_gemm<EPI_LOGITS,LN>    logits = ln_f algebra on (Whead * ln_f.weight) x + bhead
+ * Small-batch plan (1..12 rows, n_embd 1536, head_dim 64): EMBED k_sembed, QKV / PROJ / FC1 / FC2 / HEAD k_sgemv<..>, ATTN k_sattn on
+ * the row-major xs / qs / ys / hs; PROJ and FC2 add the residual in place, so there is no RESID_* stage.
+ * wmar_gpt_probe_run sets the position, runs stages first_stage..last_stage of block `layer` (EMBED, RESID_OUT and HEAD ignore it) with
+ * the engine's own StepPlan, buffers and attention phase for (B, pos + 1 cached rows), and waits for the stream.  first_stage and
+ * last_stage must exist in the plan for B (WMAR_EINVAL otherwise); absent stages between them are passed over as the step does.
+ * The residual stream buffer a stage reads follows the step: with S_qx > 0 it is x in front of an even layer's QKV and x2 behind
+ * it (odd layers the other way round), RESID_OUT and HEAD read what block n_layer - 1 left; otherwise always x.  A raised in-launch
+ * barrier flag is reported as WMAR_EHIP (the stages run are invalid; the engine continues on the two-launch path, as after
+ * wmar_gpt_check).  The persistent small-batch step (WMAR_PERSIST=1) has no stages: WMAR_EINVAL.
+ * wmar_gpt_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine).
+ * Packed buffers are laid out for the MT of the step that wrote them (MT = 1 / 2 / 4 row tiles for B <= 32 / 64 / 128), sizes are
+ * for Mpad = 32 * MT(max_batch) rows:
+ *   x, x2, y [D/8][MT][64][4] fp32; hbuf [4D/8][MT][64][4]; yq [D/16][2][3][64][4] u32 (bf16 planes, 64-row engines only);
+ *   slabs [8] pieces of D columns, qkv_slabs [8] pieces of 3D columns (piece stride = D resp. 3D x 32 MT floats of the step's MT);
+ *   stats [64][Mpad][2] fp64, stats_q [32][Mpad][2] fp64 (chunk stride = 32 MT rows of the step's MT);
+ *   kcache, vcache [max_batch][H][block_size][head_dim] fp32 of block `layer`; xs, ys, qs [12][D], hs [12][4D] row-major fp32;
+ *   wqkv, wqkvx_bx, wproj, wproj_bx, wfc1, wfc1x16, wfc1x8, wfc2, bqkv, cqkv, bproj, bfc1, cfc1, bfc2 of block `layer`;
+ *   whead, bhead, chead.
+ * It returns the buffer's size in bytes (also with ptr_dev null: a size query) or a negative status (a buffer this engine does
+ * not have: WMAR_EINVAL); `bytes` must equal that size.
+ * wmar_gpt_probe_plan writes, for a step of B rows attending to kv_len cached rows,
+ *   "small=0 MT=.. S_qx=.. nkeep=.. S_qkv=.. S_proj=.. S_fc2=.. fc2_hi=.. nch=.. nch_ln2=.. pingpong=.. x_head=x|x2 attn_waves=..
+ *    rowmajor=.. proj=gemm|bx|bx_xr head=ntw2|N,PER fc1_tiles=.. head_tiles=.. xcd_ok=.. xr_eligible=.. barrier_fallbacks=..
+ *    stages=EMBED,QKV,.. kernels=<the text of wmar_gpt_plan_info>"
+ * (stages: those of block 1 when n_layer > 1, else block 0; head=N,PER: N launches of at most PER column tiles; fc1_tiles / head_tiles:
+ * row tiles per workgroup of the k_gemm that runs FC1 / the head, 0 where another kernel does; xcd_ok: the block -> XCD grouping and
+ * residency as measured at creation, a property of the device; xr_eligible: shape and switches admit k_bx_xr, so proj is bx_xr
+ * exactly when both are 1 and no barrier has fallen back). */
+enum {
+    WMAR_GPT_STAGE_EMBED = 0, WMAR_GPT_STAGE_RESID_IN, WMAR_GPT_STAGE_QKV, WMAR_GPT_STAGE_ATTN, WMAR_GPT_STAGE_PROJ,
+    WMAR_GPT_STAGE_RESID_ATTN, WMAR_GPT_STAGE_FC1, WMAR_GPT_STAGE_FC2, WMAR_GPT_STAGE_RESID_OUT, WMAR_GPT_STAGE_HEAD
+};
+int wmar_gpt_probe_run(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t pos, int32_t layer, int32_t first_stage,
+                       int32_t last_stage, float* logits_dev, void* stream);
+int64_t wmar_gpt_probe_copy(wmar_gpt* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine,
+                            void* stream);
+int wmar_gpt_probe_plan(wmar_gpt* g, int64_t B, int32_t kv_len, char* buf, int64_t buf_len);
+
 /* ------------------------------------------------------------------------ RAR
  * RAR generator (deps/rar/modeling/rar.py): adaLN blocks, per-head q/k LayerNorm, KV cache,
  * classifier-free guidance.  Tensors by the checkpoint's key names (cls_token, embeddings.weight,

@@ -17,7 +17,8 @@ SYMBOLS = [
     "wmar_last_error", "wmar_version", "wmar_key_row_words", "wmar_key_table_rows", "wmar_key_table_build",
     "wmar_key_greenlist", "wmar_wm_process_logits", "wmar_sample_fused", "wmar_detect", "wmar_detect_num_ngrams",
     "wmar_gpt_create", "wmar_gpt_destroy", "wmar_gpt_device_bytes", "wmar_gpt_decode_step", "wmar_gpt_generate",
-    "wmar_gpt_set_timing", "wmar_gpt_set_attention_phases", "wmar_gpt_get_timing", "wmar_gpt_profile_role", "wmar_gpt_plan_info", "wmar_gpt_check", "wmar_rar_create", "wmar_rar_destroy",
+    "wmar_gpt_set_timing", "wmar_gpt_set_attention_phases", "wmar_gpt_get_timing", "wmar_gpt_profile_role", "wmar_gpt_plan_info", "wmar_gpt_check",
+    "wmar_gpt_probe_run", "wmar_gpt_probe_copy", "wmar_gpt_probe_plan", "wmar_rar_create", "wmar_rar_destroy",
     "wmar_rar_device_bytes", "wmar_rar_forward_position", "wmar_rar_generate", "wmar_vq_create", "wmar_vq_destroy", "wmar_vq_device_bytes",
     "wmar_vq_decode", "wmar_vq_encode", "wmar_vq_probe_conv", "wmar_vq_probe_attn", "wmar_vq_probe_argmin", "wmar_vq_probe_conv_backward", "wmar_vq_probe_gn_backward", "wmar_vq_probe_attn_backward",
     "wmar_vq_probe_avgpool_backward", "wmar_mvq_probe_image_backward", "wmar_mvq_probe_input_backward", "wmar_mvq_train_create",
@@ -168,6 +169,10 @@ def load():
     L.wmar_gpt_get_timing.argtypes = [vp, C.POINTER(f64), C.POINTER(i64), C.POINTER(f64)]
     L.wmar_gpt_plan_info.argtypes = [vp, i64, C.c_char_p, i64]
     L.wmar_gpt_check.argtypes = [vp, vp]
+    L.wmar_gpt_probe_run.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, vp]
+    L.wmar_gpt_probe_copy.restype = i64
+    L.wmar_gpt_probe_copy.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
+    L.wmar_gpt_probe_plan.argtypes = [vp, i64, i32, C.c_char_p, i64]
     L.wmar_rar_create.argtypes = [C.POINTER(RarConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
     L.wmar_rar_destroy.argtypes = [vp]
     L.wmar_rar_destroy.restype = None

@@ -71,12 +71,14 @@ inline int pick_split(int tiles, int KB, int NW) {
 
 // Row tiles per workgroup: two 32-row tiles share every weight fragment (half the operand
 // traffic per MFMA); a single tile when the batch has only one.
+// four row tiles per workgroup once two would need more than one workgroup per CU: a second
+// workgroup on a CU shares its MFMA pipes, so the launch takes as long as the busiest CU
+inline int gemm_row_tiles(int MT, int NT) { return (MT % 4 == 0 && NT * (MT / 2) > 256) ? 4 : (MT % 2 == 0 ? 2 : 1); }
+
 template <int EPI, bool LN>
 int gemm_dispatch(GemmArgs a, bool allow_split, hipStream_t st) {
     constexpr int NW = 4;
-    // four row tiles per workgroup once two would need more than one workgroup per CU: a second
-    // workgroup on a CU shares its MFMA pipes, so the launch takes as long as the busiest CU
-    if (a.MT % 4 == 0 && a.NT * (a.MT / 2) > 256) {
+    if (gemm_row_tiles(a.MT, a.NT) == 4) {
         a.S = allow_split ? pick_split(a.NT * (a.MT / 4), a.KB, NW) : 1;
         return launch_gemm<4, NW, EPI, LN, 0, 2>(a, st);
     }

@@ -102,6 +102,7 @@ struct wmar_gpt {
     // fused output projection + residual fold + LN2 statistics (k_bx_xr): needs the block -> XCD grouping probed at creation
     unsigned* xsync = nullptr;     // [8][64] barrier words, [8*64 ..] = fail flags (placement, timeout)
     bool xcd_ok = false;           // blocks with equal blockIdx % 8 share an XCD, eight distinct XCDs (k_xcc_probe)
+    bool xcd_ok_created = false;   // ... as measured at creation (xcd_ok is cleared by a barrier fallback)
     bool no_xr = false;            // WMAR_NO_XR=1 at creation: keep the two-launch path
     int inject_fail = 0;           // WMAR_INJECT_SYNC_FAIL=1 at creation (tests): the next fused call finds the timeout flag raised
     int fallbacks = 0;             // calls re-run on the two-launch path after a failed in-launch barrier (wmar_gpt_plan_info reports it)
@@ -230,7 +231,7 @@ struct StepPlan {
         }
         proj_bx = MT == 2 && g->yq && g->layers[0].wproj_bx && !g->no_bx && !g->no_bx_proj && g->force_s[1] <= 0;
         if (proj_bx) S_proj = D / BX_KSLICE;
-        proj_xr = proj_bx && g->xcd_ok && !g->no_xr && S_proj == 4 && (D / 32) % 8 == 0 && (D / 32 / 8) * S_proj <= 32 && (D / 32 / 8) % 2 == 0;
+        proj_xr = xr_shape() && g->xcd_ok;
         nch_ln2 = proj_xr ? 16 : nch;
     }
     void dbg(const void* p, long long bytes) {
@@ -241,11 +242,17 @@ struct StepPlan {
         (void)p; (void)bytes;
 #endif
     }
+    // the shape and the switches admit the fused projection launch; whether it runs is then the device's (g->xcd_ok)
+    bool xr_shape() const { return proj_bx && !g->no_xr && S_proj == 4 && (D / 32) % 8 == 0 && (D / 32 / 8) * S_proj <= 32 && (D / 32 / 8) % 2 == 0; }
     // the predicates the launches below use (wmar_gpt_plan_info reports from the same ones)
     bool qkv_bx() const { return S_qx > 0 && MT == 2 && g->layers[0].wqkvx_bx && !g->no_bx && !g->no_bx_qkv; }
     bool fc1_x() const { return MT == 2 && g->layers[0].wfc1x16 && nch_ln2 <= 16; }      // (k_fc1x: each wave fetches four of at most 16 statistics chunks)
     int qx_nkeep() const { const int G = 3 * D / 128; return G >= 4 && S_qx * 4 <= STAT_CHUNKS_MAX ? 4 : 1; }   // keeper groups per K slice (k_qkvx_bx)
     static bool head_narrow() { static int v = -1; if (v < 0) v = getenv("WMAR_HEAD_NARROW") ? 1 : 0; return v != 0; }   // A/B: the two-launch 32-column head
+    // the head's launch form (head() launches from these, wmar_gpt_probe_plan reports them): two column tiles per workgroup in ONE
+    // launch at 64 rows, else launches of at most head_per() column tiles
+    bool head_ntw2() const { const int NT = g->V / 32; return MT == 2 && NT % 2 == 0 && NT / 2 <= 512 && !head_narrow(); }
+    int head_per() const { const int MG = (MT % 2 == 0) ? MT / 2 : MT; return 256 / MG > 0 ? 256 / MG : 1; }
     int split_for(int NT, int KB) const { return pick_split(MT % 2 == 0 ? NT * (MT / 2) : NT * MT, KB, 4); }
     GemmArgs base() const {
         GemmArgs a{};
@@ -483,7 +490,7 @@ struct StepPlan {
         h.bias = g->bhead; h.c1 = g->chead; h.logits = io.logits; h.V = g->V;
         g->span_begin(WMAR_T_HEAD, st);
         int rc = WMAR_OK;
-        if (MT == 2 && h.NT % 2 == 0 && h.NT / 2 <= 512 && !head_narrow()) {
+        if (head_ntw2()) {
             // 64 rows: TWO column tiles per workgroup (round 4) -- the launch was bound by the bytes a CU pulls (393 KB of activation
             // beside 196 KB of weights per 32-column workgroup, two workgroups per CU: 42 us for 100 MB of weights); every activation
             // fragment now feeds two weight fragments, one launch of V / 64 workgroups
@@ -492,8 +499,7 @@ struct StepPlan {
         } else {
         // at most one workgroup per CU per launch: two workgroups on a CU share its MFMA pipes and L1 fill path, so 512 column
         // tiles run faster as two launches of 256 than as one of 512 (measured 56 us -> see DESIGN.md section 6)
-        const int MG = (MT % 2 == 0) ? MT / 2 : MT;
-        const int per = 256 / MG > 0 ? 256 / MG : 1;
+        const int per = head_per();
         const int NTall = h.NT;
         for (int nt0 = 0; nt0 < NTall && rc == WMAR_OK; nt0 += per) {
             GemmArgs p = h;
@@ -508,12 +514,82 @@ struct StepPlan {
         g->span_end(st);
         return rc;
     }
+    // ---- the step as a sequence of stages, one launch each (WMAR_GPT_STAGE_*: enqueue_step walks it, wmar_gpt_probe_run runs parts of it)
+    //   matrix-core plan:  EMBED | per layer: [RESID_IN] QKV ATTN PROJ [RESID_ATTN] FC1 FC2 | RESID_OUT HEAD
+    //   small-batch plan:  EMBED | per layer: QKV ATTN PROJ FC1 FC2 | HEAD            (residuals added in place by PROJ and FC2)
+    // RESID_IN exists only where QKV does not fold layer l - 1's FC2 itself (S_qx == 0) and l > 0; RESID_ATTN is absent behind k_bx_xr.
+    bool has_stage(int s, int l) const {
+        switch (s) {
+            case WMAR_GPT_STAGE_RESID_IN: return !small && S_qx == 0 && l > 0;
+            case WMAR_GPT_STAGE_RESID_ATTN: return !small && !proj_xr;
+            case WMAR_GPT_STAGE_RESID_OUT: return !small;
+            default: return s >= WMAR_GPT_STAGE_EMBED && s <= WMAR_GPT_STAGE_HEAD;
+        }
+    }
+    // the residual stream buffer stage s of layer l reads: the fused fold in QKV (S_qx > 0) writes the other of x / x2, so the current
+    // one is x in front of an even layer's QKV and x2 behind it; RESID_OUT and HEAD read what the last layer left
+    float4* xcur_at(int s, int l) const {
+        if (small || S_qx == 0 || s == WMAR_GPT_STAGE_EMBED) return g->x;
+        if (s >= WMAR_GPT_STAGE_RESID_OUT) l = g->L - 1;
+        return ((l + (s > WMAR_GPT_STAGE_QKV ? 1 : 0)) & 1) ? g->x2 : g->x;
+    }
+    int run_stage(int s, int l) {
+        switch (s) {
+            case WMAR_GPT_STAGE_EMBED: return embed();
+            case WMAR_GPT_STAGE_RESID_IN: return resid(g->layers[l - 1].bfc2, S_fc2, fc2_hi);
+            case WMAR_GPT_STAGE_QKV:
+                if (small) return qkv_small(l);
+                return S_qx > 0 ? qkvx(l, l > 0 ? g->layers[l - 1].bfc2 : nullptr) : qkv(l);
+            case WMAR_GPT_STAGE_ATTN: return attn(l);
+            case WMAR_GPT_STAGE_PROJ: return proj(l);
+            case WMAR_GPT_STAGE_RESID_ATTN: return resid(g->layers[l].bproj, S_proj);      // (k_bx_xr has folded and summed already)
+            case WMAR_GPT_STAGE_FC1: return fc1(l);
+            case WMAR_GPT_STAGE_FC2: return fc2(l);
+            case WMAR_GPT_STAGE_RESID_OUT: return resid(g->layers[g->L - 1].bfc2, S_fc2, fc2_hi);
+            case WMAR_GPT_STAGE_HEAD: return head();
+            default: set_error("gpt: unknown stage %d", s); return WMAR_EINVAL;
+        }
+    }
+    // dev only: the checksums behind stage s (slots 0, 1 behind EMBED, then 11 per layer, 2 behind RESID_OUT)
+    void dbg_stage(int s, int l) {
+        if (small) return;
+        const long long actb = act * 16, Mpad = MT * 32;
+        const long long lstride = (long long)g->Bmax * g->H * g->Tmax * g->hd;
+        switch (s) {
+            case WMAR_GPT_STAGE_EMBED: dbg(xcur, actb); dbg(g->stats, nch * Mpad * 16); break;
+            case WMAR_GPT_STAGE_QKV:                                                                              // +0 x', +1 stats, +2 QKV pieces
+                if (S_qx > 0) { dbg(xcur, actb); dbg(g->stats_q, S_qx * Mpad * 16); dbg(g->qkv_slabs, S_qx * 3 * actb); }
+                else { dbg(xcur, actb); dbg(g->stats, nch * Mpad * 16); dbg(g->qkv_slabs, 3 * actb); }
+                break;
+            case WMAR_GPT_STAGE_ATTN:
+                if (proj_bx) dbg(g->yq, (long long)D / 16 * 2 * 3 * 64 * 16); else dbg(g->y, actb);               // +3 attention output
+                dbg(g->kcache + l * lstride, lstride * 4); dbg(g->vcache + l * lstride, lstride * 4);             // +4, +5 caches
+                break;
+            case WMAR_GPT_STAGE_PROJ:
+                dbg(g->slabs, S_proj * actb);                                                                     // +6 proj slabs
+                if (proj_xr) { dbg(xcur, actb); dbg(g->stats, nch_ln2 * Mpad * 16); }                             // +7, +8
+                break;
+            case WMAR_GPT_STAGE_RESID_ATTN: dbg(xcur, actb); dbg(g->stats, nch_ln2 * Mpad * 16); break;           // +7, +8
+            case WMAR_GPT_STAGE_FC1: dbg(g->hbuf, 4 * actb); break;                                               // +9 hidden
+            case WMAR_GPT_STAGE_FC2: dbg(g->slabs, S_fc2 * actb); break;                                          // +10 FC2 slabs (uniform part)
+            case WMAR_GPT_STAGE_RESID_OUT: dbg(xcur, actb); dbg(g->stats, nch * Mpad * 16); break;
+            default: break;
+        }
+    }
+    // stages first..last of layer l in order; a stage this plan does not have is passed over
+    int run_stages(int first, int last, int l) {
+        for (int s = first; s <= last; ++s) {
+            if (!has_stage(s, l)) continue;
+            if (int rc = run_stage(s, l)) return rc;
+            dbg_stage(s, l);
+        }
+        return WMAR_OK;
+    }
 };
 
 int enqueue_step(wmar_gpt* g, int64_t B, const StepIO& io, hipStream_t st) {
     StepPlan p(g, B, io, st);
     int rc;
-    const long long actb = p.act * 16, Mpad = p.MT * 32;
 #ifdef WMAR_DEV_KNOBS
     if (g->dbg_sums) { g->dbg_slot = 0; if (hipMemsetAsync(g->dbg_sums, 0, 4096 * 8, st) != hipSuccess) return WMAR_EHIP; }
 #endif
@@ -530,46 +606,11 @@ int enqueue_step(wmar_gpt* g, int64_t B, const StepIO& io, hipStream_t st) {
         g->ps_enqueued = true;
         return rc;
     }
-    if ((rc = p.embed())) return rc;
-    if (p.small) {
-        // 1..12 rows: five streaming launches per layer, the residual stream updated in place (decode_small.h)
-        for (int l = 0; l < g->L; ++l) {
-            if ((rc = p.qkv_small(l))) return rc;
-            if ((rc = p.attn(l))) return rc;
-            if ((rc = p.proj(l))) return rc;
-            if ((rc = p.fc1(l))) return rc;
-            if ((rc = p.fc2(l))) return rc;
-        }
-        return p.head();
-    }
-    p.dbg(p.xcur, actb); p.dbg(g->stats, p.nch * Mpad * 16);                                   // slots 0, 1
-    for (int l = 0; l < g->L; ++l) {                                                            // then 11 per layer:
-        if (p.S_qx > 0) {
-            if ((rc = p.qkvx(l, l > 0 ? g->layers[l - 1].bfc2 : nullptr))) return rc;
-            p.dbg(p.xcur, actb); p.dbg(g->stats_q, p.S_qx * Mpad * 16); p.dbg(g->qkv_slabs, p.S_qx * 3 * actb);   // +0 x', +1 stats, +2 QKV pieces
-        } else {
-            if (l > 0 && (rc = p.resid(g->layers[l - 1].bfc2, p.S_fc2, p.fc2_hi))) return rc;
-            if ((rc = p.qkv(l))) return rc;
-            p.dbg(p.xcur, actb); p.dbg(g->stats, p.nch * Mpad * 16); p.dbg(g->qkv_slabs, 3 * actb);
-        }
-        if ((rc = p.attn(l))) return rc;
-        if (p.proj_bx) p.dbg(g->yq, (long long)p.D / 16 * 2 * 3 * 64 * 16); else p.dbg(g->y, actb);              // +3 attention output
-        {
-            const long long lstride = (long long)g->Bmax * g->H * g->Tmax * g->hd;
-            p.dbg(g->kcache + l * lstride, lstride * 4); p.dbg(g->vcache + l * lstride, lstride * 4);            // +4, +5 caches
-        }
-        if ((rc = p.proj(l))) return rc;
-        p.dbg(g->slabs, p.S_proj * actb);                                                                        // +6 proj slabs
-        if (!p.proj_xr && (rc = p.resid(g->layers[l].bproj, p.S_proj))) return rc;             // k_bx_xr has folded and summed already
-        p.dbg(p.xcur, actb); p.dbg(g->stats, p.nch_ln2 * Mpad * 16);                                             // +7, +8
-        if ((rc = p.fc1(l))) return rc;
-        p.dbg(g->hbuf, 4 * actb);                                                                                // +9 hidden
-        if ((rc = p.fc2(l))) return rc;
-        p.dbg(g->slabs, p.S_fc2 * actb);                                                                         // +10 FC2 slabs (uniform part)
-    }
-    if ((rc = p.resid(g->layers[g->L - 1].bfc2, p.S_fc2, p.fc2_hi))) return rc;
-    p.dbg(p.xcur, actb); p.dbg(g->stats, p.nch * Mpad * 16);
-    return p.head();
+    // the plan's stage sequence (has_stage): EMBED, per layer RESID_IN .. FC2, then RESID_OUT, HEAD
+    if ((rc = p.run_stages(WMAR_GPT_STAGE_EMBED, WMAR_GPT_STAGE_EMBED, 0))) return rc;
+    for (int l = 0; l < g->L; ++l)
+        if ((rc = p.run_stages(WMAR_GPT_STAGE_RESID_IN, WMAR_GPT_STAGE_FC2, l))) return rc;
+    return p.run_stages(WMAR_GPT_STAGE_RESID_OUT, WMAR_GPT_STAGE_HEAD, g->L - 1);
 }
 
 }  // namespace
@@ -770,6 +811,7 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
         const long long blocks = (long long)(D / 32) * 4;
         g->xcd_ok = xcd_grouping_ok(192, 256, st) &&
                     (xr4 ? grid_resident(k_bx_xr<BX_PER, 4>, 256, blocks) : grid_resident(k_bx_xr<BX_PER / 2, 4, 8>, 512, blocks));
+        g->xcd_ok_created = g->xcd_ok;
         { const char* e = getenv("WMAR_INJECT_SYNC_FAIL"); g->inject_fail = (e && atoi(e) > 0) ? 1 : 0; }
     }
     if (rc != WMAR_OK) { delete g; return rc; }
@@ -945,6 +987,138 @@ int wmar_gpt_plan_info(wmar_gpt* g, int64_t B, char* buf, int64_t buf_len) {
     const int n = snprintf(buf, (size_t)buf_len, "qkv=%s;attn=%s;proj=%s;resid=k_resid_stats;resid_launches_per_step=%d;fc1=%s;fc2=%s;head=k_gemm<EPI_LOGITS,LN> (fp32 MFMA);barrier_fallbacks=%d",
                            qkv, attn, proj, p.proj_xr ? 1 : g->L + 1, fc1, fc2, g->fallbacks);
     WMAR_REQUIRE(n > 0 && n < buf_len, "plan_info: buffer of %lld bytes too small", (long long)buf_len);
+    return WMAR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- test-only stage access
+static const char* const kGptStageNames[] = {"EMBED", "RESID_IN", "QKV", "ATTN", "PROJ", "RESID_ATTN", "FC1", "FC2", "RESID_OUT", "HEAD"};
+
+int wmar_gpt_probe_run(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t pos, int32_t layer, int32_t first_stage,
+                       int32_t last_stage, float* logits_dev, void* stream) {
+    WMAR_REQUIRE(g, "gpt_probe_run: null engine");
+    WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "gpt_probe_run: batch %lld outside 1..%d", (long long)B, g->Bmax);
+    WMAR_REQUIRE(pos >= 0 && pos < g->Tmax, "gpt_probe_run: position %d outside the block size %d", pos, g->Tmax);
+    WMAR_REQUIRE(layer >= 0 && layer < g->L, "gpt_probe_run: layer %d outside 0..%d", layer, g->L - 1);
+    WMAR_REQUIRE(first_stage >= WMAR_GPT_STAGE_EMBED && last_stage <= WMAR_GPT_STAGE_HEAD && first_stage <= last_stage,
+                 "gpt_probe_run: stages %d..%d", first_stage, last_stage);
+    WMAR_REQUIRE(last_stage < WMAR_GPT_STAGE_HEAD || logits_dev, "gpt_probe_run: the HEAD stage needs logits_dev");
+    WMAR_REQUIRE(first_stage > WMAR_GPT_STAGE_EMBED || tok_dev, "gpt_probe_run: the EMBED stage needs tok_dev");
+    hipStream_t st = (hipStream_t)stream;
+    StepIO io{(const long long*)tok_dev, 1, 0, logits_dev};
+    g->att_nw = wmar_gpt::phase_waves(g->att_phase(pos + 1, B));
+    StepPlan p(g, B, io, st);
+    WMAR_REQUIRE(!p.persist, "gpt_probe_run: the persistent small-batch step (k_sstep) is one launch and has no stages");
+    WMAR_REQUIRE(p.has_stage(first_stage, layer) && p.has_stage(last_stage, layer), "gpt_probe_run: the plan for %lld rows has no stage %s in block %d",
+                 (long long)B, kGptStageNames[p.has_stage(first_stage, layer) ? last_stage : first_stage], layer);
+    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, g->pos_dev, (int)pos);
+    int rc = launch_status("k_set_int");
+    for (int s = first_stage; s <= last_stage && rc == WMAR_OK; ++s) {
+        if (!p.has_stage(s, layer)) continue;
+        p.xcur = p.xcur_at(s, layer);
+        rc = p.run_stage(s, layer);
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc == WMAR_OK && e != hipSuccess) { set_error("gpt_probe_run: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
+    if (rc != WMAR_OK) return rc;
+    const int f = gpt_sync_failed(g, st);
+    if (f < 0) return f;
+    if (f > 0) {
+        set_error("gpt_probe_run: the XCD-local barrier of the fused projection launch gave up or found a block on a foreign XCD: the stages "
+                  "just run are invalid (the engine continues on the two-launch path)");
+        return WMAR_EHIP;
+    }
+    return WMAR_OK;
+}
+
+int64_t wmar_gpt_probe_copy(wmar_gpt* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine,
+                            void* stream) {
+    if (!g || !name) { set_error("gpt_probe_copy: null argument"); return WMAR_EINVAL; }
+    if (layer < 0 || layer >= g->L) { set_error("gpt_probe_copy: layer %d outside 0..%d", layer, g->L - 1); return WMAR_EINVAL; }
+    const std::string n = name;
+    const size_t Mpad = (size_t)g->MTmax * 32, D = g->D, V = g->V;
+    const size_t lkv = (size_t)g->Bmax * g->H * g->Tmax * g->hd;
+    const size_t fx_units = (size_t)(4 * D / 24) * (D / 16) * 64;
+    const LayerW& w = g->layers[layer];
+    void* p = nullptr;
+    size_t sz = 0;
+    if (n == "x") { p = g->x; sz = Mpad * D * 4; }
+    else if (n == "x2") { p = g->x2; sz = Mpad * D * 4; }
+    else if (n == "y") { p = g->y; sz = Mpad * D * 4; }
+    else if (n == "yq") { p = g->yq; sz = D / 16 * 2 * 3 * 64 * 16; }
+    else if (n == "hbuf") { p = g->hbuf; sz = Mpad * 4 * D * 4; }
+    else if (n == "slabs") { p = g->slabs; sz = (size_t)MAX_SLABS * Mpad * D * 4; }
+    else if (n == "qkv_slabs") { p = g->qkv_slabs; sz = (size_t)MAX_SLABS * Mpad * 3 * D * 4; }
+    else if (n == "stats") { p = g->stats; sz = (size_t)STAT_CHUNKS_MAX * Mpad * 2 * 8; }
+    else if (n == "stats_q") { p = g->stats_q; sz = (size_t)QKV_SLABS_MAX * 4 * Mpad * 2 * 8; }
+    else if (n == "kcache") { p = g->kcache + (size_t)layer * lkv; sz = lkv * 4; }
+    else if (n == "vcache") { p = g->vcache + (size_t)layer * lkv; sz = lkv * 4; }
+    else if (n == "xs") { p = g->xs; sz = (size_t)SG_MAX_ROWS * D * 4; }
+    else if (n == "ys") { p = g->ys; sz = (size_t)SG_MAX_ROWS * D * 4; }
+    else if (n == "qs") { p = g->qs; sz = (size_t)SG_MAX_ROWS * D * 4; }
+    else if (n == "hs") { p = g->hs; sz = (size_t)SG_MAX_ROWS * 4 * D * 4; }
+    else if (n == "wqkv") { p = w.wqkv; sz = 3 * D * D * 4; }
+    else if (n == "wqkvx_bx") { p = w.wqkvx_bx; sz = 3 * D * D * 4; }
+    else if (n == "wproj") { p = w.wproj; sz = D * D * 4; }
+    else if (n == "wproj_bx") { p = w.wproj_bx; sz = D * D * 4; }
+    else if (n == "wfc1") { p = w.wfc1; sz = 4 * D * D * 4; }
+    else if (n == "wfc1x16") { p = w.wfc1x16; sz = fx_units * 16; }
+    else if (n == "wfc1x8") { p = w.wfc1x8; sz = fx_units * 8; }
+    else if (n == "wfc2") { p = w.wfc2; sz = 4 * D * D * 4; }
+    else if (n == "bqkv") { p = w.bqkv; sz = 3 * D * 4; }
+    else if (n == "cqkv") { p = w.cqkv; sz = 3 * D * 4; }
+    else if (n == "bproj") { p = w.bproj; sz = D * 4; }
+    else if (n == "bfc1") { p = w.bfc1; sz = 4 * D * 4; }
+    else if (n == "cfc1") { p = w.cfc1; sz = 4 * D * 4; }
+    else if (n == "bfc2") { p = w.bfc2; sz = D * 4; }
+    else if (n == "whead") { p = g->whead; sz = V * D * 4; }
+    else if (n == "bhead") { p = g->bhead; sz = V * 4; }
+    else if (n == "chead") { p = g->chead; sz = V * 4; }
+    else { set_error("gpt_probe_copy: unknown buffer '%s'", name); return WMAR_EINVAL; }
+    if (!p) { set_error("gpt_probe_copy: this engine has no buffer '%s' (its shape is not eligible for the kernel that uses it)", name); return WMAR_EINVAL; }
+    if (!ptr_dev) return (int64_t)sz;
+    if (bytes != (int64_t)sz) { set_error("gpt_probe_copy: '%s' holds %zu bytes, caller passed %lld", name, sz, (long long)bytes); return WMAR_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = to_engine ? hipMemcpyAsync(p, ptr_dev, sz, hipMemcpyDeviceToDevice, st)
+                             : hipMemcpyAsync(ptr_dev, p, sz, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("gpt_probe_copy: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+    return (int64_t)sz;
+}
+
+int wmar_gpt_probe_plan(wmar_gpt* g, int64_t B, int32_t kv_len, char* buf, int64_t buf_len) {
+    WMAR_REQUIRE(g && buf && buf_len > 0, "gpt_probe_plan: null argument");
+    WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "gpt_probe_plan: batch outside 1..%d", g->Bmax);
+    WMAR_REQUIRE(kv_len >= 1 && kv_len <= g->Tmax, "gpt_probe_plan: kv_len outside 1..%d", g->Tmax);
+    StepIO io{g->past, (long long)g->Tmax + 1, 0, g->logits};
+    StepPlan p(g, B, io, nullptr);
+    WMAR_REQUIRE(!p.persist, "gpt_probe_plan: the persistent small-batch step (k_sstep) is one launch and has no stages");
+    char kernels[1024];
+    if (int rc = wmar_gpt_plan_info(g, B, kernels, sizeof kernels)) return rc;
+    const int lrep = g->L > 1 ? 1 : 0;
+    std::string stages;
+    for (int s = WMAR_GPT_STAGE_EMBED; s <= WMAR_GPT_STAGE_HEAD; ++s)
+        if (p.has_stage(s, lrep)) stages += std::string(stages.empty() ? "" : ",") + kGptStageNames[s];
+    std::string head = "small";
+    int fc1_tiles = 0, head_tiles = 0;          // row tiles per workgroup of the k_gemm FC1 / head launches (0: another kernel)
+    if (!p.small) {
+        const int NT = g->V / 32;
+        if (p.head_ntw2()) { head = "ntw2"; head_tiles = 2; }
+        else {
+            const int per = p.head_per();
+            head = std::to_string((NT + per - 1) / per) + "," + std::to_string(per);
+            head_tiles = gemm_row_tiles(p.MT, NT < per ? NT : per);
+        }
+        if (!p.fc1_x()) fc1_tiles = gemm_row_tiles(p.MT, 4 * g->D / 32);
+    }
+    const int waves = p.small ? 4 : wmar_gpt::phase_waves(g->att_phase(kv_len, B));
+    const int n = snprintf(buf, (size_t)buf_len,
+                           "small=%d MT=%d S_qx=%d nkeep=%d S_qkv=%d S_proj=%d S_fc2=%d fc2_hi=%d nch=%d nch_ln2=%d pingpong=%d x_head=%s attn_waves=%d "
+                           "rowmajor=%d proj=%s head=%s fc1_tiles=%d head_tiles=%d xcd_ok=%d xr_eligible=%d barrier_fallbacks=%d stages=%s kernels=%s",
+                           p.small ? 1 : 0, p.MT, p.small ? 0 : p.S_qx, p.qx_nkeep(), p.S_qkv, p.S_proj, p.S_fc2, p.fc2_hi, p.nch, p.nch_ln2,
+                           !p.small && p.S_qx > 0 ? 1 : 0, p.xcur_at(WMAR_GPT_STAGE_HEAD, 0) == g->x2 ? "x2" : "x", waves,
+                           !p.small && p.qkv_bx() ? 1 : 0, p.small ? "small" : p.proj_xr ? "bx_xr" : p.proj_bx ? "bx" : "gemm", head.c_str(),
+                           fc1_tiles, head_tiles, g->xcd_ok_created ? 1 : 0, !p.small && p.xr_shape() ? 1 : 0, g->fallbacks, stages.c_str(), kernels);
+    WMAR_REQUIRE(n > 0 && n < buf_len, "gpt_probe_plan: buffer of %lld bytes too small", (long long)buf_len);
     return WMAR_OK;
 }
 
