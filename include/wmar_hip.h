@@ -253,7 +253,7 @@ int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* s
  * The residual stream buffer a stage reads follows the step: with S_qx > 0 it is x in front of an even layer's QKV and x2 behind
  * it (odd layers the other way round), RESID_OUT and HEAD read what block n_layer - 1 left; otherwise always x.  A raised in-launch
  * barrier flag is reported as WMAR_EHIP (the stages run are invalid; the engine continues on the two-launch path, as after
- * wmar_gpt_check).  The persistent small-batch step (WMAR_PERSIST=1) has no stages: WMAR_EINVAL.
+ * wmar_gpt_check).
  * wmar_gpt_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine).
  * Packed buffers are laid out for the MT of the step that wrote them (MT = 1 / 2 / 4 row tiles for B <= 32 / 64 / 128), sizes are
  * for Mpad = 32 * MT(max_batch) rows:

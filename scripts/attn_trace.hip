@@ -35,8 +35,8 @@ int main(int argc, char** argv) {
         hipEventRecord(e0, st);
         for (int l = 0; l < NL; ++l) {
             t.kcache = K[l]; t.vcache = V[l];
-            if (RM) hipLaunchKernelGGL((k_attn_decode<64, 1, false, 0, true>), dim3(nwg), dim3(64), 0, st, t);
-            else hipLaunchKernelGGL((k_attn_decode<64, 1, false, 0, false>), dim3(nwg), dim3(64), 0, st, t);
+            if (RM) hipLaunchKernelGGL((k_attn_decode<64, 1, 0, true>), dim3(nwg), dim3(64), 0, st, t);
+            else hipLaunchKernelGGL((k_attn_decode<64, 1, 0, false>), dim3(nwg), dim3(64), 0, st, t);
         }
         hipEventRecord(e1, st);
         hipStreamSynchronize(st);

@@ -31,20 +31,16 @@ int main() {
     size_t wmax = (size_t)16384 * D;
     std::vector<float4*> W(NBUF);
     for (auto& p : W) { hipMalloc(&p, wmax * 4); hipMemset(p, 0x3c, wmax * 4); }
-    float4 *X, *out; double* stats; float *bias, *logits, *qbuf, *kc, *vc; int* pos;
+    float4 *X, *out; double* stats; float *bias, *logits;
     hipMalloc(&X, (size_t)64 * 4 * D * 4); hipMemset(X, 0x3c, (size_t)64 * 4 * D * 4);
     hipMalloc(&out, (size_t)8 * 64 * 4 * D * 4);
     hipMalloc(&stats, 64 * 64 * 2 * 8); hipMemset(stats, 0, 64 * 64 * 2 * 8);
     hipMalloc(&bias, 16384 * 4); hipMemset(bias, 0, 16384 * 4);
     hipMalloc(&logits, (size_t)64 * 16384 * 4);
-    hipMalloc(&qbuf, 64 * D * 4);
-    hipMalloc(&kc, (size_t)64 * D * 256 * 4); hipMalloc(&vc, (size_t)64 * D * 256 * 4);
-    hipMalloc(&pos, 16); hipMemset(pos, 0, 16);
     for (auto& s : shapes) {
         GemmArgs a{};
         a.Xp = X; a.bias = bias; a.c1 = bias; a.KB = s.K / 8; a.NT = s.N / 32; a.MT = MT; a.S = s.S;
         a.stats = stats; a.n_chunks = 8; a.K = s.K; a.out_packed = out; a.slab_stride = (long long)s.N / 8 * MT * 64;
-        a.qbuf = qbuf; a.kcache = kc; a.vcache = vc; a.pos_dev = pos; a.D = D; a.H = 24; a.hd = 64; a.Tmax = 256;
         a.logits = logits; a.V = 16384; a.B = B;
         double flops = 2.0 * B * s.N * s.K;
         double bytes = 4.0 * s.N * s.K;

@@ -41,7 +41,7 @@ namespace wmar {
 using xg_f32x16 = __attribute__((ext_vector_type(16))) float;
 using xg_f32x4 = __attribute__((ext_vector_type(4))) float;
 
-enum { XG_EPI_GELU = 1, XG_EPI_RESID = 2, XG_EPI_QKV = 3 };
+enum { XG_EPI_GELU = 1, XG_EPI_RESID = 2 };
 
 struct XgArgs {
     const float4* Wq;          // k_pack_bx layout (LayerNorm gamma folded in for the LN epilogues)
@@ -57,11 +57,6 @@ struct XgArgs {
     const float* c1;           // [N] row sums of the gamma-folded weights (LN epilogues)
     const float4* Xres;        // XG_EPI_RESID: the residual stream, Xh layout over the OUTPUT features
     float4* out;               // XG_EPI_GELU / XG_EPI_RESID: Xh layout over the output features
-    // XG_EPI_QKV
-    float* qbuf;               // [64][D] row-major
-    float* kcache; float* vcache;   // [B][H][Tmax][hd] of this layer
-    const int* pos_dev;
-    int D, H, hd, Tmax, B;
     unsigned long long* trace; // dev only (XG_TRACE): 6 words per workgroup
 };
 
@@ -419,23 +414,9 @@ __global__ __launch_bounds__(NW * 64) void k_xg(XgArgs a) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = xg_gelu(v[e]);
         }
-        if (EPI == XG_EPI_QKV) {
-            if (m < a.B) {
-                const int which = ng / a.D, cq = ng - which * a.D;
-                float* dst;
-                if (which == 0) dst = a.qbuf + (long long)m * a.D + cq;
-                else {
-                    const int hh = cq / a.hd, d = cq - hh * a.hd;
-                    dst = (which == 1 ? a.kcache : a.vcache) + (((long long)m * a.H + hh) * a.Tmax + *a.pos_dev) * a.hd + d;
-                }
-                *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-                *(float4*)(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
-            }
-        } else {
-            float4* od = a.out + ((long long)((ng >> 4) * 2 + mt) * 64 + lane) * 2;
-            od[0] = make_float4(v[0], v[1], v[2], v[3]);
-            od[1] = make_float4(v[4], v[5], v[6], v[7]);
-        }
+        float4* od = a.out + ((long long)((ng >> 4) * 2 + mt) * 64 + lane) * 2;
+        od[0] = make_float4(v[0], v[1], v[2], v[3]);
+        od[1] = make_float4(v[4], v[5], v[6], v[7]);
     }
 }
 

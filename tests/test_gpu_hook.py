@@ -126,7 +126,7 @@ def test_rar_foreign_processors_reproduce_reference_tokens(hv, rar_small, proc, 
 
 
 # ------------------------------------------------------------------------------------- 2. hooked == fused, every plan
-@pytest.mark.parametrize("B", [1, 5, 16, 33, 64, 128])     # persistent step, small-batch plan / 13..32 / fused projection / above 64
+@pytest.mark.parametrize("B", [1, 5, 16, 33, 64, 128])     # small-batch plan (1, 5) / 13..32 / fused projection / above 64
 def test_taming_hooked_equals_fused_on_every_plan(prod_engine, wm_taming, B):
     """production width (24 heads x 64, n_embd 1536, V 16384), two layers: processor (a) == the fused key table, identity == no
     watermark, bit for bit, graph and eager"""

@@ -121,7 +121,7 @@ def _check_plan(gpt, B):
     """plan_info names the plan of the table in the module docstring"""
     info = gpt.plan_info(B)
     print(f"{B} rows: qkv={info['qkv']}; attn={info['attn']}; proj={info['proj']}; fc1={info['fc1']}; fc2={info['fc2']}")
-    assert not any("k_sgemv" in v or "k_sstep" in v for v in info.values()), info
+    assert not any("k_sgemv" in v for v in info.values()), info
     if B <= 32:
         assert "k_qkvx<1" in info["qkv"], info
         assert "k_gemm<EPI_PACKED>" in info["proj"] and "k_gemm<EPI_GELU,LN>" in info["fc1"], info

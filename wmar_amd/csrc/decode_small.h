@@ -32,7 +32,7 @@ namespace wmar {
 // The arithmetic of this file is PINNED: no implicit fp contraction (the compiler's choice between a fused and an unfused a * b + c
 // follows its scheduling context -- round 6: two builds that differed only in how a wave reduction moved data returned LayerNorm
 // statistics one ulp apart for one row in ~40, because the sum of squares was fused in one and not in the other); every fused
-// multiply-add below is written as one (fmaf / __builtin_elementwise_fma).  Restored at the end of decode_persist.h / this file.
+// multiply-add below is written as one (fmaf / __builtin_elementwise_fma).  Restored at the end of this file.
 #pragma clang fp contract(off)
 
 enum { SG_QKV = 0, SG_PROJ = 1, SG_FC1 = 2, SG_FC2 = 3, SG_HEAD = 4 };

@@ -250,7 +250,7 @@ __device__ __forceinline__ void ln_row_stats(const double* __restrict__ stats, i
 }
 
 // ------------------------------------------------------------------------- skinny GEMM
-enum { EPI_PACKED = 0, EPI_GELU = 1, EPI_QKV = 2, EPI_LOGITS = 3 };
+enum { EPI_PACKED = 0, EPI_GELU = 1, EPI_LOGITS = 3 };      // (the values appear in kernel names: 2 is not reused)
 
 struct GemmArgs {
     const float4* Wp;          // [NT][KB][64]
@@ -264,8 +264,7 @@ struct GemmArgs {
     // epilogues
     float4* out_packed; long long slab_stride;          // EPI_PACKED (slab s) / EPI_GELU
     u32x4* out_planes;                                  // EPI_GELU, nullable: the activation as bf16 pieces instead (a k_bx GEMM follows)
-    float* qbuf; float* kcache; float* vcache;          // EPI_QKV
-    const int* pos_dev; int D, H, hd, Tmax;
+    long long unused_[6];                               // arguments of the removed epilogue 2: the fields below keep their kernel-argument offsets
     float* logits; int V;                               // EPI_LOGITS
     int B;
     unsigned long long* trace;                          // dev only (WMAR_GEMM_TRACE): 4 timestamps per workgroup
@@ -524,18 +523,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
             } else {
                 float4* dst = a.out_packed + (long long)s * a.slab_stride + ((long long)(nt * 4 + g) * a.MT + mt) * 64 + lane;
                 st_out(dst, make_float4(o[0], o[1], o[2], o[3]));
-            }
-        } else if (EPI == EPI_QKV) {
-            if (m < a.B) {
-                const int which = n / a.D, c = n % a.D;
-                if (which == 0) {
-                    *(float4*)(a.qbuf + (long long)m * a.D + c) = make_float4(o[0], o[1], o[2], o[3]);
-                } else {
-                    const int hh = c / a.hd, d = c % a.hd;
-                    const int pos = *a.pos_dev;
-                    float* base = (which == 1) ? a.kcache : a.vcache;
-                    *(float4*)(base + (((long long)m * a.H + hh) * a.Tmax + pos) * a.hd + d) = make_float4(o[0], o[1], o[2], o[3]);
-                }
             }
         } else {  // EPI_LOGITS
             if (m < a.B) *(float4*)(a.logits + (long long)m * a.V + n) = make_float4(o[0], o[1], o[2], o[3]);
@@ -1809,7 +1796,7 @@ struct AttnArgs {
 // MODE (AttnArgs::mode) and RM (AttnArgs::rowmajor) are template parameters (round 5): as run-time branches around the prologue's
 // loads they left merge points behind which hipcc's s_waitcnt pass waited for EVERY outstanding load (vmcnt(0)) -- the cache chunks
 // requested in front of the q / k / v algebra had to land before it could even begin.
-template <int HD, int NWA, bool PF2 = false, int MODE = 0, bool RM = false>
+template <int HD, int NWA, int MODE = 0, bool RM = false>
 __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
     // LPRA lanes (one float4 each) cover a cache row; rows are laid on LPR = next power of two lanes so
     // that the row reductions are xor-shuffles (hd = 80: 20 of 32 lanes active, 2 rows per load).
@@ -1850,8 +1837,6 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
     unsigned long long tr[5];
     tr[0] = __builtin_amdgcn_s_memtime();
 #endif
-    // PF2: the wave's first TWO chunks are requested before the prologue (32 KiB in flight per wave: with 1 / 2 / 4 waves the
-    // whole cache up to 64 / 128 / 256 rows streams while q/k/v are finished); otherwise one, the second from inside the loop.
     // (Measured dead end: clamping the first chunk to the cache's capacity instead of its fill, so that its loads need not wait
     // for the scalar load of the position, saves 1.3 us at 64 rows and costs 3 us below 32 rows -- stale rows are then streamed.)
     // The prologue's loads go FIRST: loads return in issue order, so behind 16 KiB of cache rows per wave the QKV pieces would
@@ -1904,7 +1889,7 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
 #endif
     }
     WMAR_ATT_LOAD(kA, vA, w)                    // unconditional (clamped rows): see the refills below
-    if (PF2 || LATE2) { WMAR_ATT_LOAD(kB, vB, w + NWA) }
+    if (LATE2) { WMAR_ATT_LOAD(kB, vB, w + NWA) }
     __builtin_amdgcn_sched_barrier(0);
     if (w == 0) {
 #ifdef WMAR_STAMPS
@@ -2029,7 +2014,7 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
     // The refills inside the loop are UNCONDITIONAL (rows past the cache clamp to row T-1: L1 hits): a load under a run-time branch
     // makes hipcc's s_waitcnt pass take the smaller outstanding count of the two paths at the merge, i.e. every use of chunk c
     // then waits for chunk c+1's loads as well and the double buffer degenerates to one chunk in flight.
-    if (!PF2 && !LATE2) { WMAR_ATT_LOAD(kB, vB, w + NWA) }
+    if (!LATE2) { WMAR_ATT_LOAD(kB, vB, w + NWA) }
     __builtin_amdgcn_sched_barrier(0);
     for (int c = w; c < nchunk; c += 2 * NWA) {
         WMAR_ATT_CHUNK(kA, vA, c)
@@ -2137,8 +2122,6 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode80(AttnArgs a) {
       KT = WMAR_KV_LD((const float4*)(Ktail + (long long)t * HD));                       \
       VT = WMAR_KV_LD((const float4*)(Vtail + (long long)t * HD)); }
     float4 kmA[NU], vmA[NU], ktA, vtA, kmB[NU], vmB[NU], ktB, vtB;
-    // PF2: the wave's first TWO chunks are requested before the prologue (32 KiB in flight per wave: with 1 / 2 / 4 waves the
-    // whole cache up to 64 / 128 / 256 rows streams while q/k/v are finished); otherwise one, the second from inside the loop.
     // (Measured dead end: clamping the first chunk to the cache's capacity instead of its fill, so that its loads need not wait
     // for the scalar load of the position, saves 1.3 us at 64 rows and costs 3 us below 32 rows -- stale rows are then streamed.)
     // The prologue's loads go FIRST: loads return in issue order, so behind 16 KiB of cache rows per wave the QKV pieces would

@@ -23,7 +23,6 @@
 
 #include "decoder_host.h"
 #include "decode_small.h"
-#include "decode_persist.h"
 
 
 using namespace wmar;
@@ -40,8 +39,7 @@ struct LayerW {
 
 // Row-major weights of the small-batch path (decode_small.h): the checkpoint's own layout, LayerNorm NOT folded.
 struct SmallW {
-    float *wqkv = nullptr, *bqkv = nullptr, *wproj = nullptr, *bproj = nullptr, *wfc1 = nullptr, *bfc1 = nullptr, *wfc2 = nullptr, *bfc2 = nullptr;
-    float *ln1w = nullptr, *ln1b = nullptr, *ln2w = nullptr, *ln2b = nullptr;
+    float *wqkv = nullptr, *wproj = nullptr, *wfc1 = nullptr, *wfc2 = nullptr, *ln1w = nullptr, *ln2w = nullptr;
 };
 
 struct wmar_gpt {
@@ -51,22 +49,16 @@ struct wmar_gpt {
     std::vector<LayerW> layers;
     // small-batch path (1..12 rows, n_embd 1536, head_dim 64): streaming kernels on row-major weights, five launches per layer
     std::vector<SmallW> sw;
-    float *whead_rm = nullptr, *lnfw = nullptr, *lnfb = nullptr;
+    float *whead_rm = nullptr, *lnfw = nullptr;
     float *xs = nullptr, *ys = nullptr, *hs = nullptr, *qs = nullptr;     // [SG_MAX_ROWS][D], [..][D], [..][4D], [..][D] row-major
     bool small_ok = false;
-    // ... and for 1..5 rows the whole step as ONE persistent launch (decode_persist.h): needs all 256 workgroups resident and the
-    // blockIdx % 8 -> XCD grouping; a barrier that gives up switches the engine back to the five-launch plan (the call is re-run)
-    float* sw_arena = nullptr;         // all layers' small-batch weights, SS_LAYER_FLOATS per layer (SmallW points into it)
-    unsigned* ss_bar = nullptr;        // barrier words + fail flag (SS_BAR_WORDS)
-    bool persist_ok = false;
-    bool ps_enqueued = false;          // a persistent launch was enqueued since the last flag check
+    float* sw_arena = nullptr;     // all layers' small-batch weights in one allocation (SmallW points into it)
     bool xr_enqueued = false;      // a fused projection launch (k_bx_xr) was enqueued since the last flag check
     float *tok_emb = nullptr, *pos_emb = nullptr, *bhead = nullptr, *chead = nullptr;
     float4* whead = nullptr;
     // workspaces
     float4 *x = nullptr, *x2 = nullptr, *y = nullptr, *hbuf = nullptr, *slabs = nullptr, *qkv_slabs = nullptr;
     u32x4* yq = nullptr;           // attention output as bf16 pieces (k_bx output projection; 64-row steps)
-    float* qbuf = nullptr;
     double* stats = nullptr;
     double* stats_q = nullptr;   // [QKV_SLABS_MAX][Mpad][2]: LN1 row sums per K slice, written by k_qkvx
     float *kcache = nullptr, *vcache = nullptr;
@@ -196,11 +188,9 @@ struct StepPlan {
     bool proj_xr = false;     // ... with the residual fold + LN2 statistics inside the launch (k_bx_xr): no k_resid_stats behind it
     int nch_ln2 = 0;          // statistics chunks the FC1 launch reads (16 = two per XCD group behind k_bx_xr)
     bool small = false;       // 1..12 rows on an eligible engine: the streaming path of decode_small.h
-    bool persist = false;     // 1..5 rows: the whole step as one persistent launch (decode_persist.h)
 
     StepPlan(wmar_gpt* g_, int64_t B_, const StepIO& io_, hipStream_t st_) : g(g_), B(B_), io(io_), st(st_) {
         small = B <= SG_MAX_ROWS && g->small_ok;
-        persist = small && B <= SS_MAX_ROWS && g->persist_ok;
         MT = mt_for(B); D = g->D; KBD = D / 8; KBF = 4 * D / 8; nch = stat_chunks(KBD);
         act = (long long)KBD * MT * 64;  // float4 units of one [M][D] packed activation
         r.x = g->x; r.stats = g->stats; r.KB = KBD; r.MT = MT; r.n_chunks = nch;
@@ -248,16 +238,14 @@ struct StepPlan {
     bool qkv_bx() const { return S_qx > 0 && MT == 2 && g->layers[0].wqkvx_bx && !g->no_bx && !g->no_bx_qkv; }
     bool fc1_x() const { return MT == 2 && g->layers[0].wfc1x16 && nch_ln2 <= 16; }      // (k_fc1x: each wave fetches four of at most 16 statistics chunks)
     int qx_nkeep() const { const int G = 3 * D / 128; return G >= 4 && S_qx * 4 <= STAT_CHUNKS_MAX ? 4 : 1; }   // keeper groups per K slice (k_qkvx_bx)
-    static bool head_narrow() { static int v = -1; if (v < 0) v = getenv("WMAR_HEAD_NARROW") ? 1 : 0; return v != 0; }   // A/B: the two-launch 32-column head
     // the head's launch form (head() launches from these, wmar_gpt_probe_plan reports them): two column tiles per workgroup in ONE
     // launch at 64 rows, else launches of at most head_per() column tiles
-    bool head_ntw2() const { const int NT = g->V / 32; return MT == 2 && NT % 2 == 0 && NT / 2 <= 512 && !head_narrow(); }
+    bool head_ntw2() const { const int NT = g->V / 32; return MT == 2 && NT % 2 == 0 && NT / 2 <= 512; }
     int head_per() const { const int MG = (MT % 2 == 0) ? MT / 2 : MT; return 256 / MG > 0 ? 256 / MG : 1; }
     int split_for(int NT, int KB) const { return pick_split(MT % 2 == 0 ? NT * (MT / 2) : NT * MT, KB, 4); }
     GemmArgs base() const {
         GemmArgs a{};
         a.MT = MT; a.B = (int)B; a.stats = g->stats; a.n_chunks = nch; a.K = D;
-        a.pos_dev = g->pos_dev; a.D = D; a.H = g->H; a.hd = g->hd; a.Tmax = g->Tmax;
         return a;
     }
     SgArgs sg_base() const {
@@ -363,21 +351,14 @@ struct StepPlan {
 #endif
         const dim3 grid((unsigned)(B * g->H));
         g->span_begin(WMAR_T_ATTN, st);
-#define WMAR_ATT_LAUNCH3(HDV, PF, RMV)                                                                    \
-        if (nwa == 1) hipLaunchKernelGGL((k_attn_decode<HDV, 1, PF, 0, RMV>), grid, dim3(64), 0, st, t);       \
-        else if (nwa == 2) hipLaunchKernelGGL((k_attn_decode<HDV, 2, PF, 0, RMV>), grid, dim3(128), 0, st, t); \
-        else hipLaunchKernelGGL((k_attn_decode<HDV, 4, PF, 0, RMV>), grid, dim3(256), 0, st, t);
-#define WMAR_ATT_LAUNCH2(HDV, PF) if (t.rowmajor) { WMAR_ATT_LAUNCH3(HDV, PF, true) } else { WMAR_ATT_LAUNCH3(HDV, PF, false) }
-#define WMAR_ATT_LAUNCH(HDV) if (pf2) { WMAR_ATT_LAUNCH2(HDV, true) } else { WMAR_ATT_LAUNCH2(HDV, false) }
-#ifdef WMAR_ATT_PF2
-        const bool pf2 = true;
-#else
-        const bool pf2 = false;    // re-measured with exact waits (round 3) and with non-temporal K/V loads (round 4): +-1 % either way
-#endif
+#define WMAR_ATT_LAUNCH2(HDV, RMV)                                                                    \
+        if (nwa == 1) hipLaunchKernelGGL((k_attn_decode<HDV, 1, 0, RMV>), grid, dim3(64), 0, st, t);       \
+        else if (nwa == 2) hipLaunchKernelGGL((k_attn_decode<HDV, 2, 0, RMV>), grid, dim3(128), 0, st, t); \
+        else hipLaunchKernelGGL((k_attn_decode<HDV, 4, 0, RMV>), grid, dim3(256), 0, st, t);
+#define WMAR_ATT_LAUNCH(HDV) if (t.rowmajor) { WMAR_ATT_LAUNCH2(HDV, true) } else { WMAR_ATT_LAUNCH2(HDV, false) }
         if (g->hd == 64) { WMAR_ATT_LAUNCH(64) }
         else if (g->hd == 32) { WMAR_ATT_LAUNCH(32) }
         else { WMAR_ATT_LAUNCH(128) }
-#undef WMAR_ATT_LAUNCH3
 #undef WMAR_ATT_LAUNCH2
 #undef WMAR_ATT_LAUNCH
         g->span_end(st);
@@ -593,24 +574,17 @@ int enqueue_step(wmar_gpt* g, int64_t B, const StepIO& io, hipStream_t st) {
 #ifdef WMAR_DEV_KNOBS
     if (g->dbg_sums) { g->dbg_slot = 0; if (hipMemsetAsync(g->dbg_sums, 0, 4096 * 8, st) != hipSuccess) return WMAR_EHIP; }
 #endif
-    if (p.persist) {
-        SsArgs a{};
-        a.arena = g->sw_arena; a.L = g->L; a.tok_emb = g->tok_emb; a.pos_emb = g->pos_emb; a.whead = g->whead_rm; a.lnfw = g->lnfw; a.lnfb = g->lnfb;
-        a.tok = io.tok; a.tok_stride = io.tok_stride; a.tok_use_pos = io.tok_use_pos;
-        a.xs = g->xs; a.ys = g->ys; a.hs = g->hs; a.qs = g->qs; a.kcache = g->kcache; a.vcache = g->vcache;
-        a.lstride = (long long)g->Bmax * g->H * g->Tmax * g->hd; a.logits = io.logits; a.V = g->V; a.pos_dev = g->pos_dev;
-        a.D = g->D; a.H = g->H; a.Tmax = g->Tmax; a.bar = g->ss_bar;
-        g->span_begin(WMAR_T_QKV, st);
-        rc = launch_sstep(a, (int)B, st);
-        g->span_end(st);
-        g->ps_enqueued = true;
-        return rc;
-    }
     // the plan's stage sequence (has_stage): EMBED, per layer RESID_IN .. FC2, then RESID_OUT, HEAD
     if ((rc = p.run_stages(WMAR_GPT_STAGE_EMBED, WMAR_GPT_STAGE_EMBED, 0))) return rc;
     for (int l = 0; l < g->L; ++l)
         if ((rc = p.run_stages(WMAR_GPT_STAGE_RESID_IN, WMAR_GPT_STAGE_FC2, l))) return rc;
     return p.run_stages(WMAR_GPT_STAGE_RESID_OUT, WMAR_GPT_STAGE_HEAD, g->L - 1);
+}
+
+// a graph replay runs the launches of its capture without passing through proj(): record the fused projection launch for gpt_sync_failed
+void note_replayed(wmar_gpt* g, int64_t B, const StepIO& io) {
+    StepPlan pl(g, B, io, nullptr);
+    if (!pl.small && pl.proj_xr) g->xr_enqueued = true;
 }
 
 }  // namespace
@@ -731,45 +705,34 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
     if (rc == WMAR_OK && D == 2 * SG_SEG && hd == 64 && !getenv("WMAR_NO_SMALL")) {
         g->sw.resize(L);
         const size_t DD = (size_t)D * D;
-        // ONE allocation, fixed per-layer stride (decode_persist.h forms every address from this base)
-        WMAR_TRY(g->mem.alloc(&g->sw_arena, (size_t)L * SS_LAYER_FLOATS));
+        // ONE allocation: per layer the four matrices, then the two LayerNorm weights
+        const size_t layer_floats = 12 * DD + 2 * (size_t)D;
+        WMAR_TRY(g->mem.alloc(&g->sw_arena, (size_t)L * layer_floats));
         for (int l = 0; l < L && rc == WMAR_OK; ++l) {
             std::string p = "blocks." + std::to_string(l) + ".";
             SmallW& w = g->sw[l];
-            float* base = g->sw_arena + (size_t)l * SS_LAYER_FLOATS;
-            w.wqkv = base + SS_OFF_WQKV; w.wproj = base + SS_OFF_WPROJ; w.wfc1 = base + SS_OFF_WFC1; w.wfc2 = base + SS_OFF_WFC2;
-            w.bqkv = base + SS_OFF_BQKV; w.bproj = base + SS_OFF_BPROJ; w.bfc1 = base + SS_OFF_BFC1; w.bfc2 = base + SS_OFF_BFC2;
-            w.ln1w = base + SS_OFF_LN1W; w.ln1b = base + SS_OFF_LN1B; w.ln2w = base + SS_OFF_LN2W; w.ln2b = base + SS_OFF_LN2B;
+            float* next = g->sw_arena + (size_t)l * layer_floats;
+            auto take = [&](size_t n) { float* q = next; next += n; return q; };
+            w.wqkv = take(3 * DD); w.wproj = take(DD); w.wfc1 = take(4 * DD); w.wfc2 = take(4 * DD);
+            w.ln1w = take(D); w.ln2w = take(D);
             hipError_t e = hipSuccess;
             auto cp = [&](float* dst, const std::string& key, size_t n) {
                 if (e == hipSuccess) e = hipMemcpyAsync(dst, tm.get(p + key), n * 4, hipMemcpyDeviceToDevice, st);
             };
             cp(w.wqkv, "attn.query.weight", DD); cp(w.wqkv + DD, "attn.key.weight", DD); cp(w.wqkv + 2 * DD, "attn.value.weight", DD);
-            cp(w.bqkv, "attn.query.bias", D); cp(w.bqkv + D, "attn.key.bias", D); cp(w.bqkv + 2 * D, "attn.value.bias", D);
-            cp(w.wproj, "attn.proj.weight", DD); cp(w.bproj, "attn.proj.bias", D);
-            cp(w.wfc1, "mlp.0.weight", 4 * DD); cp(w.bfc1, "mlp.0.bias", (size_t)4 * D);
-            cp(w.wfc2, "mlp.2.weight", 4 * DD); cp(w.bfc2, "mlp.2.bias", D);
-            cp(w.ln1w, "ln1.weight", D); cp(w.ln1b, "ln1.bias", D); cp(w.ln2w, "ln2.weight", D); cp(w.ln2b, "ln2.bias", D);
+            cp(w.wproj, "attn.proj.weight", DD);
+            cp(w.wfc1, "mlp.0.weight", 4 * DD);
+            cp(w.wfc2, "mlp.2.weight", 4 * DD);
+            cp(w.ln1w, "ln1.weight", D); cp(w.ln2w, "ln2.weight", D);
             if (e != hipSuccess) { set_error("gpt_create: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
         }
         WMAR_TRY(copy_vec(g, &g->whead_rm, hw, (size_t)V * D, st));
         WMAR_TRY(copy_vec(g, &g->lnfw, lfw, D, st));
-        WMAR_TRY(copy_vec(g, &g->lnfb, lfb, D, st));
         WMAR_TRY(g->mem.alloc(&g->xs, (size_t)SG_MAX_ROWS * D));
         WMAR_TRY(g->mem.alloc(&g->ys, (size_t)SG_MAX_ROWS * D));
         WMAR_TRY(g->mem.alloc(&g->hs, (size_t)SG_MAX_ROWS * 4 * D));
         WMAR_TRY(g->mem.alloc(&g->qs, (size_t)SG_MAX_ROWS * D));
         g->small_ok = rc == WMAR_OK;
-        // the persistent step: per-layer pointer table, barrier words; all 256 workgroups of 320 threads must be resident at once and
-        // workgroups with equal blockIdx % 8 must share an XCD (probed below with the kernel's own grid).  WMAR_NO_PERSIST=1: off.
-        static_assert(SSD == 2 * SG_SEG, "arena offsets are for n_embd 1536");
-        // OPT-IN (WMAR_PERSIST=1 at creation): measured SLOWER than the five launches it replaces (round 6, DESIGN section 6a: 2.01 against
-        // 1.63 ms per step at batch 1, 2.85 against 1.89 at batch 5) -- the barrier's atomics and polls travel through the same in-order
-        // per-CU memory pipeline as the weight prefetch they are meant to overlap with; kept as a tested experiment, not the default plan.
-        if (g->small_ok && getenv("WMAR_PERSIST") && !getenv("WMAR_NO_PERSIST")) {
-            WMAR_TRY(g->mem.alloc_zero(&g->ss_bar, (size_t)SS_BAR_WORDS, st));
-            if (rc == WMAR_OK) g->persist_ok = grid_resident(sstep_blocks_per_cu(), SS_WGS) && xcd_grouping_ok(SS_WGS, SS_THREADS, st);
-        }
     }
     const size_t Mpad = (size_t)g->MTmax * 32;
     // (zero-filled: padded rows of the packed buffers must hold finite numbers)
@@ -780,7 +743,6 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
     WMAR_TRY(g->mem.alloc(&g->slabs, (size_t)MAX_SLABS * Mpad * D / 4));
     WMAR_TRY(g->mem.alloc(&g->qkv_slabs, (size_t)MAX_SLABS * Mpad * 3 * D / 4));
     if (g->MTmax >= 2 && D % BX_KSLICE == 0) WMAR_TRY(g->mem.alloc_zero(&g->yq, (size_t)D / 16 * 2 * 3 * 64, st));   // rows past the batch are never written
-    WMAR_TRY(g->mem.alloc_zero(&g->qbuf, Mpad * D, st));
     WMAR_TRY(g->mem.alloc(&g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2));
     WMAR_TRY(g->mem.alloc(&g->stats_q, (size_t)QKV_SLABS_MAX * 4 * Mpad * 2));      // x 4: k_qkvx_bx's keeper groups per K slice
     const size_t kv = (size_t)L * g->Bmax * H * g->Tmax * hd;
@@ -822,26 +784,7 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
 // The fused projection launch (k_bx_xr) raises device flags when its XCD-local barrier gives up or a block sits on a foreign XCD.
 // Returns 1 when a flag was up: the engine has then been switched to the two-launch path (k_bx + k_resid_stats), its graphs dropped
 // and the flags cleared -- the caller re-runs its work, which is deterministic in its inputs.  0: clean.  < 0: HIP error.
-// the persistent step's barrier (decode_persist.h): 1 when a wait gave up -- the engine is switched to the five-launch plan, its graphs
-// dropped, the barrier words cleared; the caller re-runs its work
-static int gpt_persist_failed(wmar_gpt* g, hipStream_t st) {
-    if (!g->ss_bar || !g->persist_ok || !g->ps_enqueued) return 0;
-    g->ps_enqueued = false;
-    unsigned f = 0;
-    WMAR_HIP_CHECK(hipMemcpyAsync(&f, g->ss_bar + 8 * 64 + 64, 4, hipMemcpyDeviceToHost, st));
-    WMAR_HIP_CHECK(hipStreamSynchronize(st));
-    if (!f) return 0;
-    g->gr.drop();
-    g->grh.drop();
-    WMAR_HIP_CHECK(hipMemsetAsync(g->ss_bar, 0, SS_BAR_WORDS * 4, st));
-    g->persist_ok = false;
-    g->fallbacks += 1;
-    fprintf(stderr, "wmar_amd: the persistent decode step (k_sstep) gave up waiting at its device-wide barrier; this engine continues on the "
-                    "five-launch small-batch plan (the call is re-run; wmar_gpt_plan_info reports barrier_fallbacks)\n");
-    return 1;
-}
 static int gpt_sync_failed(wmar_gpt* g, hipStream_t st) {
-    if (const int pf = gpt_persist_failed(g, st)) return pf;
     // only a fused launch can raise the flags: calls that enqueued none (two-launch path, WMAR_NO_XR, <= 32 rows, the small-batch
     // path) stay asynchronous and legal inside a caller's stream capture
     if (!g->xsync || !g->xcd_ok || g->no_xr || !g->xr_enqueued) return 0;
@@ -949,14 +892,6 @@ int wmar_gpt_plan_info(wmar_gpt* g, int64_t B, char* buf, int64_t buf_len) {
     WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "plan_info: batch outside 1..%d", g->Bmax);
     StepIO io{g->past, (long long)g->Tmax + 1, 0, g->logits};
     StepPlan p(g, B, io, nullptr);
-    if (p.persist) {
-        const int n = snprintf(buf, (size_t)buf_len,
-                               "qkv=k_sstep phase (the arithmetic of k_sgemv<QKV>, weights streamed across the barriers);attn=k_sstep phase;proj=k_sstep phase;resid=none;"
-                               "resid_launches_per_step=0;fc1=k_sstep phase;fc2=k_sstep phase;head=k_sstep phase;barrier_fallbacks=%d;"
-                               "path=persistent step: one launch, %d device-wide barriers (decode_persist.h)", g->fallbacks, 5 * g->L + 1);
-        WMAR_REQUIRE(n > 0 && n < buf_len, "plan_info: buffer of %lld bytes too small", (long long)buf_len);
-        return WMAR_OK;
-    }
     if (p.small) {
         const int n = snprintf(buf, (size_t)buf_len,
                                "qkv=k_sgemv<QKV> (row-major weight stream, LN1 + bias + cache append inside, %d columns per workgroup);"
@@ -1007,7 +942,6 @@ int wmar_gpt_probe_run(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t p
     StepIO io{(const long long*)tok_dev, 1, 0, logits_dev};
     g->att_nw = wmar_gpt::phase_waves(g->att_phase(pos + 1, B));
     StepPlan p(g, B, io, st);
-    WMAR_REQUIRE(!p.persist, "gpt_probe_run: the persistent small-batch step (k_sstep) is one launch and has no stages");
     WMAR_REQUIRE(p.has_stage(first_stage, layer) && p.has_stage(last_stage, layer), "gpt_probe_run: the plan for %lld rows has no stage %s in block %d",
                  (long long)B, kGptStageNames[p.has_stage(first_stage, layer) ? last_stage : first_stage], layer);
     hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, g->pos_dev, (int)pos);
@@ -1091,7 +1025,6 @@ int wmar_gpt_probe_plan(wmar_gpt* g, int64_t B, int32_t kv_len, char* buf, int64
     WMAR_REQUIRE(kv_len >= 1 && kv_len <= g->Tmax, "gpt_probe_plan: kv_len outside 1..%d", g->Tmax);
     StepIO io{g->past, (long long)g->Tmax + 1, 0, g->logits};
     StepPlan p(g, B, io, nullptr);
-    WMAR_REQUIRE(!p.persist, "gpt_probe_plan: the persistent small-batch step (k_sstep) is one launch and has no stages");
     char kernels[1024];
     if (int rc = wmar_gpt_plan_info(g, B, kernels, sizeof kernels)) return rc;
     const int lrep = g->L > 1 ? 1 : 0;
@@ -1145,7 +1078,7 @@ int wmar_gpt_debug_sums(wmar_gpt* g, unsigned long long* out, int n_out, int* n_
 #endif
 
 #ifdef WMAR_DEV_KNOBS
-// dev only: the small-batch plan's exchange buffers after the last step: which = 0 xs, 1 qs, 2 ys, 3 hs (4 D wide) -> out[8][width]
+// dev only: the small-batch plan's exchange buffers after the last step: which = 0 xs, 1 qs, 2 ys, 3 hs (4 D wide) -> out[SG_MAX_ROWS][width]
 int wmar_gpt_debug_small(wmar_gpt* g, int which, float* out) {
     WMAR_REQUIRE(g && g->small_ok && out && which >= 0 && which <= 3, "debug_small: bad argument");
     WMAR_HIP_CHECK(hipDeviceSynchronize());
@@ -1263,9 +1196,7 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
         // the seam between two graph launches is paid once per group.
         int gs = 1;
         {
-            static int env_gs = -1;
-            if (env_gs < 0) { const char* e = getenv("WMAR_GRAPH_STEPS"); env_gs = e ? atoi(e) : 0; }
-            const int want = env_gs > 0 ? env_gs : WMAR_GRAPH_STEPS_DEFAULT;
+            const int want = WMAR_GRAPH_STEPS_DEFAULT;
             const int n_need = (int)need[0] + (int)need[1] + (int)need[2];
             if (n_need == 1 && want > 1 && steps % want == 0) gs = want;
         }
@@ -1289,7 +1220,7 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
         for (int n = 0; n < steps; n += gs)
             if (int rc = g->gr.replay(g->att_phase(n + 1, B), st)) return rc;
         if (int rc = g->gr.replayed(st)) return rc;      // (gr.done also ends the timed span)
-        { StepPlan pl(g, B, io, nullptr); if (!pl.small && pl.proj_xr) g->xr_enqueued = true; if (pl.persist) g->ps_enqueued = true; }   // a replay runs the launches of its capture
+        note_replayed(g, B, io);
         // asynchronous: the caller's stream orders everything after the replays
         if (g->timing) WMAR_HIP_CHECK(hipEventSynchronize(g->gr.done));
     } else {
@@ -1387,7 +1318,7 @@ static int gpt_generate_hooked_once(wmar_gpt* g, const wmar_sample_params* sp, c
             memcpy(g->hook_key, key, sizeof(key));
         }
     }
-    { StepPlan pl(g, B, io, nullptr); if (!pl.small && pl.proj_xr) g->xr_enqueued = true; if (pl.persist) g->ps_enqueued = true; }
+    note_replayed(g, B, io);
     int rc = WMAR_OK;
     for (int n = 0; n < steps && rc == WMAR_OK; ++n) {
         const int ph = g->att_phase(n + 1, B);

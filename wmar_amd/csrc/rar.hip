@@ -472,7 +472,6 @@ struct RarPlan {
     GemmArgs base() const {
         GemmArgs a{};
         a.MT = MT; a.B = M; a.stats = g->stats; a.n_chunks = nch; a.K = D;
-        a.pos_dev = g->ctr; a.D = D; a.H = g->H; a.hd = g->hd; a.Tmax = g->T;
         return a;
     }
     int embed() {
@@ -535,7 +534,6 @@ struct RarPlan {
     // words of one k_resid_mod launch site at THIS plan's row count: [chunks][32 MT][2]; the sites are packed at this size, so the
     // poison memset of a position covers exactly what the launches poll
     size_t site_words() const { const int kpw = KBD <= 256 ? 1 : 4; return (size_t)((KBD + 4 * kpw - 1) / (4 * kpw)) * MT * 32 * 2; }
-    static bool att80() { static int v = -1; if (v < 0) { const char* e = getenv("WMAR_RAR_ATT80"); v = (e && atoi(e) == 0) ? 0 : 1; } return v != 0; }
     bool fc1_bx() const {
         return bx && g->bx_fc1
 #ifdef WMAR_DEV_KNOBS
@@ -555,9 +553,8 @@ struct RarPlan {
             BxArgs x{};
             x.Wq = w.wqkv_bx; x.Xq = g->xq; x.out = g->qkv_slabs; x.slab_stride = 3 * act; x.KU = D / 16; x.S = g->bx_qkv.S;
             // head_dim 80: the pieces go out row-major, so that the attention prologue of (row, head) reads 320 contiguous bytes per piece
-            // and q / k / v instead of 20 lines of the packed layout (k_attn_decode80 takes either; WMAR_RAR_QKV_PACKED=1: A/B)
-            static const bool qkv_packed = getenv("WMAR_RAR_QKV_PACKED") != nullptr;
-            qkv_rm = g->hd == 80 && att80() && !qkv_packed;
+            // and q / k / v instead of 20 lines of the packed layout (k_attn_decode80 takes either)
+            qkv_rm = g->hd == 80;
             x.rowmajor = qkv_rm ? 1 : 0; x.N = 3 * D;
             if ((rc = launch_bx4<2>(x, 3 * D, g->bx_qkv.PER, st))) return rc;     // 64-column groups: half the activation reads per column
             S_qkv = g->bx_qkv.S;
@@ -579,20 +576,18 @@ struct RarPlan {
         { const char* e = getenv("WMAR_RAR_ATT_NW"); if (e) nwa = atoi(e); }
 #endif
 #define WMAR_RAR_ATT(HDV)                                                                                   \
-        if (nwa == 1) hipLaunchKernelGGL((k_attn_decode<HDV, 1, false, 1, false>), grid, dim3(64), 0, st, t);                \
-        else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode<HDV, 4, false, 1, false>), grid, dim3(256), 0, st, t);          \
-        else hipLaunchKernelGGL((k_attn_decode<HDV, 2, false, 1, false>), grid, dim3(128), 0, st, t);
+        if (nwa == 1) hipLaunchKernelGGL((k_attn_decode<HDV, 1, 1, false>), grid, dim3(64), 0, st, t);                \
+        else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode<HDV, 4, 1, false>), grid, dim3(256), 0, st, t);          \
+        else hipLaunchKernelGGL((k_attn_decode<HDV, 2, 1, false>), grid, dim3(128), 0, st, t);
         switch (g->hd) {
             case 32: WMAR_RAR_ATT(32) break;
             case 48: WMAR_RAR_ATT(48) break;
             case 64: WMAR_RAR_ATT(64) break;
             case 80:
-                // all 64 lanes busy (k_attn_decode80); WMAR_RAR_ATT80=0 at run time keeps the 20-of-32-lane form (A/B)
-                if (att80()) {
-                    if (nwa == 1) hipLaunchKernelGGL((k_attn_decode80<1>), grid, dim3(64), 0, st, t);
-                    else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode80<4>), grid, dim3(256), 0, st, t);
-                    else hipLaunchKernelGGL((k_attn_decode80<2>), grid, dim3(128), 0, st, t);
-                } else { WMAR_RAR_ATT(80) }
+                // all 64 lanes busy (k_attn_decode80) instead of k_attn_decode's 20 of 32
+                if (nwa == 1) hipLaunchKernelGGL((k_attn_decode80<1>), grid, dim3(64), 0, st, t);
+                else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode80<4>), grid, dim3(256), 0, st, t);
+                else hipLaunchKernelGGL((k_attn_decode80<2>), grid, dim3(128), 0, st, t);
                 break;
             case 88: WMAR_RAR_ATT(88) break;
             default: WMAR_RAR_ATT(128) break;
@@ -608,20 +603,14 @@ struct RarPlan {
             p.Wp = w.wproj; p.Xp = g->y; p.KB = KBD; p.NT = D / 32; p.out_packed = g->slabs; p.slab_stride = act;
             if ((rc = gemm_split(p, &S, st, S_proj))) return rc;
         }
-        const bool fc1x = fc1_bx();
-        // round 5: eight waves x 10 steps instead of four x 20 (WMAR_RAR_FC1_NW4=1: the round-2 form, A/B); the operand as packed fp32
-        // rows split in registers instead of bf16 planes (two thirds of the activation bytes; WMAR_RAR_FC1_PLANES=1: A/B)
-        static const bool nw4 = getenv("WMAR_RAR_FC1_NW4") != nullptr;
-        static const bool fc1_planes = getenv("WMAR_RAR_FC1_PLANES") != nullptr;
-        const bool fc1_xf = fc1x && !nw4 && !fc1_planes;
-        // x += gate_msa * (proj + bias);  norm2 + modulate(shift_mlp, scale_mlp) -> the FC1 operand
-        if ((rc = resid_mod(2 * l, w.bproj, S_proj, o + 2 * D, w.n2w, w.n2b, o + 3 * D, o + 4 * D, (fc1x && !fc1_xf) ? g->xq : nullptr))) return rc;
-        if (fc1x) {
+        // x += gate_msa * (proj + bias);  norm2 + modulate(shift_mlp, scale_mlp) -> the FC1 operand (fp32 rows in g->h on either pipe)
+        if ((rc = resid_mod(2 * l, w.bproj, S_proj, o + 2 * D, w.n2w, w.n2b, o + 3 * D, o + 4 * D, nullptr))) return rc;
+        if (fc1_bx()) {
+            // round 5: eight waves x 10 steps instead of four x 20; the operand as packed fp32 rows split in registers instead of bf16
+            // planes (two thirds of the activation bytes)
             BxArgs x{};
-            x.Wq = w.wfc1_bx; x.Xq = fc1_xf ? (const u32x4*)g->h : g->xq; x.KU = D / 16; x.S = 1; x.bias = w.bfc1; x.outq = g->hq;
-            if (nw4) { if ((rc = launch_bx<1, 20, 4, true>(x, g->F, st))) return rc; }
-            else if (fc1_xf) { if ((rc = launch_bx<1, 10, 4, true, 8, true>(x, g->F, st))) return rc; }
-            else if ((rc = launch_bx<1, 10, 4, true, 8>(x, g->F, st))) return rc;
+            x.Wq = w.wfc1_bx; x.Xq = (const u32x4*)g->h; x.KU = D / 16; x.S = 1; x.bias = w.bfc1; x.outq = g->hq;
+            if ((rc = launch_bx<1, 10, 4, true, 8, true>(x, g->F, st))) return rc;
         } else {
             GemmArgs f = base();
             f.Wp = w.wfc1; f.Xp = g->h; f.bias = w.bfc1; f.KB = KBD; f.NT = g->F / 32; f.out_packed = g->hbuf;
@@ -703,8 +692,7 @@ int wmar_rar_create(const wmar_rar_config* cfg, const char* const* names, const 
         WMAR_TRY(copy_vec(g, &g->bhead, hb, (size_t)V, st));
         WMAR_TRY(g->mem.alloc(&g->wada, (size_t)g->Ntot * D / 4));
         WMAR_TRY(g->mem.alloc(&g->bada, (size_t)g->Ntot));
-        // WMAR_RAR_ADA_FP32=1 (A/B) keeps the per-step adaLN GEMM on the fp32-input MFMA
-        g->bx_ada = D == 1280 && g->Ntot % 128 == 0 && g->MTmax >= 2 && getenv("WMAR_NO_BX") == nullptr && getenv("WMAR_RAR_ADA_FP32") == nullptr;
+        g->bx_ada = D == 1280 && g->Ntot % 128 == 0 && g->MTmax >= 2 && getenv("WMAR_NO_BX") == nullptr;
         if (g->bx_ada) { WMAR_TRY(g->mem.alloc(&g->wada_bx, (size_t)g->Ntot * D / 4)); WMAR_TRY(g->mem.alloc_zero(&g->scq, (size_t)D / 16 * 2 * 3 * 64, st)); }      // rows past the batch are never written
     }
     if (g->MTmax >= 4 && D % 32 == 0 && F % 32 == 0) {
@@ -982,8 +970,8 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
         WMAR_HIP_CHECK(hipMalloc(&tmp, (size_t)MTt * 32 * g->D * 4));
         hipLaunchKernelGGL(k_rar_cond_rows, dim3((unsigned)(g->D / 8 * MTt)), dim3(64), 0, st, tmp, g->emb, g->tstep, none_id, g->T, MTt, g->D);
         GemmArgs a{};
-        a.MT = MTt; a.B = MTt * 32; a.K = g->D; a.D = g->D; a.Wp = g->wada; a.Xp = tmp; a.KB = g->D / 8; a.NT = (int)(g->Ntot / 32);
-        a.bias = g->bada; a.logits = g->mod_u; a.V = (int)g->Ntot; a.pos_dev = g->ctr;
+        a.MT = MTt; a.B = MTt * 32; a.K = g->D; a.Wp = g->wada; a.Xp = tmp; a.KB = g->D / 8; a.NT = (int)(g->Ntot / 32);
+        a.bias = g->bada; a.logits = g->mod_u; a.V = (int)g->Ntot;
         int rc = gemm_dispatch<EPI_LOGITS, false>(a, false, st);
         hipError_t e = hipStreamSynchronize(st);
         (void)hipFree(tmp);

@@ -1071,8 +1071,6 @@ struct Loader : TensorMap {
 
 // WMAR_CONV_NO_BX=1 (read once, any build): keep every convolution on the fp32-input MFMA.  The bf16-piece split turns an infinite
 // operand into NaN (inf - inf) where fp32 arithmetic gives +-inf (bx_split.h): a model with non-finite activations can opt out.
-static bool conv_s2_bx() { static int v = -1; if (v < 0) { const char* e = getenv("WMAR_CONV_S2_FP32"); v = e ? 0 : 1; } return v != 0; }      // A/B: WMAR_CONV_S2_FP32=1 keeps k_conv
-static bool conv_pt4() { static int v = -1; if (v < 0) { const char* e = getenv("WMAR_CONV_PT"); v = (e && atoi(e) == 2) ? 0 : 1; } return v != 0; }
 static bool conv_no_bx() { static int v = -1; if (v < 0) v = getenv("WMAR_CONV_NO_BX") ? 1 : 0; return v != 0; }
 #ifdef WMAR_DEV_KNOBS
 static bool vq_trace() { static int v = -1; if (v < 0) { const char* e = getenv("WMAR_VQ_TRACE"); v = e ? atoi(e) : 0; } return v != 0; }
@@ -1124,11 +1122,11 @@ int run_conv(const ConvW& c, const float* in, float* out, const float* res, int 
     if (stats) { a.st_part = g_trk.part; a.st_cpg = cpg_out; g_trk.src = out; g_trk.tiles = a.tiles_x * a.tiles_y; g_trk.C = c.cout; }
     else if (g_trk.src == out) g_trk.src = nullptr;      // the tensor the buffer described is being overwritten
     // k_conv_bx stages (PW * PW * 8) / threads float4 per thread: up to 13 (one wave per workgroup: the 128 -> 3 output conv)
-    const bool bx2 = c.wq && c.cin_s % CONV_CCH == 0 && stride == 2 && c.ks == 3 && COT == 4 && !up && !conv_no_bx() && conv_s2_bx();   // downsampling convs
+    const bool bx2 = c.wq && c.cin_s % CONV_CCH == 0 && stride == 2 && c.ks == 3 && COT == 4 && !up && !conv_no_bx();   // downsampling convs
     const bool bx = (c.wq && c.cin_s % CONV_CCH == 0 && stride == 1 && (c.ks == 3 || c.ks == 1) && !conv_no_bx()) || bx2;
     if (bx) a.dbuf = 1;
-    // 8 x 16 output pixels per workgroup (four pixel tiles per wave) for the wide 3 x 3 convolutions on the bf16 pipe: WMAR_CONV_PT=2 keeps 8 x 8 (A/B)
-    const bool wide = bx && !bx2 && COT == 4 && c.ks == 3 && a.tiles_x % 2 == 0 && wq_bstride == 0 && conv_pt4();
+    // 8 x 16 output pixels per workgroup (four pixel tiles per wave) for the wide 3 x 3 convolutions on the bf16 pipe
+    const bool wide = bx && !bx2 && COT == 4 && c.ks == 3 && a.tiles_x % 2 == 0 && wq_bstride == 0;
     const size_t lds = bx ? (size_t)2 * PW * (wide ? PW + 8 : PW) * CONV_PSTRIDE_BX : (size_t)(a.dbuf ? 2 : 1) * PW * PW * CONV_PSTRIDE * sizeof(float);
     const int cgroups = (c.CT + COT - 1) / COT;
     const unsigned grid = (unsigned)((long long)B * cgroups * (wide ? a.tiles_x / 2 : a.tiles_x) * a.tiles_y);
