@@ -8,7 +8,12 @@ MaskGIT-VQGAN).  Writes ``encoder_ft_delta.pth`` and ``decoder_ft_delta.pth`` in
     python finetune.py --model rar --synthetic --synthetic_config maskgit_small --nb_epochs 1 --augs none --batch_size_per_gpu 2 \
         --dataset_size 4 --outdir out/
 
-``--synthetic_config`` names are bound to models: ``harness`` / ``taming`` are Taming shapes, ``maskgit_small`` / ``maskgit`` are
+``--lpips_vgg PATH --lpips_lin PATH`` (torchvision's VGG16 state dict and the reference's ``vgg.pth``) add the reference's perceptual
+term to the regulariser, ``|x_orig_dec - x_rec| + --perceptual_weight x LPIPS``, on the device (wmar_amd/lpips.py); ``--synthetic_lpips``
+draws random LPIPS weights for a ``--synthetic`` run.  Without them the regulariser is the L1 half alone.  LPIPS runs at the
+tokenizer's resolution, which must be a multiple of 128.
+
+``--synthetic_config`` names are bound to models: ``harness`` / ``harness128`` / ``taming`` are Taming shapes, ``maskgit_small`` / ``maskgit`` are
 MaskGIT shapes for ``--model rar``; ``--model rar --modelpath DIR`` loads ``RarARMMWrapper(DIR)``.
 
 Not built here, each rejected with a message: multi-GPU training (DDP), tensorboard logging, the validation pass, and the
@@ -28,7 +33,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--modelpath", type=str, help="taming: directory with configs/net2net.yaml and checkpoints/net2net.ckpt; "
                                                  "rar: directory with maskgit-vqgan-imagenet-f16-256.bin and rar_xl.bin")
     p.add_argument("--synthetic", action="store_true", help="random-init weights instead of --modelpath")
-    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "taming", "maskgit_small", "maskgit"])
+    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "harness128", "taming", "maskgit_small", "maskgit"])
     p.add_argument("--datapath", type=str, help="int64 [N, S*S] codes, .pt or .npy (with --synthetic: random codes when absent)")
     p.add_argument("--dataset_size", type=int, help="number of rows to use")
     p.add_argument("--mode", type=str, default="newenc-dec")
@@ -47,11 +52,22 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--local_rank", "--local-rank", type=int, default=-1)
     p.add_argument("--tensorboard", action="store_true")
     p.add_argument("--validate", action="store_true")
+    p.add_argument("--lpips_vgg", type=str, help="torchvision's VGG16 state dict (features.N.weight / .bias): with --lpips_lin, adds the "
+                                                 "reference's LPIPS term to the regulariser")
+    p.add_argument("--lpips_lin", type=str, help="the reference's vgg.pth (the lin layers of LPIPS)")
+    p.add_argument("--synthetic_lpips", action="store_true", help="with --synthetic: a random-init full-width LPIPS instead of the two files")
+    p.add_argument("--perceptual_weight", type=float, default=1.0)
     return p
 
 
-# the synthetic shapes each trainable model takes
-SYNTHETIC_CONFIGS = {"taming": ("harness", "taming"), "rar": ("maskgit_small", "maskgit")}
+# the synthetic shapes each trainable model takes (harness128: the harness shape at 128 x 128, the smallest LPIPS takes)
+SYNTHETIC_CONFIGS = {"taming": ("harness128", "harness", "taming"), "rar": ("maskgit_small", "maskgit")}
+# resolution of each synthetic shape
+SYNTHETIC_RESOLUTION = {"harness": 32, "harness128": 128, "taming": 256, "maskgit_small": 32, "maskgit": 256}
+
+
+def wants_lpips(args) -> bool:
+    return bool(args.lpips_vgg or args.lpips_lin or args.synthetic_lpips)
 
 
 def check_args(args) -> None:
@@ -77,6 +93,15 @@ def check_args(args) -> None:
         raise SystemExit("finetune.py: give exactly one of --modelpath and --synthetic")
     if not args.synthetic and not args.datapath:
         raise SystemExit("finetune.py: --datapath is required with --modelpath")
+    if bool(args.lpips_vgg) != bool(args.lpips_lin):
+        raise SystemExit("finetune.py: --lpips_vgg and --lpips_lin go together: LPIPS needs the VGG16 weights and the lin layers")
+    if args.synthetic_lpips and not args.synthetic:
+        raise SystemExit("finetune.py: --synthetic_lpips is valid only with --synthetic (random LPIPS weights mean nothing to a real model)")
+    if args.synthetic_lpips and args.lpips_vgg:
+        raise SystemExit("finetune.py: give either --synthetic_lpips or --lpips_vgg / --lpips_lin")
+    if wants_lpips(args) and args.synthetic and SYNTHETIC_RESOLUTION[args.synthetic_config] % 128:
+        raise SystemExit(f"finetune.py: LPIPS needs a resolution that is a multiple of 128, --synthetic_config {args.synthetic_config} has "
+                         f"{SYNTHETIC_RESOLUTION[args.synthetic_config]}")
 
 
 def load_codes(path: str):
@@ -88,9 +113,10 @@ def load_codes(path: str):
     return codes
 
 
-def train(tok, orig, codes, args, log=print):
+def train(tok, orig, codes, args, log=print, rec_loss=None):
     """Adam (0.9, 0.999) + StepLR(gamma 0.9 per epoch) over the encoder's and the decoder's weights; the idempotence weight is multiplied
-    by its factor after every epoch.  Returns the number of optimizer steps."""
+    by its factor after every epoch.  ``rec_loss``: the regulariser of ``rcc_loss`` (None: L1 only).  Returns the number of optimizer
+    steps."""
     import torch
     from wmar_amd.augmentations import finetune_schedule
     from wmar_amd.finetune import calculate_gradient_norm, rcc_loss
@@ -106,7 +132,7 @@ def train(tok, orig, codes, args, log=print):
         order = torch.randperm(codes.shape[0], generator=gen)
         for b0 in range(0, codes.shape[0], bs):
             batch = codes[order[b0:b0 + bs]]
-            loss, _, log_dict, was_aug = rcc_loss(tok, batch, schedule[epoch], p=0.5, loss_weight=weight, orig=orig)
+            loss, _, log_dict, was_aug = rcc_loss(tok, batch, schedule[epoch], p=0.5, loss_weight=weight, orig=orig, rec_loss=rec_loss)
             opt.zero_grad(set_to_none=True)
             loss.backward()
             log_dict.update(epoch=epoch, step=steps, was_augmented=bool(was_aug), lr=sched.get_last_lr()[0],
@@ -147,12 +173,30 @@ def load_model(args):
         return model, model._vq_cfg, model._vq_cfg.num_embeddings, tt.MaskgitTrainableTokenizer
     from wmar_amd.models.taming_wrapper import TamingARMMWrapper
     if args.synthetic:
-        g, v = ((synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)) if args.synthetic_config == "harness"
-                else (synth.TAMING_GPT, synth.TAMING_VQ))
+        if args.synthetic_config == "harness":
+            g, v = synth.GPTConfig(**synth.HARNESS_GPT), synth.VQConfig(**synth.HARNESS_VQ)
+        elif args.synthetic_config == "harness128":     # 32 x 32 codes: the transformer (not trained) gets a sequence that long
+            g = synth.GPTConfig(**dict(synth.HARNESS_GPT, block_size=1024))
+            v = synth.VQConfig(**dict(synth.HARNESS_VQ, resolution=SYNTHETIC_RESOLUTION["harness128"]))
+        else:
+            g, v = synth.TAMING_GPT, synth.TAMING_VQ
         model = TamingARMMWrapper.synthetic(g, v, seed=args.seed, max_batch=mb)
     else:
         model = TamingARMMWrapper(args.modelpath, max_batch=mb)
     return model, model.model.vq_cfg, model.model.vq_cfg.n_embed, tt.TrainableTokenizer
+
+
+def load_lpips(args, resolution: int, device):
+    """The LPIPS engine the flags ask for, at the tokenizer's resolution; None without any of them."""
+    if not wants_lpips(args):
+        return None
+    from wmar_amd.lpips import LPIPS
+    if resolution % 128:
+        raise SystemExit(f"finetune.py: LPIPS needs a resolution that is a multiple of 128, the tokenizer has {resolution}")
+    if args.synthetic_lpips:
+        from wmar_amd.utils import synth
+        return LPIPS(synth.synth_lpips_state(seed=args.seed), resolution=resolution, max_batch=args.batch_size_per_gpu, device=device)
+    return LPIPS.from_files(args.lpips_vgg, args.lpips_lin, resolution=resolution, max_batch=args.batch_size_per_gpu, device=device)
 
 
 def main(argv=None) -> int:
@@ -179,14 +223,22 @@ def main(argv=None) -> int:
     for prm in orig.parameters():
         prm.requires_grad_(False)
     tok = model.trainable_tokenizer(max_batch=args.batch_size_per_gpu)
-    steps = train(tok, orig, codes, args)
+    lpips = load_lpips(args, vcfg.resolution, model.model.device)
+    rec_loss = None
+    if lpips is not None:
+        from wmar_amd.finetune import reference_rec_loss
+        rec_loss = reference_rec_loss(lpips, args.perceptual_weight)
+    steps = train(tok, orig, codes, args, rec_loss=rec_loss)
     os.makedirs(args.outdir, exist_ok=True)
     for name in ("encoder", "decoder"):
         handle = getattr(tokenizer, name)
         n = len(name) + 1
         save_delta(handle.state_dict(), {k[n:]: v for k, v in original.items() if k.startswith(name + ".")},
                    os.path.join(args.outdir, f"{name}_ft_delta.pth"))
-    print(json.dumps({"steps": steps, "outdir": args.outdir, "device_bytes": tok.device_bytes}))
+    summary = {"steps": steps, "outdir": args.outdir, "device_bytes": tok.device_bytes}
+    if lpips is not None:
+        summary["lpips_device_bytes"] = lpips.device_bytes
+    print(json.dumps(summary))
     return 0
 
 

@@ -653,6 +653,59 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 int wmar_mvq_train_create(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
                           wmar_vq_train** out);
 
+/* ------------------------------------------------------------------------ LPIPS (wmar_amd/csrc/lpips.h)
+ * The perceptual term of the tokenizer fine-tuning loss (deps/taming/modules/losses/lpips.py:41-122 in .eval()): a frozen VGG16
+ * features[0:30] on two images, per-pixel normalised at five taps, the squared differences weighted by the lin layers, averaged over
+ * the pixels and added in tap order.  The gradient goes to the first image (`input`) only; every weight is frozen.
+ *
+ * Tensors by the reference module's key names: scaling_layer.shift / .scale [1, 3, 1, 1]; net.slice1.0 / .2, net.slice2.5 / .7,
+ * net.slice3.10 / .12 / .14, net.slice4.17 / .19 / .21, net.slice5.24 / .26 / .28 each with .weight [cout, cin, 3, 3] and .bias;
+ * lin0 .. lin4 as lin<k>.model.1.weight [1, chns[k], 1, 1].  chns: the five slice widths (multiples of 8; VGG16 has 64, 128, 256,
+ * 512, 512).  resolution: a multiple of 128 (relu5_3 is resolution / 16 and the convolutions work on 8 x 8 tiles).
+ *
+ * All memory is allocated at create time for max_batch image pairs; no call allocates.  Reductions have a fixed order everywhere and
+ * there are no floating-point atomics: two runs give the same bits.  Images are [B, 3, S, S] fp32, contiguous. */
+typedef struct wmar_lpips_config {
+    int32_t chns[5];
+    int32_t resolution;
+    int32_t max_batch;
+} wmar_lpips_config;
+
+typedef struct wmar_lpips wmar_lpips;
+int wmar_lpips_create(const wmar_lpips_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                      wmar_lpips** out);
+void wmar_lpips_destroy(wmar_lpips* h);
+int64_t wmar_lpips_device_bytes(const wmar_lpips* h);
+/* value_dev [B] = LPIPS(input, target) per image; per_tap_dev [5, B] (may be NULL) the five terms it is the sum of.  keep_tape != 0
+ * keeps what the backward needs (the post-ReLU activations of the input branch, the normalised taps of the target branch); every
+ * forward replaces the tape of the one before. */
+int wmar_lpips_forward(wmar_lpips* h, const float* input_dev, const float* target_dev, int64_t B, int32_t keep_tape, float* value_dev,
+                       float* per_tap_dev, void* stream);
+/* grad_input_dev [B, 3, S, S] = sum_b grad_value_dev[b] d value[b] / d input.  WMAR_EINVAL (engine still usable) when the last
+ * forward kept no tape or ran another B. */
+int wmar_lpips_backward(wmar_lpips* h, const float* grad_value_dev, int64_t B, float* grad_input_dev, void* stream);
+
+/* One new layer alone, through the host functions the engine calls (the stream is waited for).  Activations NHWC fp32.
+ * Input edge: x_dev [B, 3, HW] -> y_dev [B, HW, 8] = (x - shift) / scale (fp32 subtract, fp32 divide; padding channels 0); its backward
+ * g_nhwc_dev [B, HW, 8] -> g_nchw_dev [B, 3, HW] = g / scale.  Both bit-equal to torch's fp32 result. */
+int wmar_lpips_probe_input(const float* x_dev, const float* shift_dev, const float* scale_dev, int64_t B, int32_t HW, float* y_dev, void* stream);
+int wmar_lpips_probe_input_backward(const float* g_nhwc_dev, const float* scale_dev, int64_t B, int32_t HW, float* g_nchw_dev, void* stream);
+/* ReLU + 2 x 2 stride-2 max-pool: x_dev [B, H, W, C] (C a multiple of 4, H and W even) -> y_dev = relu(x) (may be x_dev) and p_dev
+ * [B, H / 2, W / 2, C]; p_dev NULL runs the ReLU alone.  relu(x) = x < 0 ? 0 : x: -0.0 and NaN pass, as through torch's relu.
+ * Backward at the taped y_dev: gp_dev (gradient of p) goes to the first maximum of its window in row-major order, gt_dev (gradient
+ * reaching y directly; may be NULL) is added, the sum passes where y > 0 -> gx_dev (may be gt_dev).  gp_dev NULL: the ReLU alone on
+ * gt_dev.  Bit-equal to torch's fp32 autograd. */
+int wmar_lpips_probe_relu_pool(const float* x_dev, int64_t B, int32_t H, int32_t W, int32_t C, float* y_dev, float* p_dev, void* stream);
+int wmar_lpips_probe_relu_pool_backward(const float* y_dev, const float* gp_dev, const float* gt_dev, int64_t B, int32_t H, int32_t W, int32_t C,
+                                        float* gx_dev, void* stream);
+/* The head of one tap: f0_dev, f1_dev [B, HW, C] (C a multiple of 4, at most 1024), w_dev [C] -> value_dev [B], the mean over pixels
+ * of sum_c w_c (n0_c - n1_c)^2 with n = f / (sqrt(sum_c f^2) + 1e-10); its backward grad_value_dev [B] -> g0_dev [B, HW, C], the
+ * gradient towards f0 only, exactly 0 at a pixel whose f0 is all zero. */
+int wmar_lpips_probe_head(const float* f0_dev, const float* f1_dev, const float* w_dev, int64_t B, int32_t HW, int32_t C, float* value_dev,
+                          void* stream);
+int wmar_lpips_probe_head_backward(const float* f0_dev, const float* f1_dev, const float* w_dev, const float* grad_value_dev, int64_t B, int32_t HW,
+                                   int32_t C, float* g0_dev, void* stream);
+
 /* ------------------------------------------------------------------------ evaluation transforms (harness)
  * wmar/augmentations/valuemetric.py:41-140, geometric.py:22-117 as applied by generate.py:142-164: one launch over the whole batch
  * [B, C, H, W] (fp32, contiguous).  op: 0 identity, 1 Gaussian blur (p0 = odd kernel size), 2 Gaussian noise (p0 = standard deviation,

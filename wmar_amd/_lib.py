@@ -24,7 +24,9 @@ SYMBOLS = [
     "wmar_vq_probe_avgpool_backward", "wmar_mvq_probe_image_backward", "wmar_mvq_probe_input_backward", "wmar_mvq_train_create",
     "wmar_vq_train_create", "wmar_vq_train_destroy", "wmar_vq_train_device_bytes", "wmar_vq_train_set_weights", "wmar_vq_train_encode",
     "wmar_vq_train_encode_backward", "wmar_vq_train_decode", "wmar_vq_train_decode_backward", "wmar_vq_train_get_grads", "wmar_mvq_create", "wmar_mvq_destroy", "wmar_mvq_device_bytes", "wmar_mvq_decode",
-    "wmar_mvq_encode", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
+    "wmar_mvq_encode", "wmar_lpips_create", "wmar_lpips_destroy", "wmar_lpips_device_bytes", "wmar_lpips_forward", "wmar_lpips_backward",
+    "wmar_lpips_probe_input", "wmar_lpips_probe_input_backward", "wmar_lpips_probe_relu_pool", "wmar_lpips_probe_relu_pool_backward",
+    "wmar_lpips_probe_head", "wmar_lpips_probe_head_backward", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
     "wmar_cham_create", "wmar_cham_destroy", "wmar_cham_device_bytes", "wmar_cham_forward_tokens", "wmar_cham_generate_image",
     "wmar_cham_sample", "wmar_cham_probe_run", "wmar_cham_probe_copy", "wmar_cham_probe_plan",
     "wmar_cfg_mix", "wmar_gpt_generate_hooked", "wmar_rar_generate_hooked", "wmar_cham_generate_image_hooked",
@@ -79,6 +81,10 @@ class MvqConfig(C.Structure):
     _fields_ = [("hidden_channels", C.c_int32), ("num_res_blocks", C.c_int32), ("resolution", C.c_int32),
                 ("num_channels", C.c_int32), ("z_channels", C.c_int32), ("num_embeddings", C.c_int32),
                 ("n_levels", C.c_int32), ("channel_mult", C.c_int32 * 8), ("max_batch", C.c_int32)]
+
+
+class LpipsConfig(C.Structure):
+    _fields_ = [("chns", C.c_int32 * 5), ("resolution", C.c_int32), ("max_batch", C.c_int32)]
 
 
 class ChamConfig(C.Structure):
@@ -218,6 +224,19 @@ def load():
         L.wmar_vq_train_decode.argtypes = [vp, vp, i64, vp, vp]
         L.wmar_vq_train_decode_backward.argtypes = [vp, vp, i64, vp, vp]
         L.wmar_vq_train_get_grads.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(vp), i32, i32, vp]
+        L.wmar_lpips_create.argtypes = [C.POINTER(LpipsConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
+        L.wmar_lpips_destroy.argtypes = [vp]
+        L.wmar_lpips_destroy.restype = None
+        L.wmar_lpips_device_bytes.restype = i64
+        L.wmar_lpips_device_bytes.argtypes = [vp]
+        L.wmar_lpips_forward.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
+        L.wmar_lpips_backward.argtypes = [vp, vp, i64, vp, vp]
+        L.wmar_lpips_probe_input.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+        L.wmar_lpips_probe_input_backward.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.wmar_lpips_probe_relu_pool.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp]
+        L.wmar_lpips_probe_relu_pool_backward.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp]
+        L.wmar_lpips_probe_head.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+        L.wmar_lpips_probe_head_backward.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp]
     L.wmar_cham_create.argtypes = [C.POINTER(ChamConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
     L.wmar_cham_destroy.argtypes = [vp]
     L.wmar_cham_destroy.restype = None

@@ -1678,3 +1678,4 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 // ============================================================================ layer backward (tokenizer fine-tuning)
 #include "vq_grad.h"
 #include "vq_train.h"
+#include "lpips.h"

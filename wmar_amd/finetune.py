@@ -35,8 +35,9 @@ def rcc_loss(tok, z_indices: torch.Tensor, augmentations, p: float = 0.5, loss_w
     """decode -> ``apply_random_augmentation`` -> re-encode -> quantize, loss ``hard-to-soft-with-ae``: the regulariser
     ``rec_loss(xrec, orig.decode(z_q))`` plus ``loss_weight`` x the mean squared difference between the original (hard) code vectors
     and the re-encoded (soft) ones over ``idempotence_region``.  ``orig``: a frozen tokenizer holding the original decoder (the
-    reference's ``orig_decoder``); None drops the regulariser.  ``rec_loss`` defaults to the mean absolute difference.  The reference
-    adds LPIPS to it; LPIPS needs VGG weights this project does not ship, so a perceptual term stays a caller-supplied callable.
+    reference's ``orig_decoder``); None drops the regulariser.  ``rec_loss`` defaults to the mean absolute difference, the L1 half of
+    the reference's regulariser; ``reference_rec_loss(LPIPS(...))`` is the whole of it (L1 + LPIPS on the device, wmar_amd/lpips.py).
+    A ``rec_loss`` that leaves a ``perceptual_component`` attribute behind gets it logged as ``rec_loss_perceptual_component``.
     Returns the reference's ``(loss, res_dict, log_dict, was_augmented)``."""
     z_q = tok.embed(z_indices)
     xrec = tok.decode(z_q)
@@ -48,6 +49,8 @@ def rcc_loss(tok, z_indices: torch.Tensor, augmentations, p: float = 0.5, loss_w
             xrec_orig = orig.decode(z_q)
         reg = rec_loss(xrec, xrec_orig) if rec_loss is not None else (xrec - xrec_orig).abs().mean()
         log_dict["rec_loss"] = float(reg.detach())
+        if rec_loss is not None and getattr(rec_loss, "perceptual_component", None) is not None:
+            log_dict["rec_loss_perceptual_component"] = float(rec_loss.perceptual_component)
     applied = None
     xaug = xrec
     if augmentations is not None and len(augmentations) > 0:
@@ -65,6 +68,24 @@ def rcc_loss(tok, z_indices: torch.Tensor, augmentations, p: float = 0.5, loss_w
     res_dict = {"orig_z_q": z_q, "orig_z_indices": z_indices, "rec_x": xrec, "rec_x_maybe_augmented": xaug, "rec_x_orig_decoder": xrec_orig,
                 "rec_z": zrec, "rec_z_q": zrec_q, "rec_z_indices": zrec_indices}
     return loss, res_dict, log_dict, was_augmented
+
+
+class reference_rec_loss:
+    """The reference's regulariser ``torch.mean(|x_orig_dec - x_rec| + perceptual_weight * LPIPS(x_orig_dec, x_rec))``
+    (deps/taming/modules/losses/vqperceptual.py:83-92 with the GAN off; deps/rar/modeling/titok.py:113-115) as a ``rec_loss`` of
+    ``rcc_loss``: ``(xrec, xrec_orig) -> mean|xrec - xrec_orig| + perceptual_weight * mean_b lpips(xrec, xrec_orig)``.  The mean of the
+    broadcast sum is the sum of the two means.  LPIPS is symmetric in its arguments (every term is ``(n0 - n1)^2``), so handing it
+    ``xrec`` first changes no bit of the value and puts the gradient where the reference has it, on ``xrec``.  ``perceptual_component``
+    holds the last call's ``mean_b LPIPS`` (the reference logs it as ``vqgan_rec_loss_perceptual_component``)."""
+
+    def __init__(self, lpips, perceptual_weight: float = 1.0):
+        self.lpips, self.perceptual_weight = lpips, float(perceptual_weight)
+        self.perceptual_component: Optional[torch.Tensor] = None
+
+    def __call__(self, xrec: torch.Tensor, xrec_orig: torch.Tensor) -> torch.Tensor:
+        p = self.lpips(xrec, xrec_orig).mean()
+        self.perceptual_component = p.detach()
+        return (xrec - xrec_orig).abs().mean() + self.perceptual_weight * p
 
 
 def save_delta(trained_state: Dict[str, torch.Tensor], original_state: Dict[str, torch.Tensor], path: str) -> Dict[str, torch.Tensor]:

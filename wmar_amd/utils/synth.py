@@ -550,3 +550,45 @@ def synth_delta(state: Dict[str, torch.Tensor], prefix: str, seed: int = 0, scal
         t = state[k]
         out[k[len(prefix):]] = (torch.randn(t.shape, generator=g) * scale * float(t.abs().mean().clamp_min(1e-3))).to(torch.float32)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ LPIPS (VGG16 + lin layers)
+LPIPS_CHNS = (64, 128, 256, 512, 512)
+# torchvision's vgg16().features index of the convs of each slice (deps/taming/modules/losses/lpips.py:76-95)
+LPIPS_SLICE_CONVS = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))
+LPIPS_SHIFT = (-.030, -.088, -.188)     # lpips.py:60-61
+LPIPS_SCALE = (.458, .448, .450)
+
+
+def lpips_shapes(chns=LPIPS_CHNS) -> Dict[str, Tuple[int, ...]]:
+    """The reference LPIPS module's state_dict layout (its own key names and order) for slice widths ``chns``."""
+    s: Dict[str, Tuple[int, ...]] = {"scaling_layer.shift": (1, 3, 1, 1), "scaling_layer.scale": (1, 3, 1, 1)}
+    cin = 3
+    for k, idxs in enumerate(LPIPS_SLICE_CONVS):
+        for i in idxs:
+            s[f"net.slice{k + 1}.{i}.weight"] = (chns[k], cin, 3, 3)
+            s[f"net.slice{k + 1}.{i}.bias"] = (chns[k],)
+            cin = chns[k]
+    for k in range(5):
+        s[f"lin{k}.model.1.weight"] = (1, chns[k], 1, 1)
+    return s
+
+
+def synth_lpips_state(chns=LPIPS_CHNS, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A seeded LPIPS state in the reference layout: conv weights ``randn * sqrt(2 / (9 cin))`` (activations stay O(1) through the
+    13 layers), biases ``0.05 * randn``, non-negative lin weights ``rand / c``, the scaling constants of lpips.py:60-61."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed + 271828)
+    out: Dict[str, torch.Tensor] = {}
+    for k, shp in lpips_shapes(chns).items():
+        if k == "scaling_layer.shift":
+            out[k] = torch.tensor(LPIPS_SHIFT, dtype=torch.float32).view(shp)
+        elif k == "scaling_layer.scale":
+            out[k] = torch.tensor(LPIPS_SCALE, dtype=torch.float32).view(shp)
+        elif k.startswith("lin"):
+            out[k] = torch.rand(shp, generator=g) / shp[1]
+        elif k.endswith(".bias"):
+            out[k] = 0.05 * torch.randn(shp, generator=g)
+        else:
+            out[k] = torch.randn(shp, generator=g) * (2.0 / (9 * shp[1])) ** 0.5
+    return out
