@@ -352,6 +352,62 @@ int wmar_rar_generate_gumbel_ctx(wmar_rar* g, const int64_t* class_ids_dev, int6
 int wmar_rar_launch_status(const wmar_rar* g, int32_t* fused, int32_t* fallbacks);
 int wmar_rar_check(wmar_rar* g, void* stream);
 
+/* Test-only stage access to a live engine (no engine path calls these; tests/test_gpu_rar_kernels.py holds the launches of a RAR
+ * position to a float64 reference one at a time).  A position IS the sequence of stages below, one launch each (RESID_* on the
+ * two-launch pair: two); the engine walks it, the probe runs parts of it.  M rows, MT = 1 / 2 / 4 row tiles for M <= 32 / 64 / 128;
+ * MTc = row tiles of the adaLN rows (MT, or those of Bhalf under shared_u); bx = the 128-row plan on the bf16 matrix pipe.
+ *   EMBED       k_rar_embed             x = token vector + pos_embed[p] (+ target_aware_pos_embed[p + 1] for p >= 1), stats; sc (and scq
+ *                                       planes where ADALN runs as k_bx) = SiLU(emb[cond] + timesteps[p]) of the first 32 MTc rows.
+ *                                       tok_dev given: row m takes tok_dev[m] (-1 = cls); null: p = 0 cls, p = 1 emb[cond[m]],
+ *                                       p >= 2 emb[ids[(m % Bhalf) * image_seq_len + p - 2]]
+ *   ADALN       k_gemm<EPI_PACKED> / k_bx<4,20,2>   mod = sc Wada^T + bada, packed [Ntot/8][MTc][64][4]
+ *   MOD_IN      k_modulate              h (bx: xq planes) = LayerNorm(x; norm1 of block 0, eps 1e-6) (1 + scale) + shift
+ *   QKV         k_gemm<EPI_PACKED> / k_bx<2,PER,4>  qkv_slabs = S_qkv K slices of Wqkv h (head_dim 80 on bx: row-major pieces)
+ *   ATTN        k_attn_decode<HD,1,1> / k_attn_decode80<1>   bias, q_norm / k_norm per head (eps 1e-6), K / V row appended at p,
+ *                                       softmax(q K^T / sqrt(hd)) V -> y (bx: yq planes)
+ *   PROJ        k_gemm / k_bx<1,PER,4>  slabs = S_proj K slices of Wproj y
+ *   RESID_ATTN  k_resid_mod (site 2l)   x += gate_msa (bproj + slabs); h = LayerNorm(x; norm2) (1 + scale_mlp) + shift_mlp; part
+ *   FC1         k_gemm<EPI_GELU> / k_bx<1,10,4,GELU,8,XF>   hbuf (bx: hq planes) = gelu(Wfc1 h + bfc1)
+ *   FC2         k_gemm / k_bx<2,PER,4>  slabs = S_fc2 K slices of Wfc2 hbuf
+ *   RESID_MLP   k_resid_mod (site 2l+1) x += gate_mlp (bfc2 + slabs); h (bx: xq) = block l + 1's norm1 modulation, or behind the last
+ *                                       block the final layer's affine-free norm (its adaLN columns: scale first, then shift) into h
+ *   HEAD        k_gemm<EPI_LOGITS>      logits = Whead h + bhead
+ * Rows at or past Bhalf under shared_u take shift / scale / gate from row p of the row-major table mod_u [T][Ntot] instead of mod.
+ * adaLN columns: block l at 6 D l: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp; the final layer at 6 D L: scale, shift.
+ * wmar_rar_probe_run copies cond_ids_dev (int64 [M], may be null behind EMBED) into the engine, sets the position, builds the
+ * unconditional table if shared_u != 0 and it is not ready (M must then be 2 Bhalf; otherwise Bhalf = M), poisons the `part` sites of the
+ * RESID_* stages it runs as a position does, runs stages first_stage..last_stage of block `layer` (EMBED, ADALN, MOD_IN and HEAD
+ * ignore it) with the engine's own RarPlan and buffers, and waits for the stream.  tok_dev null selects the generate form of the
+ * embedding, reading the engine's `ids`.  A raised in-launch wait flag is reported as WMAR_EHIP, not re-run (the stages run are
+ * invalid; the engine continues on the two-launch pair, as after wmar_rar_check).
+ * wmar_rar_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine).
+ * Packed buffers are laid out for the MT of the position that wrote them, sizes are for Mpad = 32 MT(2 max_batch) rows:
+ *   x, h, y, sc [D/8][MT][64][4] fp32 (sc: MTc row tiles); hbuf [F/8][MT][64][4]; mod [Ntot/8][MTc][64][4]; mod_u [32 ceil(T/32)][Ntot];
+ *   slabs [8] pieces of D columns, qkv_slabs [S_qkv of the bx plan, else 1] pieces of 3 D columns (piece stride = columns x 32 MT floats);
+ *   xq, yq [D/16][MT][3][64][4] u32 and hq [F/16][MT][3][64][4] (bf16 planes, engines with the bx plan), scq [D/16][2][3][64][4];
+ *   stats [64][Mpad][2] fp64 (chunk stride 32 MT rows); part [2 L sites][nrm][32 MT][2] u64, sites packed at the position's MT;
+ *   logits [2 max_batch][V]; ids int64 [max_batch][image_seq_len]; cond_ids int64 [2 max_batch]; ctr int32 [4] (pos, step, len);
+ *   kcache, vcache [2 max_batch][H][image_seq_len + 2][head_dim] fp32 of block `layer`;
+ *   wqkv, wproj, wfc1, wfc2 (k_pack_linear order), wqkv_bx, wproj_bx, wfc1_bx, wfc2_bx (k_pack_bx order), bqkv, bproj, bfc1, bfc2,
+ *   norm1_w, norm1_b, norm2_w, norm2_b, q_norm_w, q_norm_b, k_norm_w, k_norm_b of block `layer`; wada, wada_bx, bada, whead, bhead.
+ * It returns the buffer's size in bytes (also with ptr_dev null: a size query) or a negative status (a buffer this engine does
+ * not have: WMAR_EINVAL); `bytes` must equal that size.
+ * wmar_rar_probe_plan writes, for a position of M rows attending to kv_len cached rows,
+ *   "MT=.. MTc=.. bx=.. ada_bx=.. fc1_bx=.. rowmajor=.. S_qkv=.. S_proj=.. S_fc2=.. PER_qkv=.. PER_proj=.. PER_fc2=.. nch=.. nrm=.. kpw=..
+ *    fused=.. fallbacks=.. ada_tiles=.. fc1_tiles=.. head_tiles=.. attn_waves=.. stages=EMBED,ADALN,.. kernels=embed=..;adaln=..;.."
+ * (nch: statistics chunks of EMBED / MOD_IN; nrm, kpw: chunks and k-blocks per wave of k_resid_mod; *_tiles: row tiles per workgroup
+ * of the k_gemm that runs the adaLN GEMM / FC1 / the head, 0 where k_bx does; PER_*: 0 off the bx plan; kernels: the instantiation
+ * behind every stage).  Every figure comes from the helper the launch itself uses. */
+enum {
+    WMAR_RAR_STAGE_EMBED = 0, WMAR_RAR_STAGE_ADALN, WMAR_RAR_STAGE_MOD_IN, WMAR_RAR_STAGE_QKV, WMAR_RAR_STAGE_ATTN, WMAR_RAR_STAGE_PROJ,
+    WMAR_RAR_STAGE_RESID_ATTN, WMAR_RAR_STAGE_FC1, WMAR_RAR_STAGE_FC2, WMAR_RAR_STAGE_RESID_MLP, WMAR_RAR_STAGE_HEAD
+};
+int wmar_rar_probe_run(wmar_rar* g, const int64_t* tok_dev, const int64_t* cond_ids_dev, int64_t M, int64_t Bhalf, int32_t shared_u,
+                       int32_t pos, int32_t layer, int32_t first_stage, int32_t last_stage, float* logits_dev, void* stream);
+int64_t wmar_rar_probe_copy(wmar_rar* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine,
+                            void* stream);
+int wmar_rar_probe_plan(wmar_rar* g, int64_t M, int64_t Bhalf, int32_t shared_u, int32_t kv_len, char* buf, int64_t buf_len);
+
 /* ----------------------------------------------------------------- Gumbel key (row G1)
  * Aaronson-style sampling of wmar_audio/watermark/engine.py:29-75 (`gumbel_sample`) and its
  * detector :123-134 (`gumbel_score_tok`).  The key of a row is rs = torch.rand(V, generator =

@@ -35,8 +35,8 @@ Rules this file applies, and why:
   * the head never runs on four row tiles per workgroup: its launches hold at most 128 column tiles at > 64 rows, and the dispatch
     takes that path only above 256 workgroups of two row tiles (head_tiles in the plan pins it; fc1_tiles = 4 pins the FC1 of A).
 
-Not reachable stage by stage, the obvious follow-up: the RAR-only variants (k_attn_decode80, attention mode 1, k_modulate,
-k_resid_mod, k_bx with GELU / XF / four row tiles)."""
+The RAR-only variants of these kernels (k_attn_decode80, attention mode 1, k_modulate, k_resid_mod, k_bx with GELU / XF / four row
+tiles) are held stage by stage in tests/test_gpu_rar_kernels.py, through wmar_rar_probe_*."""
 import ctypes as C
 import os
 import time

@@ -29,6 +29,7 @@ SYMBOLS = [
     "wmar_lpips_probe_head", "wmar_lpips_probe_head_backward", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
     "wmar_cham_create", "wmar_cham_destroy", "wmar_cham_device_bytes", "wmar_cham_forward_tokens", "wmar_cham_generate_image",
     "wmar_cham_sample", "wmar_cham_probe_run", "wmar_cham_probe_copy", "wmar_cham_probe_plan",
+    "wmar_rar_probe_run", "wmar_rar_probe_copy", "wmar_rar_probe_plan",
     "wmar_cfg_mix", "wmar_gpt_generate_hooked", "wmar_rar_generate_hooked", "wmar_cham_generate_image_hooked",
     "wmar_augment", "wmar_augment_backward", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
     "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
@@ -190,6 +191,10 @@ def load():
     L.wmar_rar_generate_gumbel_ctx.argtypes = [vp, vp, i64, C.POINTER(f32), i32, f32, f32, i32, C.c_uint64, i32, vp, vp, i32, vp]
     L.wmar_rar_check.argtypes = [vp, vp]
     L.wmar_rar_launch_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.wmar_rar_probe_run.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp]
+    L.wmar_rar_probe_copy.restype = i64
+    L.wmar_rar_probe_copy.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
+    L.wmar_rar_probe_plan.argtypes = [vp, i64, i64, i32, i32, C.c_char_p, i64]
     L.wmar_gumbel_key_build.argtypes = [C.c_uint64, i64, vp, vp, vp]
     L.wmar_gumbel_sample.argtypes = [vp, i64, i64, vp, i64, i32, f32, f32, i32, vp, vp]
     L.wmar_gumbel_score.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp]

@@ -90,10 +90,13 @@ int gemm_dispatch(GemmArgs a, bool allow_split, hipStream_t st) {
     return launch_gemm<1, NW, EPI, LN>(a, st);
 }
 
+// row tiles per workgroup of gemm_split's k_gemm
+inline int gemm_split_row_tiles(int MT) { return MT % 2 == 0 ? 2 : 1; }
+
 // split-K GEMM writing partial slabs; reports the S it used
 inline int gemm_split(GemmArgs a, int* S_out, hipStream_t st, int force_S = 0) {
     constexpr int NW = 4;
-    if (a.MT % 2 == 0) {
+    if (gemm_split_row_tiles(a.MT) == 2) {
         a.S = force_S > 0 ? force_S : pick_split(a.NT * (a.MT / 2), a.KB, NW);
         *S_out = a.S;
         return launch_gemm<2, NW, EPI_PACKED, false>(a, st);

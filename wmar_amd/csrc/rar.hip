@@ -456,6 +456,7 @@ struct RarPlan {
     bool bx = false;        // 128 rows: QKV / proj / FC2 on the bf16 matrix pipe
     const long long* ids = nullptr;   // generated ids the embedding reads: the engine's, or the caller's past buffer (hooked mode)
     long long ids_stride = 0;
+    float* logits_out = nullptr;      // where HEAD writes; null: the position has no HEAD stage
 
     RarPlan(wmar_rar* g_, int M_, int Bhalf_, const long long* tok_, hipStream_t st_, bool shared_u_ = false)
         : g(g_), M(M_), Bhalf(Bhalf_), st(st_), tok(tok_), shared_u(shared_u_) {
@@ -486,6 +487,7 @@ struct RarPlan {
     // all adaLN modulations of this position: mod[M][Ntot] = SiLU(c) W_ada^T + b_ada
     // 33..64 adaLN rows at hidden size 1280: on the bf16 pipe (round 5)
     bool ada_bx() const { return g->bx_ada && MTc == 2; }
+    int ada_mt() const { return MTc; }      // row tiles of the adaLN GEMM: the conditional rows' under shared_u, else MT (= MTc)
     int adaln() {
         if (ada_bx()) {
             // k_bx<4, 20, 2>: 128 columns x the whole K per workgroup (1940 workgroups), its four waves a K quarter each; weights fp32
@@ -499,7 +501,8 @@ struct RarPlan {
         GemmArgs a = base();
         a.Wp = g->wada; a.Xp = g->sc; a.KB = KBD; a.NT = (int)(g->Ntot / 32); a.bias = g->bada;
         a.out_packed = (float4*)g->mod; a.slab_stride = 0;        // packed [Ntot/8][MTc][64]: read like an activation by k_modulate / k_resid_mod
-        if (shared_u) { a.MT = MTc; a.B = Bhalf; }
+        a.MT = ada_mt();
+        if (shared_u) a.B = Bhalf;
         // (round 4: four column tiles per workgroup -- a quarter of the activation re-reads -- is 0.4 % SLOWER per step: at 1 wave per SIMD
         // the fp32-MFMA-bound launch, 259 us at peak, loses more latency hiding than the bytes buy)
         return gemm_dispatch<EPI_PACKED, false>(a, false, st);
@@ -520,7 +523,7 @@ struct RarPlan {
                   long long off_scale, u32x4* planes) {
         ResidModArgs a{};
         ResidArgs& r = a.r;
-        const int kpw = KBD <= 256 ? 1 : 4, nrm = (KBD + 4 * kpw - 1) / (4 * kpw);      // chunks of 4 (or 16) k-blocks: <= 64 per row tile
+        const int kpw = rm_kpw(), nrm = rm_chunks();      // chunks of 4 (or 16) k-blocks: <= 64 per row tile
         r.x = g->x; r.stats = g->stats; r.KB = KBD; r.MT = MT; r.n_chunks = nrm; r.B = M; r.K = D;
         r.slabs = g->slabs; r.slab_stride = act; r.S = S; r.bias = bias;
         r.pos_dev = g->ctr;
@@ -533,7 +536,9 @@ struct RarPlan {
     }
     // words of one k_resid_mod launch site at THIS plan's row count: [chunks][32 MT][2]; the sites are packed at this size, so the
     // poison memset of a position covers exactly what the launches poll
-    size_t site_words() const { const int kpw = KBD <= 256 ? 1 : 4; return (size_t)((KBD + 4 * kpw - 1) / (4 * kpw)) * MT * 32 * 2; }
+    int rm_kpw() const { return KBD <= 256 ? 1 : 4; }
+    int rm_chunks() const { return (KBD + 4 * rm_kpw() - 1) / (4 * rm_kpw()); }
+    size_t site_words() const { return (size_t)rm_chunks() * MT * 32 * 2; }
     bool fc1_bx() const {
         return bx && g->bx_fc1
 #ifdef WMAR_DEV_KNOBS
@@ -541,45 +546,54 @@ struct RarPlan {
 #endif
             ;
     }
+    // ---- one launch per stage (WMAR_RAR_STAGE_*): position() walks the sequence, wmar_rar_probe_run runs parts of it
     // The block's input rows arrive already modulated for the QKV projection (planes in g->xq when bx, else fp32 in g->h): by the
-    // position's first k_modulate (block 0) or by the previous block's second k_resid_mod.
-    int layer(int l) {
-        const RarLayer& w = g->layers[l];
-        const long long o = (long long)l * 6 * D;   // chunk(6): shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        int rc, S = 1;
-        int S_qkv = 1;
-        bool qkv_rm = false;
-        if (bx) {
-            BxArgs x{};
-            x.Wq = w.wqkv_bx; x.Xq = g->xq; x.out = g->qkv_slabs; x.slab_stride = 3 * act; x.KU = D / 16; x.S = g->bx_qkv.S;
-            // head_dim 80: the pieces go out row-major, so that the attention prologue of (row, head) reads 320 contiguous bytes per piece
-            // and q / k / v instead of 20 lines of the packed layout (k_attn_decode80 takes either)
-            qkv_rm = g->hd == 80;
-            x.rowmajor = qkv_rm ? 1 : 0; x.N = 3 * D;
-            if ((rc = launch_bx4<2>(x, 3 * D, g->bx_qkv.PER, st))) return rc;     // 64-column groups: half the activation reads per column
-            S_qkv = g->bx_qkv.S;
-        } else {
-            GemmArgs a = base();
-            a.Wp = w.wqkv; a.Xp = g->h; a.KB = KBD; a.NT = 3 * D / 32; a.out_packed = g->qkv_slabs; a.slab_stride = 3 * act;
-            if ((rc = gemm_split(a, &S, st, 1))) return rc;
-        }
-        AttnArgs t{};
-        const long long lstride = (long long)g->Mmax * g->H * g->T * g->hd;
-        t.qkv_slabs = g->qkv_slabs; t.slab_stride = 3 * act; t.S = S_qkv; t.stats = g->stats; t.n_chunks = nch; t.K = D; t.invK = 1.0 / (double)D;
-        t.rowmajor = qkv_rm ? 1 : 0;
-        t.bias = w.bqkv; t.mode = 1; t.qn_w = w.qnw; t.qn_b = w.qnb; t.kn_w = w.knw; t.kn_b = w.knb;
-        t.kcache = g->kcache + l * lstride; t.vcache = g->vcache + l * lstride; t.y = g->y; t.yq = bx ? g->yq : nullptr; t.pos_dev = g->ctr;
-        t.D = D; t.H = g->H; t.Tmax = g->T; t.MT = MT; t.scale = 1.0f / sqrtf((float)g->hd);
-        const dim3 grid((unsigned)(M * g->H));
+    // position's first k_modulate (MOD_IN) or by the previous block's second k_resid_mod (RESID_MLP).
+    // head_dim 80: the QKV pieces go out row-major, so that the attention prologue of (row, head) reads 320 contiguous bytes per piece
+    // and q / k / v instead of 20 lines of the packed layout (k_attn_decode80 takes either)
+    bool qkv_rm() const { return bx && g->hd == 80; }
+    int S_qkv() const { return bx ? g->bx_qkv.S : 1; }
+    int attn_waves() const {
         int nwa = 1;      // measured at 128 rows, head_dim 80, 256 positions: 4.58 / 4.75 / 4.83 ms per step with 1 / 2 / 4 waves per (sequence, head)
 #ifdef WMAR_DEV_KNOBS
         { const char* e = getenv("WMAR_RAR_ATT_NW"); if (e) nwa = atoi(e); }
 #endif
+        return nwa;
+    }
+    // the head_dim the attention launch is instantiated for (wmar_rar_create admits 32, 48, 64, 80, 88, 128)
+    int attn_hd() const {
+        switch (g->hd) { case 32: case 48: case 64: case 80: case 88: return g->hd; default: return 128; }
+    }
+    int mod_in() { const RarLayer& w0 = g->layers[0]; return modulate(w0.n1w, w0.n1b, 0, D, bx ? g->xq : nullptr); }
+    int qkv(int l) {
+        const RarLayer& w = g->layers[l];
+        if (bx) {
+            BxArgs x{};
+            x.Wq = w.wqkv_bx; x.Xq = g->xq; x.out = g->qkv_slabs; x.slab_stride = 3 * act; x.KU = D / 16; x.S = g->bx_qkv.S;
+            x.rowmajor = qkv_rm() ? 1 : 0; x.N = 3 * D;
+            return launch_bx4<2>(x, 3 * D, g->bx_qkv.PER, st);     // 64-column groups: half the activation reads per column
+        }
+        int S = 1;
+        GemmArgs a = base();
+        a.Wp = w.wqkv; a.Xp = g->h; a.KB = KBD; a.NT = 3 * D / 32; a.out_packed = g->qkv_slabs; a.slab_stride = 3 * act;
+        return gemm_split(a, &S, st, S_qkv());
+    }
+    int attn(int l) {
+        const RarLayer& w = g->layers[l];
+        AttnArgs t{};
+        const long long lstride = (long long)g->Mmax * g->H * g->T * g->hd;
+        t.qkv_slabs = g->qkv_slabs; t.slab_stride = 3 * act; t.S = S_qkv(); t.stats = g->stats; t.n_chunks = nch; t.K = D; t.invK = 1.0 / (double)D;
+        t.rowmajor = qkv_rm() ? 1 : 0;
+        t.bias = w.bqkv; t.mode = 1; t.qn_w = w.qnw; t.qn_b = w.qnb; t.kn_w = w.knw; t.kn_b = w.knb;
+        t.kcache = g->kcache + l * lstride; t.vcache = g->vcache + l * lstride; t.y = g->y; t.yq = bx ? g->yq : nullptr; t.pos_dev = g->ctr;
+        t.D = D; t.H = g->H; t.Tmax = g->T; t.MT = MT; t.scale = 1.0f / sqrtf((float)g->hd);
+        const dim3 grid((unsigned)(M * g->H));
+        const int nwa = attn_waves();
 #define WMAR_RAR_ATT(HDV)                                                                                   \
         if (nwa == 1) hipLaunchKernelGGL((k_attn_decode<HDV, 1, 1, false>), grid, dim3(64), 0, st, t);                \
         else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode<HDV, 4, 1, false>), grid, dim3(256), 0, st, t);          \
         else hipLaunchKernelGGL((k_attn_decode<HDV, 2, 1, false>), grid, dim3(128), 0, st, t);
-        switch (g->hd) {
+        switch (attn_hd()) {
             case 32: WMAR_RAR_ATT(32) break;
             case 48: WMAR_RAR_ATT(48) break;
             case 64: WMAR_RAR_ATT(64) break;
@@ -593,41 +607,57 @@ struct RarPlan {
             default: WMAR_RAR_ATT(128) break;
         }
 #undef WMAR_RAR_ATT
-        if ((rc = launch_status("k_attn_decode"))) return rc;
+        return launch_status("k_attn_decode");
+    }
+    int proj(int l) {
+        const RarLayer& w = g->layers[l];
         if (bx) {
             BxArgs x{};
             x.Wq = w.wproj_bx; x.Xq = g->yq; x.out = g->slabs; x.slab_stride = act; x.KU = D / 16; x.S = g->bx_proj.S;
-            if ((rc = launch_bx4<1>(x, D, g->bx_proj.PER, st))) return rc;
-        } else {
-            GemmArgs p = base();
-            p.Wp = w.wproj; p.Xp = g->y; p.KB = KBD; p.NT = D / 32; p.out_packed = g->slabs; p.slab_stride = act;
-            if ((rc = gemm_split(p, &S, st, S_proj))) return rc;
+            return launch_bx4<1>(x, D, g->bx_proj.PER, st);
         }
-        // x += gate_msa * (proj + bias);  norm2 + modulate(shift_mlp, scale_mlp) -> the FC1 operand (fp32 rows in g->h on either pipe)
-        if ((rc = resid_mod(2 * l, w.bproj, S_proj, o + 2 * D, w.n2w, w.n2b, o + 3 * D, o + 4 * D, nullptr))) return rc;
+        int S = 1;
+        GemmArgs p = base();
+        p.Wp = w.wproj; p.Xp = g->y; p.KB = KBD; p.NT = D / 32; p.out_packed = g->slabs; p.slab_stride = act;
+        return gemm_split(p, &S, st, S_proj);
+    }
+    // x += gate_msa * (proj + bias);  norm2 + modulate(shift_mlp, scale_mlp) -> the FC1 operand (fp32 rows in g->h on either pipe)
+    int resid_attn(int l) {
+        const RarLayer& w = g->layers[l];
+        const long long o = (long long)l * 6 * D;   // chunk(6): shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        return resid_mod(2 * l, w.bproj, S_proj, o + 2 * D, w.n2w, w.n2b, o + 3 * D, o + 4 * D, nullptr);
+    }
+    int fc1(int l) {
+        const RarLayer& w = g->layers[l];
         if (fc1_bx()) {
             // round 5: eight waves x 10 steps instead of four x 20; the operand as packed fp32 rows split in registers instead of bf16
             // planes (two thirds of the activation bytes)
             BxArgs x{};
             x.Wq = w.wfc1_bx; x.Xq = (const u32x4*)g->h; x.KU = D / 16; x.S = 1; x.bias = w.bfc1; x.outq = g->hq;
-            if ((rc = launch_bx<1, 10, 4, true, 8, true>(x, g->F, st))) return rc;
-        } else {
-            GemmArgs f = base();
-            f.Wp = w.wfc1; f.Xp = g->h; f.bias = w.bfc1; f.KB = KBD; f.NT = g->F / 32; f.out_packed = g->hbuf;
-            f.out_planes = bx ? g->hq : nullptr;
-            if ((rc = gemm_dispatch<EPI_GELU, false>(f, false, st))) return rc;
+            return launch_bx<1, 10, 4, true, 8, true>(x, g->F, st);
         }
+        GemmArgs f = base();
+        f.Wp = w.wfc1; f.Xp = g->h; f.bias = w.bfc1; f.KB = KBD; f.NT = g->F / 32; f.out_packed = g->hbuf;
+        f.out_planes = bx ? g->hq : nullptr;
+        return gemm_dispatch<EPI_GELU, false>(f, false, st);
+    }
+    int fc2(int l) {
+        const RarLayer& w = g->layers[l];
         if (bx) {
             BxArgs x{};
             x.Wq = w.wfc2_bx; x.Xq = g->hq; x.out = g->slabs; x.slab_stride = act; x.KU = g->F / 16; x.S = g->bx_fc2.S;
-            if ((rc = launch_bx4<2>(x, D, g->bx_fc2.PER, st))) return rc;
-        } else {
-            GemmArgs q = base();
-            q.Wp = w.wfc2; q.Xp = g->hbuf; q.KB = KBF; q.NT = D / 32; q.out_packed = g->slabs; q.slab_stride = act;
-            if ((rc = gemm_split(q, &S, st, S_fc2))) return rc;
+            return launch_bx4<2>(x, D, g->bx_fc2.PER, st);
         }
-        // x += gate_mlp * (FC2 + bias);  then the NEXT consumer's modulation: block l+1's norm1 (shift_msa, scale_msa), or the
-        // FinalLayer's affine-free norm (scale first, then shift: rar.py:132) into fp32 rows for the vocabulary head
+        int S = 1;
+        GemmArgs q = base();
+        q.Wp = w.wfc2; q.Xp = g->hbuf; q.KB = KBF; q.NT = D / 32; q.out_packed = g->slabs; q.slab_stride = act;
+        return gemm_split(q, &S, st, S_fc2);
+    }
+    // x += gate_mlp * (FC2 + bias);  then the NEXT consumer's modulation: block l+1's norm1 (shift_msa, scale_msa), or the
+    // FinalLayer's affine-free norm (scale first, then shift: rar.py:132) into fp32 rows for the vocabulary head
+    int resid_mlp(int l) {
+        const RarLayer& w = g->layers[l];
+        const long long o = (long long)l * 6 * D;
         if (l + 1 < g->L) {
             const RarLayer& nx = g->layers[l + 1];
             const long long o2 = o + 6 * D;
@@ -636,22 +666,56 @@ struct RarPlan {
         const long long of = (long long)g->L * 6 * D;
         return resid_mod(2 * l + 1, w.bfc2, S_fc2, o + 5 * D, nullptr, nullptr, of + D, of, nullptr);
     }
-    int head(float* logits_out) {
+    int head() {
         GemmArgs a = base();
         a.Wp = g->whead; a.Xp = g->h; a.KB = KBD; a.NT = g->V / 32; a.bias = g->bhead; a.logits = logits_out; a.V = g->V;
         return gemm_dispatch<EPI_LOGITS, false>(a, false, st);
     }
-    int position(bool with_head, float* logits_out) {
-        int rc;
-        if (hipMemsetAsync(g->part, 0xff, (size_t)2 * g->L * site_words() * 8, st) != hipSuccess) {     // poison: "not published yet"
+    // ---- the position as a sequence of stages:  EMBED ADALN MOD_IN | per block: QKV ATTN PROJ RESID_ATTN FC1 FC2 RESID_MLP | HEAD
+    // (HEAD only where logits are asked for: position 0 of a generation has none)
+    bool has_stage(int s, int /*l*/) const {
+        if (s == WMAR_RAR_STAGE_HEAD) return logits_out != nullptr;
+        return s >= WMAR_RAR_STAGE_EMBED && s < WMAR_RAR_STAGE_HEAD;
+    }
+    int run_stage(int s, int l) {
+        switch (s) {
+            case WMAR_RAR_STAGE_EMBED: return embed();
+            case WMAR_RAR_STAGE_ADALN: return adaln();
+            case WMAR_RAR_STAGE_MOD_IN: return mod_in();
+            case WMAR_RAR_STAGE_QKV: return qkv(l);
+            case WMAR_RAR_STAGE_ATTN: return attn(l);
+            case WMAR_RAR_STAGE_PROJ: return proj(l);
+            case WMAR_RAR_STAGE_RESID_ATTN: return resid_attn(l);
+            case WMAR_RAR_STAGE_FC1: return fc1(l);
+            case WMAR_RAR_STAGE_FC2: return fc2(l);
+            case WMAR_RAR_STAGE_RESID_MLP: return resid_mlp(l);
+            case WMAR_RAR_STAGE_HEAD: return head();
+            default: set_error("rar: unknown stage %d", s); return WMAR_EINVAL;
+        }
+    }
+    // stages first..last of block l in order; a stage this plan does not have is passed over
+    int run_stages(int first, int last, int l) {
+        for (int s = first; s <= last; ++s) {
+            if (!has_stage(s, l)) continue;
+            if (int rc = run_stage(s, l)) return rc;
+        }
+        return WMAR_OK;
+    }
+    // poison ("not published yet") the partial sums of k_resid_mod's launch sites [site0, site0 + n)
+    int poison(int site0, int n) {
+        if (hipMemsetAsync(g->part + (size_t)site0 * site_words(), 0xff, (size_t)n * site_words() * 8, st) != hipSuccess) {
             set_error("rar position: poisoning the partial sums failed"); return WMAR_EHIP;
         }
-        if ((rc = embed())) return rc;
-        if ((rc = adaln())) return rc;
-        { const RarLayer& w0 = g->layers[0]; if ((rc = modulate(w0.n1w, w0.n1b, 0, D, bx ? g->xq : nullptr))) return rc; }
+        return WMAR_OK;
+    }
+    int position(bool with_head, float* logits) {
+        int rc;
+        logits_out = with_head ? logits : nullptr;
+        if ((rc = poison(0, 2 * g->L))) return rc;
+        if ((rc = run_stages(WMAR_RAR_STAGE_EMBED, WMAR_RAR_STAGE_MOD_IN, 0))) return rc;
         for (int l = 0; l < g->L; ++l)
-            if ((rc = layer(l))) return rc;
-        return with_head ? head(logits_out) : WMAR_OK;
+            if ((rc = run_stages(WMAR_RAR_STAGE_QKV, WMAR_RAR_STAGE_RESID_MLP, l))) return rc;
+        return run_stages(WMAR_RAR_STAGE_HEAD, WMAR_RAR_STAGE_HEAD, g->L - 1);
     }
 };
 
@@ -930,6 +994,28 @@ static int rar_hooked_loop(wmar_rar* g, const HookIO& hk, int M, int B, bool sha
     return rc;
 }
 
+// The unconditional adaLN table mod_u [T][Ntot] (built once per engine): every unconditional row carries the "none" condition, so its
+// adaLN modulations depend on the position only -- SiLU(emb[none] + timesteps[p]) for every p (k_rar_cond_rows), then the adaLN GEMM
+// row-major.  wmar_rar_generate* under guidance and wmar_rar_probe_run with shared_u call it.
+static int rar_build_mod_u(wmar_rar* g, hipStream_t st) {
+    if (g->mod_u_ready) return WMAR_OK;
+    const long long none_id = (long long)g->cfg.condition_num_classes + g->V + 1;
+    const int MTt = (g->T + 31) / 32;
+    float4* tmp = nullptr;
+    WMAR_HIP_CHECK(hipMalloc(&tmp, (size_t)MTt * 32 * g->D * 4));
+    hipLaunchKernelGGL(k_rar_cond_rows, dim3((unsigned)(g->D / 8 * MTt)), dim3(64), 0, st, tmp, g->emb, g->tstep, none_id, g->T, MTt, g->D);
+    GemmArgs a{};
+    a.MT = MTt; a.B = MTt * 32; a.K = g->D; a.Wp = g->wada; a.Xp = tmp; a.KB = g->D / 8; a.NT = (int)(g->Ntot / 32);
+    a.bias = g->bada; a.logits = g->mod_u; a.V = (int)g->Ntot;
+    int rc = gemm_dispatch<EPI_LOGITS, false>(a, false, st);
+    hipError_t e = hipStreamSynchronize(st);
+    (void)hipFree(tmp);
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("unconditional adaLN table: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+    g->mod_u_ready = true;
+    return WMAR_OK;
+}
+
 static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,
                              const float* cfg_scale_host, int32_t use_guidance, float temperature, const float* q_dev,
                              const float* log_rs_dev, float top_p, int32_t top_k, uint64_t h0, int32_t ngram, const float* u_dev,
@@ -963,22 +1049,7 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
     if (use_guidance) WMAR_HIP_CHECK(hipMemcpyAsync(g->cfg_scale, cfg_scale_host, (size_t)L * 4, hipMemcpyHostToDevice, st));
     WMAR_HIP_CHECK(hipStreamSynchronize(st));   // host staging vectors go out of scope
 
-    if (use_guidance && !g->mod_u_ready) {
-        // every unconditional row has the same condition: its adaLN modulations depend on the position only
-        const int MTt = (g->T + 31) / 32;
-        float4* tmp = nullptr;
-        WMAR_HIP_CHECK(hipMalloc(&tmp, (size_t)MTt * 32 * g->D * 4));
-        hipLaunchKernelGGL(k_rar_cond_rows, dim3((unsigned)(g->D / 8 * MTt)), dim3(64), 0, st, tmp, g->emb, g->tstep, none_id, g->T, MTt, g->D);
-        GemmArgs a{};
-        a.MT = MTt; a.B = MTt * 32; a.K = g->D; a.Wp = g->wada; a.Xp = tmp; a.KB = g->D / 8; a.NT = (int)(g->Ntot / 32);
-        a.bias = g->bada; a.logits = g->mod_u; a.V = (int)g->Ntot;
-        int rc = gemm_dispatch<EPI_LOGITS, false>(a, false, st);
-        hipError_t e = hipStreamSynchronize(st);
-        (void)hipFree(tmp);
-        if (rc) return rc;
-        if (e != hipSuccess) { set_error("unconditional adaLN table: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-        g->mod_u_ready = true;
-    }
+    if (use_guidance) { if (int rc = rar_build_mod_u(g, st)) return rc; }
     const bool shared_u = use_guidance != 0;
     if (hk) return rar_hooked_loop(g, *hk, M, (int)B, shared_u, temperature, q_dev, tokens_out_dev, use_graph, st);
     RarPlan p(g, M, (int)B, nullptr, st, shared_u);
@@ -1088,6 +1159,168 @@ int wmar_rar_generate_gumbel_ctx(wmar_rar* g, const int64_t* class_ids_dev, int6
                  g->cfg.image_seq_len);
     return rar_generate_impl(g, nullptr, class_ids_dev, B, cfg_scale_host, use_guidance, temperature, nullptr, g->gum_keys, top_p,
                              top_k, h0, ngram, u_dev, tokens_out_dev, use_graph, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- test-only stage access
+static const char* const kRarStageNames[] = {"EMBED", "ADALN", "MOD_IN", "QKV", "ATTN", "PROJ", "RESID_ATTN", "FC1", "FC2", "RESID_MLP", "HEAD"};
+
+static int rar_probe_rows(const wmar_rar* g, const char* who, int64_t M, int64_t Bhalf, int32_t shared_u) {
+    WMAR_REQUIRE(M >= 1 && M <= g->Mmax, "%s: rows %lld outside 1..%d", who, (long long)M, g->Mmax);
+    if (shared_u) WMAR_REQUIRE(Bhalf >= 1 && Bhalf <= g->Bmax && M == 2 * Bhalf, "%s: shared_u needs M = 2 Bhalf, Bhalf in 1..%d", who, g->Bmax);
+    else WMAR_REQUIRE(Bhalf == M, "%s: without shared_u Bhalf is M", who);
+    return WMAR_OK;
+}
+
+int wmar_rar_probe_run(wmar_rar* g, const int64_t* tok_dev, const int64_t* cond_ids_dev, int64_t M, int64_t Bhalf, int32_t shared_u,
+                       int32_t pos, int32_t layer, int32_t first_stage, int32_t last_stage, float* logits_dev, void* stream) {
+    WMAR_REQUIRE(g, "rar_probe_run: null engine");
+    if (int rc = rar_probe_rows(g, "rar_probe_run", M, Bhalf, shared_u)) return rc;
+    WMAR_REQUIRE(pos >= 0 && pos < g->T, "rar_probe_run: position %d outside 0..%d", pos, g->T - 1);
+    WMAR_REQUIRE(layer >= 0 && layer < g->L, "rar_probe_run: layer %d outside 0..%d", layer, g->L - 1);
+    WMAR_REQUIRE(first_stage >= WMAR_RAR_STAGE_EMBED && last_stage <= WMAR_RAR_STAGE_HEAD && first_stage <= last_stage,
+                 "rar_probe_run: stages %d..%d", first_stage, last_stage);
+    WMAR_REQUIRE(last_stage < WMAR_RAR_STAGE_HEAD || logits_dev, "rar_probe_run: the HEAD stage needs logits_dev");
+    WMAR_REQUIRE(first_stage > WMAR_RAR_STAGE_EMBED || cond_ids_dev, "rar_probe_run: the EMBED stage needs cond_ids_dev");
+    hipStream_t st = (hipStream_t)stream;
+    if (shared_u) { if (int rc = rar_build_mod_u(g, st)) return rc; }
+    if (cond_ids_dev) WMAR_HIP_CHECK(hipMemcpyAsync(g->cond_ids, cond_ids_dev, (size_t)M * 8, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, (int)pos, pos > 0 ? pos - 1 : 0, pos > 1 ? pos - 2 : 0);
+    int rc = launch_status("k_set3");
+    RarPlan p(g, (int)M, (int)Bhalf, (const long long*)tok_dev, st, shared_u != 0);
+    p.logits_out = logits_dev;
+    // the sites of the k_resid_mod stages that run are poisoned, as position() does for all of them: a stale, non-poison word would let
+    // the fused wait pass with the previous run's sums
+    for (int s = first_stage; s <= last_stage && rc == WMAR_OK; ++s) {
+        if (!p.has_stage(s, layer)) continue;
+        if (s == WMAR_RAR_STAGE_RESID_ATTN) rc = p.poison(2 * layer, 1);
+        else if (s == WMAR_RAR_STAGE_RESID_MLP) rc = p.poison(2 * layer + 1, 1);
+    }
+    if (rc == WMAR_OK) rc = p.run_stages(first_stage, last_stage, layer);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc == WMAR_OK && e != hipSuccess) { set_error("rar_probe_run: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
+    if (rc != WMAR_OK) return rc;
+    const int f = rar_sync_failed(g, st, true);
+    if (f < 0) return f;
+    if (f > 0) {
+        set_error(f == 2 ? "rar_probe_run: the second launch of the two-launch residual pair read a partial sum its first launch had not written: "
+                           "the stages just run are invalid"
+                         : "rar_probe_run: an in-launch wait of k_resid_mod gave up: the stages just run are invalid (the engine continues on the "
+                           "two-launch pair)");
+        return WMAR_EHIP;
+    }
+    return WMAR_OK;
+}
+
+int64_t wmar_rar_probe_copy(wmar_rar* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine, void* stream) {
+    if (!g || !name) { set_error("rar_probe_copy: null argument"); return WMAR_EINVAL; }
+    if (layer < 0 || layer >= g->L) { set_error("rar_probe_copy: layer %d outside 0..%d", layer, g->L - 1); return WMAR_EINVAL; }
+    const std::string n = name;
+    const size_t Mpad = (size_t)g->MTmax * 32, D = g->D, F = g->F, V = g->V, hd = g->hd, Ntot = (size_t)g->Ntot;
+    const size_t lkv = (size_t)g->Mmax * g->H * g->T * g->hd;
+    const RarLayer& w = g->layers[layer];
+    void* p = nullptr;
+    size_t sz = 0;
+    if (n == "x") { p = g->x; sz = Mpad * D * 4; }
+    else if (n == "h") { p = g->h; sz = Mpad * D * 4; }
+    else if (n == "y") { p = g->y; sz = Mpad * D * 4; }
+    else if (n == "sc") { p = g->sc; sz = Mpad * D * 4; }
+    else if (n == "hbuf") { p = g->hbuf; sz = Mpad * F * 4; }
+    else if (n == "scq") { p = g->scq; sz = D / 16 * 2 * 3 * 64 * 16; }
+    else if (n == "mod") { p = g->mod; sz = Mpad * Ntot * 4; }
+    else if (n == "mod_u") { p = g->mod_u; sz = (size_t)((g->T + 31) / 32) * 32 * Ntot * 4; }
+    else if (n == "slabs") { p = g->slabs; sz = (size_t)MAX_SLABS * Mpad * D * 4; }
+    else if (n == "qkv_slabs") { p = g->qkv_slabs; sz = (size_t)(g->bx_ok ? g->bx_qkv.S : 1) * Mpad * 3 * D * 4; }
+    else if (n == "xq") { p = g->xq; sz = D / 16 * 4 * 3 * 64 * 16; }
+    else if (n == "yq") { p = g->yq; sz = D / 16 * 4 * 3 * 64 * 16; }
+    else if (n == "hq") { p = g->hq; sz = F / 16 * 4 * 3 * 64 * 16; }
+    else if (n == "stats") { p = g->stats; sz = (size_t)STAT_CHUNKS_MAX * Mpad * 2 * 8; }
+    else if (n == "part") { p = g->part; sz = (size_t)2 * g->L * g->part_site * 8; }
+    else if (n == "logits") { p = g->logits; sz = (size_t)g->Mmax * V * 4; }
+    else if (n == "ids") { p = g->ids; sz = (size_t)g->Bmax * g->cfg.image_seq_len * 8; }
+    else if (n == "cond_ids") { p = g->cond_ids; sz = (size_t)g->Mmax * 8; }
+    else if (n == "ctr") { p = g->ctr; sz = 16; }
+    else if (n == "kcache") { p = g->kcache + (size_t)layer * lkv; sz = lkv * 4; }
+    else if (n == "vcache") { p = g->vcache + (size_t)layer * lkv; sz = lkv * 4; }
+    else if (n == "wqkv") { p = w.wqkv; sz = 3 * D * D * 4; }
+    else if (n == "wproj") { p = w.wproj; sz = D * D * 4; }
+    else if (n == "wfc1") { p = w.wfc1; sz = F * D * 4; }
+    else if (n == "wfc2") { p = w.wfc2; sz = F * D * 4; }
+    else if (n == "wqkv_bx") { p = w.wqkv_bx; sz = 3 * D * D * 4; }
+    else if (n == "wproj_bx") { p = w.wproj_bx; sz = D * D * 4; }
+    else if (n == "wfc1_bx") { p = w.wfc1_bx; sz = F * D * 4; }
+    else if (n == "wfc2_bx") { p = w.wfc2_bx; sz = F * D * 4; }
+    else if (n == "bqkv") { p = w.bqkv; sz = 3 * D * 4; }
+    else if (n == "bproj") { p = w.bproj; sz = D * 4; }
+    else if (n == "bfc1") { p = w.bfc1; sz = F * 4; }
+    else if (n == "bfc2") { p = w.bfc2; sz = D * 4; }
+    else if (n == "norm1_w") { p = w.n1w; sz = D * 4; }
+    else if (n == "norm1_b") { p = w.n1b; sz = D * 4; }
+    else if (n == "norm2_w") { p = w.n2w; sz = D * 4; }
+    else if (n == "norm2_b") { p = w.n2b; sz = D * 4; }
+    else if (n == "q_norm_w") { p = w.qnw; sz = hd * 4; }
+    else if (n == "q_norm_b") { p = w.qnb; sz = hd * 4; }
+    else if (n == "k_norm_w") { p = w.knw; sz = hd * 4; }
+    else if (n == "k_norm_b") { p = w.knb; sz = hd * 4; }
+    else if (n == "wada") { p = g->wada; sz = Ntot * D * 4; }
+    else if (n == "wada_bx") { p = g->wada_bx; sz = Ntot * D * 4; }
+    else if (n == "bada") { p = g->bada; sz = Ntot * 4; }
+    else if (n == "whead") { p = g->whead; sz = V * D * 4; }
+    else if (n == "bhead") { p = g->bhead; sz = V * 4; }
+    else { set_error("rar_probe_copy: unknown buffer '%s'", name); return WMAR_EINVAL; }
+    if (!p) { set_error("rar_probe_copy: this engine has no buffer '%s' (its shape is not eligible for the kernel that uses it)", name); return WMAR_EINVAL; }
+    if (!ptr_dev) return (int64_t)sz;
+    if (bytes != (int64_t)sz) { set_error("rar_probe_copy: '%s' holds %zu bytes, caller passed %lld", name, sz, (long long)bytes); return WMAR_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = to_engine ? hipMemcpyAsync(p, ptr_dev, sz, hipMemcpyDeviceToDevice, st)
+                             : hipMemcpyAsync(ptr_dev, p, sz, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("rar_probe_copy: %s", hipGetErrorString(e)); return WMAR_EHIP; }
+    return (int64_t)sz;
+}
+
+int wmar_rar_probe_plan(wmar_rar* g, int64_t M, int64_t Bhalf, int32_t shared_u, int32_t kv_len, char* buf, int64_t buf_len) {
+    WMAR_REQUIRE(g && buf && buf_len > 0, "rar_probe_plan: null argument");
+    if (int rc = rar_probe_rows(g, "rar_probe_plan", M, Bhalf, shared_u)) return rc;
+    WMAR_REQUIRE(kv_len >= 1 && kv_len <= g->T, "rar_probe_plan: kv_len outside 1..%d", g->T);
+    RarPlan p(g, (int)M, (int)Bhalf, nullptr, nullptr, shared_u != 0);
+    p.logits_out = g->logits;
+    std::string stages;
+    for (int s = WMAR_RAR_STAGE_EMBED; s <= WMAR_RAR_STAGE_HEAD; ++s)
+        if (p.has_stage(s, 0)) stages += std::string(stages.empty() ? "" : ",") + kRarStageNames[s];
+    const int ada_tiles = p.ada_bx() ? 0 : gemm_row_tiles(p.ada_mt(), (int)(g->Ntot / 32));
+    const int split_tiles = gemm_split_row_tiles(p.MT);
+    const int fc1_tiles = p.fc1_bx() ? 0 : gemm_row_tiles(p.MT, g->F / 32);
+    const int head_tiles = gemm_row_tiles(p.MT, g->V / 32);
+    const int kpw = p.rm_kpw(), nwa = p.attn_waves();
+    char k[1024], t[160];
+    std::string ks = "embed=k_rar_embed;adaln=";
+    if (p.ada_bx()) ks += "k_bx<4,20,2>"; else { snprintf(t, sizeof t, "k_gemm<%d,EPI_PACKED>", ada_tiles); ks += t; }
+    ks += ";mod_in=k_modulate;qkv=";
+    if (p.bx) snprintf(t, sizeof t, "k_bx<2,%d,4>%s", g->bx_qkv.PER, p.qkv_rm() ? " rowmajor" : ""); else snprintf(t, sizeof t, "k_gemm<%d,EPI_PACKED>", split_tiles);
+    ks += t; ks += ";attn=";
+    if (p.attn_hd() == 80) snprintf(t, sizeof t, "k_attn_decode80<%d>%s", nwa, p.qkv_rm() ? " rowmajor" : ""); else snprintf(t, sizeof t, "k_attn_decode<%d,%d,1>", p.attn_hd(), nwa);
+    ks += t; ks += ";proj=";
+    if (p.bx) snprintf(t, sizeof t, "k_bx<1,%d,4>", g->bx_proj.PER); else snprintf(t, sizeof t, "k_gemm<%d,EPI_PACKED>", split_tiles);
+    ks += t;
+    if (g->rm_fused) snprintf(t, sizeof t, ";resid_attn=k_resid_mod<%d,%d,0>;resid_mlp=k_resid_mod<%d,%d,0>", p.S_proj, kpw, p.S_fc2, kpw);
+    else snprintf(t, sizeof t, ";resid_attn=k_resid_mod<%d,%d,1>+k_resid_mod<%d,%d,2>;resid_mlp=k_resid_mod<%d,%d,1>+k_resid_mod<%d,%d,2>", p.S_proj, kpw, p.S_proj, kpw,
+                  p.S_fc2, kpw, p.S_fc2, kpw);
+    ks += t; ks += ";fc1=";
+    if (p.fc1_bx()) ks += "k_bx<1,10,4,GELU,8,XF>"; else { snprintf(t, sizeof t, "k_gemm<%d,EPI_GELU>%s", fc1_tiles, p.bx ? " planes" : ""); ks += t; }
+    ks += ";fc2=";
+    if (p.bx) snprintf(t, sizeof t, "k_bx<2,%d,4>", g->bx_fc2.PER); else snprintf(t, sizeof t, "k_gemm<%d,EPI_PACKED>", split_tiles);
+    ks += t;
+    snprintf(t, sizeof t, ";head=k_gemm<%d,EPI_LOGITS>", head_tiles);
+    ks += t;
+    snprintf(k, sizeof k, "%s", ks.c_str());
+    const int n = snprintf(buf, (size_t)buf_len,
+                           "MT=%d MTc=%d bx=%d ada_bx=%d fc1_bx=%d rowmajor=%d S_qkv=%d S_proj=%d S_fc2=%d PER_qkv=%d PER_proj=%d PER_fc2=%d nch=%d nrm=%d "
+                           "kpw=%d fused=%d fallbacks=%d ada_tiles=%d fc1_tiles=%d head_tiles=%d attn_waves=%d stages=%s kernels=%s",
+                           p.MT, p.MTc, p.bx ? 1 : 0, p.ada_bx() ? 1 : 0, p.fc1_bx() ? 1 : 0, p.qkv_rm() ? 1 : 0, p.S_qkv(), p.S_proj, p.S_fc2,
+                           p.bx ? g->bx_qkv.PER : 0, p.bx ? g->bx_proj.PER : 0, p.bx ? g->bx_fc2.PER : 0, p.nch, p.rm_chunks(), kpw,
+                           g->rm_fused ? 1 : 0, g->fallbacks, ada_tiles, fc1_tiles, head_tiles, nwa, stages.c_str(), k);
+    WMAR_REQUIRE(n > 0 && n < buf_len, "rar_probe_plan: buffer of %lld bytes too small", (long long)buf_len);
+    return WMAR_OK;
 }
 
 }  // extern "C"
