@@ -1,11 +1,13 @@
-"""Tokenizer fine-tuning (reverse-cycle-consistency) for ``--model taming`` and ``--model rar`` on one MI355X: the reference's
-finetune.py flags, driving ``wmar_amd.finetune.rcc_loss`` over the native trainable tokenizer (the Taming VQGAN, or RAR's
-MaskGIT-VQGAN).  Writes ``encoder_ft_delta.pth`` and ``decoder_ft_delta.pth`` into ``--outdir`` in the form
+"""Tokenizer fine-tuning (reverse-cycle-consistency) for ``--model taming``, ``--model chameleon7b`` and ``--model rar`` on one
+MI355X: the reference's finetune.py flags, driving ``wmar_amd.finetune.rcc_loss`` over the native trainable tokenizer (the Taming
+VQGAN, Chameleon's VQGAN -- the Taming network at its own layout -- or RAR's MaskGIT-VQGAN).  Writes ``encoder_ft_delta.pth`` and ``decoder_ft_delta.pth`` into ``--outdir`` in the form
 ``generate.py --encoder_ft_ckpt / --decoder_ft_ckpt`` accept.
 
     python finetune.py --model taming --synthetic --synthetic_config harness --nb_epochs 1 --augs none --optimizer adam --lr 1e-4 \
         --batch_size_per_gpu 2 --dataset_size 4 --idempotence_loss_weight 1.0 --idempotence_loss_weight_factor 1.0 --outdir out/
     python finetune.py --model rar --synthetic --synthetic_config maskgit_small --nb_epochs 1 --augs none --batch_size_per_gpu 2 \
+        --dataset_size 4 --outdir out/
+    python finetune.py --model chameleon7b --synthetic --synthetic_config chameleon_small --nb_epochs 1 --augs none --batch_size_per_gpu 2 \
         --dataset_size 4 --outdir out/
 
 ``--lpips_vgg PATH --lpips_lin PATH`` (torchvision's VGG16 state dict and the reference's ``vgg.pth``) add the reference's perceptual
@@ -14,10 +16,22 @@ draws random LPIPS weights for a ``--synthetic`` run.  Without them the regulari
 tokenizer's resolution, which must be a multiple of 128.
 
 ``--synthetic_config`` names are bound to models: ``harness`` / ``harness128`` / ``taming`` are Taming shapes, ``maskgit_small`` / ``maskgit`` are
-MaskGIT shapes for ``--model rar``; ``--model rar --modelpath DIR`` loads ``RarARMMWrapper(DIR)``.
+MaskGIT shapes for ``--model rar``, ``chameleon_small`` / ``chameleon`` are Chameleon shapes (five levels, no level attention; 128 x 128
+and the real 512 x 512); ``--model rar --modelpath DIR`` loads ``RarARMMWrapper(DIR)``, ``--model chameleon7b --modelpath DIR``
+``ChameleonARMMWrapper(DIR)``.  The codes of ``--datapath`` are the tokenizer's own code ids ``0 .. n_embed - 1`` (for Chameleon: not
+vocabulary ids); ``precompute_codes.py`` writes such a file from a directory of images.
 
-Not built here, each rejected with a message: multi-GPU training (DDP), tensorboard logging, the validation pass, and the
-``chameleon7b`` model."""
+``--val_percent F`` (0 <= F < 1, default 0: no validation; the reference hard-codes 0.05) keeps the last ``n - int(n * (1 - F))`` rows,
+in file order after ``--dataset_size``, for validation (finetune.py:73-128, 388-391, 509-514): before every epoch and once after
+training ends, the loss without gradients for "no augmentation" and for every (transform, parameter) of the epoch's curriculum, one
+JSON line each with ``"split": "val"``, the share of codes that change (``l0``), and one line with the mean L2 distance of the
+encoder's and the decoder's tensors from the originals (``enc_l2`` / ``dec_l2``).  Validation draws from no generator training sees:
+the deltas are bit-identical to those of a run on the same training rows without it.
+
+The original decoder of the regulariser and every no-grad forward run on forward-only engine handles (no tape, no gradient memory).
+
+Not built here, each rejected with a message: multi-GPU training (DDP), tensorboard logging, and the reference's ``--validate``
+switch (use ``--val_percent``)."""
 from __future__ import annotations
 
 import argparse
@@ -33,7 +47,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--modelpath", type=str, help="taming: directory with configs/net2net.yaml and checkpoints/net2net.ckpt; "
                                                  "rar: directory with maskgit-vqgan-imagenet-f16-256.bin and rar_xl.bin")
     p.add_argument("--synthetic", action="store_true", help="random-init weights instead of --modelpath")
-    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "harness128", "taming", "maskgit_small", "maskgit"])
+    p.add_argument("--synthetic_config", type=str, default="harness", choices=["harness", "harness128", "taming", "maskgit_small", "maskgit", "chameleon_small", "chameleon"])
     p.add_argument("--datapath", type=str, help="int64 [N, S*S] codes, .pt or .npy (with --synthetic: random codes when absent)")
     p.add_argument("--dataset_size", type=int, help="number of rows to use")
     p.add_argument("--mode", type=str, default="newenc-dec")
@@ -52,6 +66,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--local_rank", "--local-rank", type=int, default=-1)
     p.add_argument("--tensorboard", action="store_true")
     p.add_argument("--validate", action="store_true")
+    p.add_argument("--val_percent", type=float, default=0.0, help="share of the rows (the last ones, in file order) kept for the validation "
+                                                                  "pass; 0: no validation (the reference hard-codes 0.05)")
     p.add_argument("--lpips_vgg", type=str, help="torchvision's VGG16 state dict (features.N.weight / .bias): with --lpips_lin, adds the "
                                                  "reference's LPIPS term to the regulariser")
     p.add_argument("--lpips_lin", type=str, help="the reference's vgg.pth (the lin layers of LPIPS)")
@@ -61,9 +77,15 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 # the synthetic shapes each trainable model takes (harness128: the harness shape at 128 x 128, the smallest LPIPS takes)
-SYNTHETIC_CONFIGS = {"taming": ("harness128", "harness", "taming"), "rar": ("maskgit_small", "maskgit")}
+SYNTHETIC_CONFIGS = {"taming": ("harness128", "harness", "taming"), "rar": ("maskgit_small", "maskgit"),
+                     "chameleon7b": ("chameleon_small", "chameleon")}
 # resolution of each synthetic shape
-SYNTHETIC_RESOLUTION = {"harness": 32, "harness128": 128, "taming": 256, "maskgit_small": 32, "maskgit": 256}
+SYNTHETIC_RESOLUTION = {"harness": 32, "harness128": 128, "taming": 256, "maskgit_small": 32, "maskgit": 256, "chameleon_small": 128,
+                        "chameleon": 512}
+# chameleon_small keeps Chameleon's layout -- five levels, two neighbouring levels of equal width (a downsample behind blocks without a
+# shortcut), no level attention, a mid attention (64 tokens) -- at 128 x 128, a resolution LPIPS takes, with an 8 x 8 code grid
+CHAMELEON_SMALL_VQ = dict(ch=32, ch_mult=(1, 1, 2, 2, 4), num_res_blocks=2, attn_resolutions=(), resolution=128, z_channels=32, embed_dim=32,
+                          n_embed=512)
 
 
 def wants_lpips(args) -> bool:
@@ -73,16 +95,18 @@ def wants_lpips(args) -> bool:
 def check_args(args) -> None:
     """Everything this CLI does not implement is refused here, before any model is built."""
     if args.model not in SYNTHETIC_CONFIGS:
-        raise SystemExit(f"finetune.py: --model {args.model} is not built: only the Taming and the RAR tokenizers have a training engine")
+        raise SystemExit(f"finetune.py: --model {args.model} is not built")
     if args.synthetic and args.synthetic_config not in SYNTHETIC_CONFIGS[args.model]:
-        raise SystemExit(f"finetune.py: --synthetic_config {args.synthetic_config} is not a shape of --model {args.model}: "
-                         f"choose from {', '.join(SYNTHETIC_CONFIGS[args.model])}")
+        raise SystemExit(f"finetune.py: --synthetic_config {args.synthetic_config} with --model {args.model} is not built: "
+                         f"the shapes of that model are {', '.join(SYNTHETIC_CONFIGS[args.model])}")
     if args.local_rank != -1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("finetune.py: multi-GPU training (DDP) is not built: run one process on one GPU")
     if args.tensorboard:
         raise SystemExit("finetune.py: tensorboard logging is not built: the log lines go to stdout as JSON")
     if args.validate:
-        raise SystemExit("finetune.py: the validation pass is not built")
+        raise SystemExit("finetune.py: --validate is not built: the validation pass runs with --val_percent F (the reference's share is 0.05)")
+    if not 0.0 <= getattr(args, "val_percent", 0.0) < 1.0:
+        raise SystemExit(f"finetune.py: --val_percent {args.val_percent} outside [0, 1)")
     if args.mode != "newenc-dec":
         raise SystemExit(f"finetune.py: --mode {args.mode} not supported (newenc-dec)")
     if args.loss != "hard-to-soft-with-ae":
@@ -113,14 +137,45 @@ def load_codes(path: str):
     return codes
 
 
-def train(tok, orig, codes, args, log=print, rec_loss=None):
+def split_rows(n: int, val_percent: float):
+    """(n_train, n_val) of ``--val_percent``: the first ``int(n * (1 - F))`` rows train, the rest validate; an empty half is refused."""
+    if not val_percent:
+        return n, 0
+    n_train = int(n * (1 - val_percent))
+    if n_train < 1 or n_train >= n:
+        raise SystemExit(f"finetune.py: --val_percent {val_percent} of {n} rows leaves {n_train} to train on and {n - n_train} to validate on: "
+                         f"both halves need at least one row")
+    return n_train, n - n_train
+
+
+def run_validation(tok, orig, val_codes, entries, epoch, weight, args, original, log, rec_loss):
+    """One validation pass (wmar_amd.finetune.validate) as JSON lines: a record per (transform, parameter), then the weight distances."""
+    from wmar_amd.finetune import validate, weight_distance
+    for rec in validate(tok, orig, val_codes, entries, args.batch_size_per_gpu, weight, rec_loss=rec_loss):
+        log(json.dumps(dict(rec, split="val", epoch=epoch)))
+    if original is not None:
+        log(json.dumps({"split": "val", "epoch": epoch, "enc_l2": weight_distance(tok.state, original, "encoder."),
+                        "dec_l2": weight_distance(tok.state, original, "decoder.")}))
+
+
+def train(tok, orig, codes, args, log=print, rec_loss=None, val_codes=None, original=None):
     """Adam (0.9, 0.999) + StepLR(gamma 0.9 per epoch) over the encoder's and the decoder's weights; the idempotence weight is multiplied
-    by its factor after every epoch.  ``rec_loss``: the regulariser of ``rcc_loss`` (None: L1 only).  Returns the number of optimizer
-    steps."""
-    import torch
+    by its factor after every epoch.  ``rec_loss``: the regulariser of ``rcc_loss`` (None: L1 only).  ``val_codes``: rows for the
+    validation pass, run before every epoch with that epoch's curriculum and the current idempotence weight, and once after training
+    ends for any reason with ``epoch = nb_epochs`` and the last epoch's entries (finetune.py:388-391, 509-514); ``original``: the
+    state the weight distances are taken from.  Returns the number of optimizer steps."""
     from wmar_amd.augmentations import finetune_schedule
-    from wmar_amd.finetune import calculate_gradient_norm, rcc_loss
     schedule = finetune_schedule(args.augs, args.augs_schedule, args.nb_epochs)
+    steps, weight = _train(tok, orig, codes, args, log, rec_loss, val_codes, original, schedule)
+    if val_codes is not None:
+        run_validation(tok, orig, val_codes, schedule[args.nb_epochs - 1], args.nb_epochs, weight, args, original, log, rec_loss)
+    return steps
+
+
+def _train(tok, orig, codes, args, log, rec_loss, val_codes, original, schedule):
+    """The loop of ``train``; returns (optimizer steps, the idempotence weight it ended with)."""
+    import torch
+    from wmar_amd.finetune import calculate_gradient_norm, rcc_loss
     for k, prm in tok.named_parameters():
         prm.requires_grad_(k.startswith(("encoder.", "decoder.")))          # the 1x1 quant convolutions stay as they are
     params = list(tok.parameters(("encoder.", "decoder.")))
@@ -129,6 +184,8 @@ def train(tok, orig, codes, args, log=print, rec_loss=None):
     weight, steps, bs = args.idempotence_loss_weight, 0, args.batch_size_per_gpu
     gen = torch.Generator().manual_seed(args.seed)
     for epoch in range(args.nb_epochs):
+        if val_codes is not None:
+            run_validation(tok, orig, val_codes, schedule[epoch], epoch, weight, args, original, log, rec_loss)
         order = torch.randperm(codes.shape[0], generator=gen)
         for b0 in range(0, codes.shape[0], bs):
             batch = codes[order[b0:b0 + bs]]
@@ -141,10 +198,10 @@ def train(tok, orig, codes, args, log=print, rec_loss=None):
             steps += 1
             log(json.dumps(log_dict))
             if args.max_steps is not None and steps >= args.max_steps:
-                return steps
+                return steps, weight
         sched.step()
         weight *= args.idempotence_loss_weight_factor
-    return steps
+    return steps, weight
 
 
 def synthetic_rar_configs(name: str):
@@ -156,6 +213,16 @@ def synthetic_rar_configs(name: str):
     r = synth.RARConfig(hidden_size=128, num_hidden_layers=2, num_attention_heads=4, intermediate_size=512, image_seq_len=v.codes_size ** 2,
                         codebook_size=v.num_embeddings)
     return r, v
+
+
+def synthetic_chameleon_configs(name: str):
+    """(ChameleonConfig, VQConfig) of a ``--synthetic_config`` of ``--model chameleon7b``.  The transformer is not trained: a small one
+    whose vocabulary holds the tokenizer's codes."""
+    from wmar_amd.utils import synth
+    v = synth.VQConfig(**CHAMELEON_SMALL_VQ) if name == "chameleon_small" else synth.CHAMELEON_VQ
+    c = synth.ChameleonConfig(dim=256, n_layers=2, n_heads=4, n_kv_heads=4, vocab_size=max(1024, 2 * v.n_embed), multiple_of=64,
+                              qk_normalization=True)
+    return c, v
 
 
 def load_model(args):
@@ -171,6 +238,14 @@ def load_model(args):
         else:
             model = RarARMMWrapper(args.modelpath, max_batch=mb)
         return model, model._vq_cfg, model._vq_cfg.num_embeddings, tt.MaskgitTrainableTokenizer
+    if args.model == "chameleon7b":
+        from wmar_amd.models.chameleon_wrapper import ChameleonARMMWrapper
+        if args.synthetic:
+            c, v = synthetic_chameleon_configs(args.synthetic_config)
+            model = ChameleonARMMWrapper.synthetic(c, v, seed=args.seed, max_batch=mb)
+        else:
+            model = ChameleonARMMWrapper(args.modelpath, max_batch=mb)
+        return model, model._vq_cfg, model._vq_cfg.n_embed, tt.TrainableTokenizer
     from wmar_amd.models.taming_wrapper import TamingARMMWrapper
     if args.synthetic:
         if args.synthetic_config == "harness":
@@ -216,19 +291,20 @@ def main(argv=None) -> int:
         codes = codes[:args.dataset_size]
     if codes.shape[1] != vcfg.codes_size ** 2:
         raise SystemExit(f"finetune.py: codes have {codes.shape[1]} columns, the tokenizer has {vcfg.codes_size ** 2}")
+    n_train, n_val = split_rows(codes.shape[0], args.val_percent)
     codes = codes.to(model.model.device)
+    codes, val_codes = codes[:n_train], (codes[n_train:] if n_val else None)
     tokenizer = model.get_image_tokenizer()
     original = {k: v.detach().clone() for k, v in tokenizer.state_dict().items()}
-    orig = tok_class(vcfg, {k: v.clone() for k, v in original.items()}, max_batch=args.batch_size_per_gpu, device=model.model.device)
-    for prm in orig.parameters():
-        prm.requires_grad_(False)
+    # the original decoder: forward only, on a handle without tape or gradient memory
+    orig = tok_class(vcfg, {k: v.clone() for k, v in original.items()}, max_batch=args.batch_size_per_gpu, device=model.model.device, frozen=True)
     tok = model.trainable_tokenizer(max_batch=args.batch_size_per_gpu)
     lpips = load_lpips(args, vcfg.resolution, model.model.device)
     rec_loss = None
     if lpips is not None:
         from wmar_amd.finetune import reference_rec_loss
         rec_loss = reference_rec_loss(lpips, args.perceptual_weight)
-    steps = train(tok, orig, codes, args, rec_loss=rec_loss)
+    steps = train(tok, orig, codes, args, rec_loss=rec_loss, val_codes=val_codes, original=original)
     os.makedirs(args.outdir, exist_ok=True)
     for name in ("encoder", "decoder"):
         handle = getattr(tokenizer, name)

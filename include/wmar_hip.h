@@ -709,6 +709,18 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 int wmar_mvq_train_create(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
                           wmar_vq_train** out);
 
+/* Forward-only handles: the arguments of wmar_vq_train_create / wmar_mvq_train_create, a wmar_vq_train that serves
+ * wmar_vq_train_encode, _decode, _set_weights, _device_bytes and _destroy.  The activations live in the plan's rotating and attention
+ * slot buffers, as the inference engines' do; there is no per-tensor tape, no gradient slot, no weight-gradient buffer, no flipped or
+ * dgrad weight pack, no backward scratch and no softmax tape.  The forward is the same executor on the same packed weights, so its
+ * outputs are bit-equal to the taped handle's and to wmar_vq_* / wmar_mvq_*.  wmar_vq_train_encode_backward, _decode_backward and
+ * _get_grads on such a handle return WMAR_EINVAL ("... a frozen handle ...") and leave it usable.  What a no-grad forward and the
+ * original decoder of the fine-tuning loss run on. */
+int wmar_vq_train_create_frozen(const wmar_vq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors,
+                                void* stream, wmar_vq_train** out);
+int wmar_mvq_train_create_frozen(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors,
+                                 void* stream, wmar_vq_train** out);
+
 /* ------------------------------------------------------------------------ LPIPS (wmar_amd/csrc/lpips.h)
  * The perceptual term of the tokenizer fine-tuning loss (deps/taming/modules/losses/lpips.py:41-122 in .eval()): a frozen VGG16
  * features[0:30] on two images, per-pixel normalised at five taps, the squared differences weighted by the lin layers, averaged over
@@ -820,6 +832,19 @@ typedef struct wmar_image_desc {
  * (the whitening table is uploaded when it is allocated); the call waits for its launches, and calls on one device take turns. */
 int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n, int32_t target,
                       float* out_dev, uint8_t* out_u8_dev, void* stream);
+
+/* The two entries above with the resampling filter as an argument (Pillow's numbers, Image.Resampling).  BILINEAR is Pillow's triangle
+ * filter 1 - |x| on |x| < 1 with support 1 (src/libImaging/Resample.c, bilinear_filter): what torchvision's Resize(interpolation =
+ * BILINEAR) applies to a PIL image, as the reference's precompute_imagenet_codes.py does.  Everything else -- the stretch by
+ * max(in / out, 1), the normalisation, the 22-bit rounding, the two integer passes, the unfiltered unchanged axis -- is shared, so
+ * wmar_resample_coeffs(...) == wmar_resample_coeffs_filtered(..., WMAR_RESAMPLE_LANCZOS) and likewise for the ingest.  Any other
+ * filter value is WMAR_EINVAL before anything is computed. */
+#define WMAR_RESAMPLE_LANCZOS 1
+#define WMAR_RESAMPLE_BILINEAR 2
+int wmar_resample_coeffs_filtered(int32_t in_size, int32_t out_size, int32_t out0, int32_t n_out, int32_t* xmin_out, int32_t* count_out,
+                                  int32_t* k_out, int32_t k_capacity, int32_t* ksize_out, int32_t filter);
+int wmar_image_ingest_filtered(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n, int32_t target,
+                               float* out_dev, uint8_t* out_u8_dev, int32_t filter, void* stream);
 
 /* ------------------------------------------------------------------------ synchronisation layer (WAM geometry fit)
  * wmar/watermarking/synchronization.py: the device half of WamSync.remove_sync.  All tensors contiguous; images and label maps are

@@ -32,11 +32,13 @@ SYMBOLS = [
     "wmar_rar_probe_run", "wmar_rar_probe_copy", "wmar_rar_probe_plan",
     "wmar_cfg_mix", "wmar_gpt_generate_hooked", "wmar_rar_generate_hooked", "wmar_cham_generate_image_hooked",
     "wmar_augment", "wmar_augment_backward", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
+    "wmar_resample_coeffs_filtered", "wmar_image_ingest_filtered", "wmar_vq_train_create_frozen", "wmar_mvq_train_create_frozen",
     "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
 
 WMAR_ESHORT = -3
+RESAMPLE_LANCZOS, RESAMPLE_BILINEAR = 1, 2      # WMAR_RESAMPLE_* (Pillow's numbers)
 WMAR_ECALLBACK = -6
 
 # wmar_logits_hook (include/wmar_hip.h): int (*)(void* user, int32_t step, int64_t t)
@@ -148,6 +150,8 @@ def load():
     L.wmar_jpeg.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp]
     L.wmar_resample_coeffs.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, C.POINTER(i32)]
     L.wmar_image_ingest.argtypes = [vp, i64, C.POINTER(ImageDesc), i64, i32, vp, vp, vp]
+    L.wmar_resample_coeffs_filtered.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, C.POINTER(i32), i32]
+    L.wmar_image_ingest_filtered.argtypes = [vp, i64, C.POINTER(ImageDesc), i64, i32, vp, vp, i32, vp]
     L.wmar_sync_positions.argtypes = [vp, i64, i32, vp, vp, vp]
     L.wmar_sync_workspace_bytes.restype = i64
     L.wmar_sync_workspace_bytes.argtypes = [i64, i32]
@@ -219,6 +223,8 @@ def load():
         L.wmar_mvq_probe_input_backward.argtypes = [vp, i64, i32, i32, i32, vp, vp]
         L.wmar_mvq_train_create.argtypes = [C.POINTER(MvqConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
         L.wmar_vq_train_create.argtypes = [C.POINTER(VqConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
+        L.wmar_mvq_train_create_frozen.argtypes = L.wmar_mvq_train_create.argtypes
+        L.wmar_vq_train_create_frozen.argtypes = L.wmar_vq_train_create.argtypes
         L.wmar_vq_train_destroy.argtypes = [vp]
         L.wmar_vq_train_destroy.restype = None
         L.wmar_vq_train_device_bytes.restype = i64

@@ -11,6 +11,9 @@
 //                                clip(((1 << 21) + sum pixel * weight) >> 22, 0, 255) in int32; the horizontal pass writes an 8-bit
 //                                image and the vertical pass reads it: the rounding in between is part of the result
 //   ImagingResample              an axis whose size does not change is not filtered
+// The filter is an argument of the *_filtered entries (Pillow's numbers): BILINEAR swaps the weight function for the triangle 1 - |x|
+// and the support 3 for 1 (what torchvision's Resize applies to a PIL image; precompute_codes.py) and shares every other step -- the
+// kernels only see tables, and take any tap count from 1 up.
 // The tables are built on the host in double (wmar_resample_coeffs, below) and uploaded; the kernels do the integer work.  The
 // whitening (uint8)((1 - a / 255.0) * 255 + (a / 255.0) * c) in float64 is a 64 KB table built on the host, applied while the
 // input row sits in LDS; the exit (float)((double)u / 255.0 * 2.0 - 1.0) is a compile-time table.
@@ -177,15 +180,26 @@ double ingest_sinc(double x) {
 
 double ingest_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? ingest_sinc(x) * ingest_sinc(x / 3.0) : 0.0; }
 
-int ingest_ksize(int in_size, int out_size) {
+// Pillow's bilinear_filter (Resample.c): the triangle 1 - |x| on |x| < 1
+double ingest_bilinear(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+bool ingest_filter_ok(int filter) { return filter == WMAR_RESAMPLE_LANCZOS || filter == WMAR_RESAMPLE_BILINEAR; }
+// the filter's support (Resample.c: LANCZOS 3.0, BILINEAR 1.0)
+double ingest_support(int filter) { return filter == WMAR_RESAMPLE_BILINEAR ? 1.0 : 3.0; }
+
+int ingest_ksize(int in_size, int out_size, int filter) {
     const double scale = (double)in_size / (double)out_size, filterscale = scale < 1.0 ? 1.0 : scale;
-    return (int)std::ceil(3.0 * filterscale) * 2 + 1;
+    return (int)std::ceil(ingest_support(filter) * filterscale) * 2 + 1;
 }
 
 // Tables of one axis for the outputs [out0, out0 + n_out); k row-major [n_out][ksize], zero beyond a row's count
-void ingest_coeffs(int in_size, int out_size, int out0, int n_out, int32_t* xmin_out, int32_t* count_out, int32_t* k_out, int ksize) {
+void ingest_coeffs(int in_size, int out_size, int out0, int n_out, int32_t* xmin_out, int32_t* count_out, int32_t* k_out, int ksize,
+                   int filter) {
     const double scale = (double)in_size / (double)out_size, filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 3.0 * filterscale, ss = 1.0 / filterscale;      // the tap position is multiplied by the reciprocal
+    const double support = ingest_support(filter) * filterscale, ss = 1.0 / filterscale;      // the tap position is multiplied by the reciprocal
     std::vector<double> w((size_t)ksize);
     for (int i = 0; i < n_out; ++i) {
         const double center = ((double)(out0 + i) + 0.5) * scale;
@@ -196,7 +210,8 @@ void ingest_coeffs(int in_size, int out_size, int out0, int n_out, int32_t* xmin
         const int count = xmax - xmin;
         double ww = 0.0;
         for (int x = 0; x < count; ++x) {
-            w[x] = ingest_lanczos(((double)(x + xmin) - center + 0.5) * ss);
+            const double at = ((double)(x + xmin) - center + 0.5) * ss;
+            w[x] = filter == WMAR_RESAMPLE_BILINEAR ? ingest_bilinear(at) : ingest_lanczos(at);
             ww += w[x];
         }
         int32_t* k = k_out + (size_t)i * ksize;
@@ -234,7 +249,7 @@ std::map<int, IngestScratch> ingest_scratch;
 
 // Appends one axis' device tables to the pool: xmin [T] (`rebase`: relative to the first one), count [T], weights [ksize][T].  An unchanged axis becomes
 // the identity (one tap of weight 1.0, which the fixed-point arithmetic reproduces exactly): Pillow does not filter it.
-void ingest_axis(std::vector<int32_t>& pool, int in_size, int out_size, int out0, int T, bool rebase, int* off, int* ksize_out,
+void ingest_axis(std::vector<int32_t>& pool, int in_size, int out_size, int out0, int T, bool rebase, int filter, int* off, int* ksize_out,
                  int* first, int* end) {
     *off = (int)pool.size();
     if (in_size == out_size) {
@@ -248,11 +263,11 @@ void ingest_axis(std::vector<int32_t>& pool, int in_size, int out_size, int out0
             for (int i = 0; i < T; ++i) p[i] -= out0;
         return;
     }
-    const int ksize = ingest_ksize(in_size, out_size);
+    const int ksize = ingest_ksize(in_size, out_size, filter);
     std::vector<int32_t> k((size_t)T * ksize);
     pool.resize(pool.size() + (size_t)T * (2 + ksize));
     int32_t* p = pool.data() + *off;
-    ingest_coeffs(in_size, out_size, out0, T, p, p + T, k.data(), ksize);
+    ingest_coeffs(in_size, out_size, out0, T, p, p + T, k.data(), ksize, filter);
     for (int i = 0; i < T; ++i)
         for (int j = 0; j < ksize; ++j) p[2 * T + (size_t)j * T + i] = k[(size_t)i * ksize + j];
     *ksize_out = ksize;
@@ -267,24 +282,31 @@ void ingest_axis(std::vector<int32_t>& pool, int in_size, int out_size, int out0
 
 using namespace wmar;
 
-extern "C" int wmar_resample_coeffs(int32_t in_size, int32_t out_size, int32_t out0, int32_t n_out, int32_t* xmin_out,
-                                    int32_t* count_out, int32_t* k_out, int32_t k_capacity, int32_t* ksize_out) {
+extern "C" int wmar_resample_coeffs_filtered(int32_t in_size, int32_t out_size, int32_t out0, int32_t n_out, int32_t* xmin_out,
+                                             int32_t* count_out, int32_t* k_out, int32_t k_capacity, int32_t* ksize_out, int32_t filter) {
+    WMAR_REQUIRE(ingest_filter_ok(filter), "resample_coeffs: filter %d (1 = LANCZOS, 2 = BILINEAR)", filter);
     WMAR_REQUIRE(in_size >= 1 && out_size >= 1, "resample_coeffs: sizes %d -> %d (both must be positive)", in_size, out_size);
     WMAR_REQUIRE(in_size <= INGEST_MAX_SIDE && out_size <= (1 << 30), "resample_coeffs: sizes %d -> %d beyond %d -> 2^30", in_size,
                  out_size, INGEST_MAX_SIDE);
     WMAR_REQUIRE(out0 >= 0 && n_out >= 1 && (long long)out0 + n_out <= out_size, "resample_coeffs: window [%d, %d + %d) outside %d outputs",
                  out0, out0, n_out, out_size);
     WMAR_REQUIRE(xmin_out && count_out && k_out && ksize_out, "resample_coeffs: null output");
-    const int ksize = ingest_ksize(in_size, out_size);
+    const int ksize = ingest_ksize(in_size, out_size, filter);
     WMAR_REQUIRE((long long)n_out * ksize <= k_capacity, "resample_coeffs: %lld coefficients, capacity %d", (long long)n_out * ksize,
                  k_capacity);
-    ingest_coeffs(in_size, out_size, out0, n_out, xmin_out, count_out, k_out, ksize);
+    ingest_coeffs(in_size, out_size, out0, n_out, xmin_out, count_out, k_out, ksize, filter);
     *ksize_out = ksize;
     return WMAR_OK;
 }
 
-extern "C" int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n,
-                                 int32_t target, float* out_dev, uint8_t* out_u8_dev, void* stream) {
+extern "C" int wmar_resample_coeffs(int32_t in_size, int32_t out_size, int32_t out0, int32_t n_out, int32_t* xmin_out,
+                                    int32_t* count_out, int32_t* k_out, int32_t k_capacity, int32_t* ksize_out) {
+    return wmar_resample_coeffs_filtered(in_size, out_size, out0, n_out, xmin_out, count_out, k_out, k_capacity, ksize_out, WMAR_RESAMPLE_LANCZOS);
+}
+
+extern "C" int wmar_image_ingest_filtered(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n,
+                                          int32_t target, float* out_dev, uint8_t* out_u8_dev, int32_t filter, void* stream) {
+    WMAR_REQUIRE(ingest_filter_ok(filter), "image_ingest: filter %d (1 = LANCZOS, 2 = BILINEAR)", filter);
     WMAR_REQUIRE(pixels_dev && desc_host && out_dev && pixels_bytes >= 1, "image_ingest: bad argument");
     WMAR_REQUIRE(n >= 1 && n <= 65535, "image_ingest: %lld images (1..65535 per call)", (long long)n);
     WMAR_REQUIRE(target >= 1 && target <= INGEST_MAX_SIDE, "image_ingest: target %d (1..%d)", target, INGEST_MAX_SIDE);
@@ -310,7 +332,7 @@ extern "C" int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes
         WMAR_REQUIRE(s.crop_x0 >= 0 && s.crop_y0 >= 0 && (long long)s.crop_x0 + T <= s.new_width && (long long)s.crop_y0 + T <= s.new_height,
                      "image_ingest: image %lld: crop window %d x %d at (%d, %d) outside the %d x %d resized image", (long long)i, T, T,
                      s.crop_x0, s.crop_y0, s.new_width, s.new_height);
-        WMAR_REQUIRE((long long)T * (2 + ingest_ksize(s.width, s.new_width)) + (long long)T * (2 + ingest_ksize(s.height, s.new_height)) +
+        WMAR_REQUIRE((long long)T * (2 + ingest_ksize(s.width, s.new_width, filter)) + (long long)T * (2 + ingest_ksize(s.height, s.new_height, filter)) +
                              (long long)pool.size() < (1LL << 30),
                      "image_ingest: coefficient tables of the batch too large");
         IngestImage& d = images[(size_t)i];
@@ -323,7 +345,7 @@ extern "C" int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes
             auto it = axes.find(key);
             if (it == axes.end()) {
                 int off, ks;
-                ingest_axis(pool, std::get<1>(key), std::get<2>(key), std::get<3>(key), T, axis == 1, &off, &ks, &first, &end);
+                ingest_axis(pool, std::get<1>(key), std::get<2>(key), std::get<3>(key), T, axis == 1, filter, &off, &ks, &first, &end);
                 it = axes.emplace(key, std::make_tuple(off, ks, first, end)).first;
             }
             if (axis == 0) { d.h_off = std::get<0>(it->second); d.h_ksize = std::get<1>(it->second); }
@@ -383,4 +405,9 @@ extern "C" int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes
         rc = WMAR_EHIP;
     }
     return rc;
+}
+
+extern "C" int wmar_image_ingest(const uint8_t* pixels_dev, int64_t pixels_bytes, const wmar_image_desc* desc_host, int64_t n,
+                                 int32_t target, float* out_dev, uint8_t* out_u8_dev, void* stream) {
+    return wmar_image_ingest_filtered(pixels_dev, pixels_bytes, desc_host, n, target, out_dev, out_u8_dev, WMAR_RESAMPLE_LANCZOS, stream);
 }

@@ -14,6 +14,11 @@
 // the norm's backward then runs once.  All memory is allocated at create time for max_batch images.
 //
 // For the MaskGIT-VQGAN plan the [-1, 1] <-> [0, 1] range change and the clamp are differentiated at the image edges.
+//
+// A FROZEN handle (wmar_vq_train_create_frozen / wmar_mvq_train_create_frozen) is the forward alone: the same packed weights and the same
+// executor, with the tensors in the plan's slot buffers as the inference engines have them (tensor i at slot[p.t[i].slot]) and no tape
+// passed -- nothing of the backward is allocated, and the backward entries refuse the handle.  set_weights repacks from the caller's
+// tensors directly.
 #pragma once
 
 namespace wmar {
@@ -91,6 +96,7 @@ struct wmar_vq_train {
     double* gnb = nullptr;
     float *ybuf = nullptr, *ngy = nullptr, *gtmp = nullptr, *ups = nullptr, *ws = nullptr, *dp = nullptr, *tr = nullptr;
     bool ngy_set = false;
+    bool frozen = false;                // forward only: t[i].d are slot buffers, t[i].g and everything the backward reads are null
 };
 
 namespace {
@@ -112,6 +118,10 @@ int repack_conv(const VqConvDesc& d, ConvW& fw, TConv& c, const float* W, const 
         }
     };
     const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks;
+    if (!c.w) {                                         // a frozen handle keeps no raw copy and no dgrad pack
+        pack(fw, W, d.cin, d.cout, bias);
+        return launch_status("repack_conv");
+    }
     WMAR_HIP_CHECK(hipMemcpyAsync(c.w, W, nw * 4, hipMemcpyDeviceToDevice, st));
     pack(fw, c.w, d.cin, d.cout, bias);
     if (d.stride == 1) {
@@ -124,7 +134,7 @@ int repack_conv(const VqConvDesc& d, ConvW& fw, TConv& c, const float* W, const 
 // A plan as a training handle: the weights, the tape (every tensor's value and gradient, every norm's statistics, every attention's
 // softmax), what the backward needs of every conv and norm, and the backward's scratch sized by the largest layer.
 int train_create(VqPlan plan, const char* who, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
-                 wmar_vq_train** out) {
+                 wmar_vq_train** out, bool frozen = false) {
     WMAR_REQUIRE(names && tensors_dev && out, "%s: null argument", who);
     WMAR_REQUIRE(plan.err.empty(), "%s", plan.err.c_str());
     std::unique_ptr<wmar_vq_train> e(new wmar_vq_train());
@@ -135,6 +145,25 @@ int train_create(VqPlan plan, const char* who, const char* const* names, const v
     Loader ld(names, tensors_dev, n_tensors, &e->mem, st);
     int& rc = ld.rc;
     net_load(e->net, ld);
+    e->frozen = frozen;
+    if (frozen) {                       // one buffer per slot, as large as the largest tensor the plan puts there (engine_create, vqgan.hip)
+        float* slot[VQ_SLOTS] = {};
+        for (int s = 0; s < VQ_SLOTS; ++s)
+            if (s < 4 || p.att_elems) WMAR_TRY(e->mem.alloc(&slot[s], (size_t)Bmax * (s < 4 ? p.rot_elems : p.att_elems)));
+        for (const VqTensor& pt : p.t) {
+            TTensor tt; static_cast<VqTensor&>(tt) = pt;
+            tt.d = slot[pt.slot];
+            e->t.push_back(tt);
+            e->net.at.push_back(tt.d);
+        }
+        e->norms.resize(p.norms.size()); e->convs.resize(p.convs.size());
+        if (p.attn_nn) WMAR_TRY(e->mem.alloc(&e->net.att.asc, (size_t)Bmax * p.attn_nn));
+        net_scratch(e->net, e->mem, rc, st);
+        if (rc == WMAR_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("%s: sync failed", who); rc = WMAR_EHIP; }
+        if (rc != WMAR_OK) return rc;
+        *out = e.release();
+        return WMAR_OK;
+    }
     for (const VqTensor& pt : p.t) {
         TTensor tt; static_cast<VqTensor&>(tt) = pt;
         WMAR_TRY(e->mem.alloc(&tt.d, tt.elems(Bmax)));
@@ -311,6 +340,18 @@ int wmar_mvq_train_create(const wmar_mvq_config* cfg, const char* const* names, 
     return train_create(plan_mvq(*cfg, "mvq_train_create"), "mvq_train_create", names, tensors_dev, n_tensors, stream, out);
 }
 
+int wmar_vq_train_create_frozen(const wmar_vq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors,
+                                void* stream, wmar_vq_train** out) {
+    WMAR_REQUIRE(cfg, "vq_train_create_frozen: null argument");
+    return train_create(plan_taming(*cfg, "vq_train_create_frozen"), "vq_train_create_frozen", names, tensors_dev, n_tensors, stream, out, true);
+}
+
+int wmar_mvq_train_create_frozen(const wmar_mvq_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors,
+                                 void* stream, wmar_vq_train** out) {
+    WMAR_REQUIRE(cfg, "mvq_train_create_frozen: null argument");
+    return train_create(plan_mvq(*cfg, "mvq_train_create_frozen"), "mvq_train_create_frozen", names, tensors_dev, n_tensors, stream, out, true);
+}
+
 void wmar_vq_train_destroy(wmar_vq_train* e) { delete e; }
 int64_t wmar_vq_train_device_bytes(const wmar_vq_train* e) { return e ? e->mem.bytes : 0; }
 
@@ -348,15 +389,16 @@ int wmar_vq_train_encode(wmar_vq_train* e, const float* images_dev, int64_t B, f
     hipLaunchKernelGGL(p.unit_range ? k_nchw_to_nhwc01 : k_nchw_to_nhwc, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, images_dev, x0.d,
                        p.in_channels, HW, x0.C);
     if (int rc = launch_status("k_nchw_to_nhwc")) return rc;
-    if (int rc = vq_forward(e->net, p.half[0], (int)B, st, &e->tape)) return rc;
+    if (int rc = vq_forward(e->net, p.half[0], (int)B, st, e->frozen ? nullptr : &e->tape)) return rc;
     const TTensor& zo = e->t[p.half[0].last];
     WMAR_HIP_CHECK(hipMemcpyAsync(prequant_dev, zo.d, zo.elems((int)B) * 4, hipMemcpyDeviceToDevice, st));
-    s.tape = true; s.B = (int)B;
+    s.tape = !e->frozen; s.B = (int)B;
     return WMAR_OK;
 }
 
 int wmar_vq_train_encode_backward(wmar_vq_train* e, const float* grad_prequant_dev, int64_t B, float* grad_images_dev, void* stream) {
     WMAR_REQUIRE(e && grad_prequant_dev, "vq_train_encode_backward: null argument");
+    WMAR_REQUIRE(!e->frozen, "vq_train_encode_backward: a frozen handle has no tape and no gradients (wmar_vq_train_create_frozen)");
     const VqPlan& p = e->net.plan;
     const VqHalf& h = p.half[0];
     THalf& s = e->half[0];
@@ -393,18 +435,19 @@ int wmar_vq_train_decode(wmar_vq_train* e, const float* zq_dev, int64_t B, float
     s.tape = false; s.grads = false;
     const TTensor& x0 = e->t[p.half[1].first];
     WMAR_HIP_CHECK(hipMemcpyAsync(x0.d, zq_dev, x0.elems((int)B) * 4, hipMemcpyDeviceToDevice, st));
-    if (int rc = vq_forward(e->net, p.half[1], (int)B, st, &e->tape)) return rc;
+    if (int rc = vq_forward(e->net, p.half[1], (int)B, st, e->frozen ? nullptr : &e->tape)) return rc;
     const int HW = p.resolution * p.resolution;
     const TTensor& yo = e->t[p.half[1].last];
     hipLaunchKernelGGL(p.unit_range ? k_nhwc_to_nchw_01 : k_nhwc_to_nchw, dim3((HW + 255) / 256, (unsigned)B), dim3(256), 0, st, (const float*)yo.d,
                        images_dev, p.out_ch, HW, yo.C);
     if (int rc = launch_status("k_nhwc_to_nchw")) return rc;
-    s.tape = true; s.B = (int)B;
+    s.tape = !e->frozen; s.B = (int)B;
     return WMAR_OK;
 }
 
 int wmar_vq_train_decode_backward(wmar_vq_train* e, const float* grad_images_dev, int64_t B, float* grad_zq_dev, void* stream) {
     WMAR_REQUIRE(e && grad_images_dev, "vq_train_decode_backward: null argument");
+    WMAR_REQUIRE(!e->frozen, "vq_train_decode_backward: a frozen handle has no tape and no gradients (wmar_vq_train_create_frozen)");
     const VqPlan& p = e->net.plan;
     const VqHalf& h = p.half[1];
     THalf& s = e->half[1];
@@ -433,6 +476,7 @@ int wmar_vq_train_decode_backward(wmar_vq_train* e, const float* grad_images_dev
 
 int wmar_vq_train_get_grads(wmar_vq_train* e, const char* const* names, void* const* grads_dev, int32_t n, int32_t accumulate, void* stream) {
     WMAR_REQUIRE(e && names && grads_dev, "vq_train_get_grads: null argument");
+    WMAR_REQUIRE(!e->frozen, "vq_train_get_grads: a frozen handle has no tape and no gradients (wmar_vq_train_create_frozen)");
     hipStream_t st = (hipStream_t)stream;
     for (int i = 0; i < n; ++i) {
         WMAR_REQUIRE(names[i] && grads_dev[i], "vq_train_get_grads: null entry %d", i);

@@ -10,7 +10,8 @@ reference's finetune.py (``compute_and_save_delta``, ``calculate_gradient_norm``
 from __future__ import annotations
 
 import math
-from typing import Callable, Dict, Optional
+import random
+from typing import Callable, Dict, List, Optional
 
 import torch
 
@@ -68,6 +69,59 @@ def rcc_loss(tok, z_indices: torch.Tensor, augmentations, p: float = 0.5, loss_w
     res_dict = {"orig_z_q": z_q, "orig_z_indices": z_indices, "rec_x": xrec, "rec_x_maybe_augmented": xaug, "rec_x_orig_decoder": xrec_orig,
                 "rec_z": zrec, "rec_z_q": zrec_q, "rec_z_indices": zrec_indices}
     return loss, res_dict, log_dict, was_augmented
+
+
+class _rng_kept:
+    """Saves the state of Python's ``random``, of torch's CPU generator and of the current device's generator, and puts all three back
+    on exit: what runs inside draws (``apply_random_augmentation`` does, even at p = 1) without moving anything outside."""
+
+    def __enter__(self):
+        self._py, self._cpu = random.getstate(), torch.get_rng_state()
+        self._dev = torch.cuda.get_rng_state() if torch.cuda.is_available() and torch.cuda.is_initialized() else None
+        return self
+
+    def __exit__(self, *exc):
+        random.setstate(self._py)
+        torch.set_rng_state(self._cpu)
+        if self._dev is not None:
+            torch.cuda.set_rng_state(self._dev)
+        return False
+
+
+def validate(tok, orig, codes: torch.Tensor, augmentations, batch_size: int, loss_weight: float,
+             rec_loss: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None) -> List[dict]:
+    """The reference's validation pass (finetune.py:73-128) over ``codes`` [N, S*S]: for ``[(Identity, [0])] + augmentations`` and every
+    parameter of every entry, ``rcc_loss(tok, batch, [(cls, [param])], p=1.0, ...)`` under ``torch.no_grad()`` on batches of
+    ``batch_size`` (the last may be short), with ``l0 = mean(orig_z_indices != rec_z_indices)`` added; every logged value is averaged
+    over rows, weighted by the batch size (:86-99).  One record per (transform, parameter): ``aug`` (class name), ``param``, ``n`` and
+    the averages.  Nothing is trained and no tape is touched: the forwards run on the tokenizer's no-grad engine.  The states of Python's
+    ``random`` and of torch's CPU and current-device generators are the same after the call as before it, so a run that validates
+    trains exactly as one that does not."""
+    from .augmentations.geometric import Identity
+    records = []
+    with _rng_kept(), torch.no_grad():
+        for cls, params in [(Identity, [0])] + list(augmentations or []):
+            for param in params:
+                sums: Dict[str, float] = {}
+                n = 0
+                for b0 in range(0, codes.shape[0], batch_size):
+                    batch = codes[b0:b0 + batch_size]
+                    _, res, log, _ = rcc_loss(tok, batch, [(cls, [param])], p=1.0, loss_weight=loss_weight, orig=orig, rec_loss=rec_loss)
+                    log["l0"] = float((res["orig_z_indices"] != res["rec_z_indices"]).float().mean())
+                    for k, v in log.items():
+                        sums[k] = sums.get(k, 0.0) + v * batch.shape[0]
+                    n += batch.shape[0]
+                rec = {"aug": cls.__name__, "param": param, "n": n}
+                rec.update({k: v / n for k, v in sums.items()})
+                records.append(rec)
+    return records
+
+
+def weight_distance(state: Dict[str, torch.Tensor], original_state: Dict[str, torch.Tensor], prefix: str) -> float:
+    """The mean over the tensors under ``prefix`` of ``||a - b||_2`` between ``state`` and ``original_state`` (``get_decoder_dist`` /
+    ``get_encoder_dist``, wmar/utils/utils.py:180-186)."""
+    dists = [torch.norm(v.detach() - original_state[k].detach().to(v.device)) for k, v in state.items() if k.startswith(prefix)]
+    return float(torch.mean(torch.stack(dists))) if dists else 0.0
 
 
 class reference_rec_loss:

@@ -133,6 +133,15 @@ class ChameleonARMMWrapper(AutoregressiveMultimodalModelWrapper):
     def get_vq(self):
         return self.get_image_tokenizer().quantize
 
+    def trainable_tokenizer(self, max_batch: int = 4):
+        """The image tokenizer as a trainable module on this wrapper's own weights (wmar_amd/models/tokenizer_train.py): what it trains
+        is what ``get_image_tokenizer().state_dict()`` returns, and the packed inference engine is rebuilt after every change.
+        Chameleon's VQGAN is the Taming network (the reference loads it with ``vqgan_codebase = "taming"``, finetune.py:272), so this is
+        the Taming class at ``_vq_cfg``; its codes are VQGAN code ids ``0 .. n_embed - 1``, not vocabulary ids."""
+        from .tokenizer_train import TrainableTokenizer
+        return TrainableTokenizer(self._vq_cfg, self._vq_state, max_batch=max_batch, device=self.model.device,
+                                  on_change=self._drop_vq_engine)
+
     def get_total_vocab_size(self):
         return len(self.vocab.all_tokens)
 

@@ -10,7 +10,11 @@ drops its packed inference engine) is called whenever a forward finds the weight
 The two forwards are ``torch.autograd.Function``s.  Their backward returns the input gradient and ADDS the weight gradients into the
 parameters' ``.grad`` itself (the engine hands over all gradients of a half in one call).  Each half has one tape: a backward must
 belong to the LAST forward of its half, anything else raises.  Under ``torch.no_grad()``, or when nothing requires a gradient, the
-forwards run on a second engine (created on first use) and leave the tapes alone.  There is no PyTorch fallback.
+forwards run on a second engine (created on first use) and leave the tapes alone.  That engine is a forward-only handle
+(``wmar_vq_train_create_frozen``): the same executor over the plan's slot buffers, bit-equal outputs, none of the tape or of the
+backward's memory.  ``frozen=True`` makes a tokenizer of that handle alone -- the original decoder of the fine-tuning loss: it leaves
+``requires_grad`` of its state as it finds it, never builds a taped engine and returns tensors without a graph.  There is no PyTorch
+fallback.
 
 The MaskGIT flavour is what the reference's RAR fine-tuning differentiates (deps/rar/modeling/titok.py:91-208): ``decode`` is
 ``decode_like_taming`` -- ``clamp(decoder(z_q), 0, 1) * 2 - 1``, images in [-1, 1] -- and ``encode_prequant`` is
@@ -124,10 +128,11 @@ class TrainableTokenizer:
     def _dims(cfg) -> Tuple[int, int, int]:
         return cfg.embed_dim, cfg.in_channels, cfg.out_ch
 
-    def _engine(self) -> _TrainEngine:
-        return _TrainEngine(self._create, self._abi_config(self.cfg, self.max_batch), self._tensors(), self.device)
+    def _engine(self, frozen: bool = False) -> _TrainEngine:
+        return _TrainEngine(self._create + ("_frozen" if frozen else ""), self._abi_config(self.cfg, self.max_batch), self._tensors(), self.device)
 
-    def __init__(self, cfg, state: Dict[str, torch.Tensor], max_batch: int = 4, device="cuda", on_change: Optional[Callable[[], None]] = None):
+    def __init__(self, cfg, state: Dict[str, torch.Tensor], max_batch: int = 4, device="cuda", on_change: Optional[Callable[[], None]] = None,
+                 frozen: bool = False):
         self.cfg, self.state, self.max_batch = cfg, state, int(max_batch)
         self._E, self._Cin, self._Cout = self._dims(cfg)
         self.device = torch.device(device)
@@ -138,9 +143,11 @@ class TrainableTokenizer:
             _require_cuda(t, k)
             if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_leaf:
                 raise ValueError(f"TrainableTokenizer: {k} must be a contiguous float32 leaf tensor")
-            t.requires_grad_(True)
-        self._train = self._engine()
-        self._eval: Optional[_TrainEngine] = None
+            if not frozen:
+                t.requires_grad_(True)
+        self.frozen = bool(frozen)
+        self._train = None if frozen else self._engine()
+        self._eval: Optional[_TrainEngine] = self._engine(frozen=True) if frozen else None
         self._versions = self._current_versions()
         self._tape = [0, 0]            # serial number of the forward each half's tape belongs to
         self._last_out = None
@@ -164,7 +171,7 @@ class TrainableTokenizer:
 
     @property
     def device_bytes(self) -> int:
-        return self._train.device_bytes + (self._eval.device_bytes if self._eval is not None else 0)
+        return sum(e.device_bytes for e in (self._train, self._eval) if e is not None)
 
     def _sync_weights(self):
         """Repack (wmar_vq_train_set_weights) when any parameter changed in place since the last pack: optimizer.step() needs no call."""
@@ -172,7 +179,8 @@ class TrainableTokenizer:
         if now == self._versions:
             return
         names, ptrs, n = _lib.tensor_table(self._tensors())
-        self._train.call("set_weights", names, ptrs, n)
+        if self._train is not None:
+            self._train.call("set_weights", names, ptrs, n)
         if self._eval is not None:
             self._eval.call("set_weights", names, ptrs, n)
         self._versions = now
@@ -234,10 +242,10 @@ class TrainableTokenizer:
     def _apply(self, fn, half: int, x: torch.Tensor) -> torch.Tensor:
         self._sync_weights()
         params = [p for k, p in self.named_parameters() if _half_of(k) == half and p.requires_grad]
-        if torch.is_grad_enabled() and (x.requires_grad or params):
+        if not self.frozen and torch.is_grad_enabled() and (x.requires_grad or params):
             return fn.apply(self, x, *params)
         if self._eval is None:
-            self._eval = self._engine()
+            self._eval = self._engine(frozen=True)
         return self._run(self._eval, half, self._prepare(half, x))
 
     def encode_prequant(self, images: torch.Tensor) -> torch.Tensor:

@@ -74,6 +74,27 @@ def plan(size: Tuple[int, int], target: int) -> Tuple[Tuple[int, int], Tuple[int
     return new, ((new[0] - target) // 2, (new[1] - target) // 2)
 
 
+def resize_plan(size: Tuple[int, int], target: int) -> Tuple[int, int]:
+    """(new_width, new_height) of torchvision's ``Resize(target)`` for a (width, height) image (transforms/functional.py,
+    ``_compute_resized_output_size``): the short side becomes ``target``, the long side ``int(target * long / short)``."""
+    w, h = size
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(target * long / short)
+    return (target, new_long) if w <= h else (new_long, target)
+
+
+def random_crop_origin(new: Tuple[int, int], target: int, generator: torch.Generator) -> Tuple[int, int]:
+    """(crop_x0, crop_y0) of torchvision's ``RandomCrop(target)`` on a (width, height) image (``RandomCrop.get_params``): no draw when
+    both sides already equal ``target``, else the top ``i = randint(0, h - target + 1)`` and then the left ``j = randint(0, w - target +
+    1)``, both from ``generator``."""
+    w, h = new
+    if w == target and h == target:
+        return 0, 0
+    i = int(torch.randint(0, h - target + 1, size=(1,), generator=generator).item())
+    j = int(torch.randint(0, w - target + 1, size=(1,), generator=generator).item())
+    return j, i
+
+
 def _host_one(px: np.ndarray, target: int) -> np.ndarray:
     from PIL import Image
     img = Image.fromarray(whiten(px) if px.shape[2] == 4 else px, "RGB")
@@ -103,8 +124,9 @@ def ingest(images: Sequence, target: int, device="cuda", return_u8: bool = False
     return ingest_packed(host.to(device, non_blocking=True), desc, target, return_u8)
 
 
-def pack(pix: List[np.ndarray], target: int):
-    """(uint8 host tensor holding the images back to back, each at a multiple of 4 bytes; the descriptor array of the C ABI)."""
+def pack(pix: List[np.ndarray], target: int, plans=None):
+    """(uint8 host tensor holding the images back to back, each at a multiple of 4 bytes; the descriptor array of the C ABI).
+    ``plans``: per image ``((new_width, new_height), (crop_x0, crop_y0))`` instead of ``plan``'s."""
     from .. import _lib
     offs, total = [], 0
     for p in pix:
@@ -116,13 +138,14 @@ def pack(pix: List[np.ndarray], target: int):
     for i, (p, o) in enumerate(zip(pix, offs)):
         flat[o:o + p.size] = p.reshape(-1)
         h, w, c = p.shape
-        (nw, nh), (x0, y0) = plan((w, h), target)
+        (nw, nh), (x0, y0) = plans[i] if plans is not None else plan((w, h), target)
         desc[i] = _lib.ImageDesc(o, w, h, c, nw, nh, x0, y0)
     return host, desc
 
 
-def ingest_packed(pixels_dev: torch.Tensor, desc, target: int, return_u8: bool = False):
-    """The device call on an uploaded pixel buffer (uint8, 1-D) and its descriptors (``pack``)."""
+def ingest_packed(pixels_dev: torch.Tensor, desc, target: int, return_u8: bool = False, filter: int = 1):
+    """The device call on an uploaded pixel buffer (uint8, 1-D) and its descriptors (``pack``).  ``filter``: Pillow's number of the
+    resampling filter, 1 = LANCZOS (the default: ``wmar_image_ingest``) or 2 = BILINEAR (``wmar_image_ingest_filtered``)."""
     from .. import _lib
     if not pixels_dev.is_cuda:
         raise RuntimeError("ingest_packed: the pixel buffer must be on the GPU")
@@ -130,6 +153,10 @@ def ingest_packed(pixels_dev: torch.Tensor, desc, target: int, return_u8: bool =
     out = torch.empty(n, 3, target, target, dtype=torch.float32, device=dev)
     u8 = torch.empty(n, target, target, 3, dtype=torch.uint8, device=dev) if return_u8 else None
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().wmar_image_ingest(pixels_dev.data_ptr(), pixels_dev.numel(), desc, n, int(target), out.data_ptr(),
-                                                 u8.data_ptr() if return_u8 else None, _lib.stream_ptr(dev)))
+        if filter == _lib.RESAMPLE_LANCZOS:
+            _lib.check(_lib.load().wmar_image_ingest(pixels_dev.data_ptr(), pixels_dev.numel(), desc, n, int(target), out.data_ptr(),
+                                                     u8.data_ptr() if return_u8 else None, _lib.stream_ptr(dev)))
+        else:
+            _lib.check(_lib.load().wmar_image_ingest_filtered(pixels_dev.data_ptr(), pixels_dev.numel(), desc, n, int(target), out.data_ptr(),
+                                                              u8.data_ptr() if return_u8 else None, int(filter), _lib.stream_ptr(dev)))
     return (out, u8) if return_u8 else out
