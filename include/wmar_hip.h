@@ -866,7 +866,11 @@ int wmar_sync_positions(const float* preds_dev, int64_t B, int32_t S, int8_t* po
  * cut / flip search, its half-to-even roundings and the selection across angles are integer / fp64 restatements without tolerance.
  * workspace_dev (16-byte aligned): error and cut tables of the batch plus the spline coefficients fp64 [n, S, S, 4] of as many
  * images n as fit; wmar_sync_workspace_bytes(B, S) holds the whole batch (four launches), a smaller one (at least the tables plus
- * one image) makes the call walk the batch in chunks of three launches each.  B <= 65535. */
+ * one image) makes the call walk the batch in chunks of three launches each.  B <= 65535.
+ * Result region (part of the contract; tests read it): once the call's launches have finished, the workspace starts with
+ *   err  fp64  [B, 41]      errori + errorj of every angle -20..20 (what total_error_dev receives), then, without padding,
+ *   cut  int32 [B, 41, 3]   (cut_i, cut_j, flipped_j) find_cut returned at that angle: S / 2 and 0 where an axis has no weight;
+ * B * 41 * 20 bytes, rounded up to a multiple of 256, in front of the coefficients.  aug_dev is selected from these tables. */
 int64_t wmar_sync_workspace_bytes(int64_t B, int32_t S);
 int wmar_sync_fit(const int8_t* positions_dev, int64_t B, int32_t S, int32_t* aug_dev, double* total_error_dev, void* workspace_dev,
                   int64_t workspace_bytes, void* stream);

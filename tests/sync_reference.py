@@ -93,7 +93,8 @@ def spline_rotate_values(coeffs, angle):
 
 
 # ---- the fit --------------------------------------------------------------------------------------------------------------------
-def find_cut(cumsums, pairs, dim, SZ):
+def find_cut(cumsums, pairs, dim, SZ, seen=None):
+    """`seen` (a set, optional) collects the names of the branches taken: the census of tests/test_sync_reference.py."""
     cut, cut_weight, votes = 0, 0, 0
     for l, r in pairs:
         cl, cr = cumsums[dim][l], cumsums[dim][r]
@@ -108,16 +109,25 @@ def find_cut(cumsums, pairs, dim, SZ):
             is_f, idx = True, idx_f
             votes += 1
         if cr[-1] != 0 and cl[-1] == 0:
-            pick = idx[0] if is_f else idx[-1]
+            pick, branch = (idx[0] if is_f else idx[-1]), "only_R"
         elif cl[-1] != 0 and cr[-1] == 0:
-            pick = idx[-1] if is_f else idx[0]
+            pick, branch = (idx[-1] if is_f else idx[0]), "only_L"
         else:
-            pick = (idx[0] + idx[-1]) // 2
+            pick, branch = (idx[0] + idx[-1]) // 2, "both" if cl[-1] != 0 else "neither"
+        if seen is not None:
+            seen.add(f"{branch}_{'flipped' if is_f else 'normal'}_curve")
         w = int(cl[-1] + cr[-1])
         cut += int(pick) * w
         cut_weight += w
     if cut_weight == 0:
+        if seen is not None:
+            seen.add("no_weight")
         return 1e9, SZ // 2, False
+    if seen is not None:
+        if (2 * cut) % cut_weight == 0 and (2 * cut // cut_weight) % 2 == 1:
+            seen.add("half_cut_floor_even" if (cut // cut_weight) % 2 == 0 else "half_cut_floor_odd")
+        if votes == 0 and dim == 0:
+            seen.add("votes_zero_dim0")
     cut = round(cut / cut_weight)
     flipped_vote = (votes / cut_weight) > 0
     error = 0
@@ -127,34 +137,75 @@ def find_cut(cumsums, pairs, dim, SZ):
     return error, cut, flipped_vote
 
 
-def fit_angle(wm_rot):
+def fit_angle(wm_rot, seen=None):
     S = wm_rot.shape[-1]
     thresh = 40 if S == 256 else 80
     cumsums = [[None], [None]]
     for dim in range(2):
         for i in range(1, 5):
             sums = np.sum(wm_rot == i, axis=dim)
+            if seen is not None:                         # axis 0 sums over the rows: one count per column
+                for v, what in ((thresh, "on_thresh"), (thresh - 1, "below_thresh")):
+                    if np.any(sums == v):
+                        seen.add(f"{'column' if dim == 0 else 'row'}_count_{what}")
             sums[sums < thresh] = 0
             cumsums[dim].append(np.cumsum(sums))
-    errori, cuti, _ = find_cut(cumsums, [(1, 3), (2, 4)], 1, S)
-    errorj, cutj, flipped = find_cut(cumsums, [(1, 2), (3, 4)], 0, S)
+    errori, cuti, _ = find_cut(cumsums, [(1, 3), (2, 4)], 1, S, seen)
+    errorj, cutj, flipped = find_cut(cumsums, [(1, 2), (3, 4)], 0, S, seen)
     return float(errori + errorj), cuti, cutj, flipped
 
 
-def fit(positions, rotate=rotate_wm):
-    """((rotation, cut_i, cut_j, flipped), total_error fp64 [41]) of one label map."""
+def fit_detail(positions, rotate=rotate_wm, seen=None):
+    """((rotation, cut_i, cut_j, flipped), total_error fp64 [41], cuts int32 [41, 3] = (cut_i, cut_j, flipped) of every angle)."""
     S = positions.shape[-1]
     wm = labels_of(positions)
     best, best_angles, total = (float("inf"), S // 2, S // 2, False), [0], np.zeros(len(ANGLES))
+    cuts = np.zeros((len(ANGLES), 3), dtype=np.int32)
     for n, angle in enumerate(ANGLES):
-        e, ci, cj, fl = fit_angle(rotate(wm, angle))
+        e, ci, cj, fl = fit_angle(rotate(wm, angle), seen)
         total[n] = e
+        cuts[n] = (ci, cj, int(fl))
         if e < best[0]:
             best, best_angles = (e, ci, cj, fl), [int(angle)]
         elif e == best[0]:
             best_angles.append(int(angle))
+    if seen is not None:
+        seen.add("several_best_angles" if len(best_angles) > 1 else "one_best_angle")
+        if (max(best_angles) + min(best_angles)) % 2:
+            seen.add("half_rotation")
     rotation = round((max(best_angles) + min(best_angles)) / 2)
-    return (rotation, int(best[1]), int(best[2]), bool(best[3])), total
+    return (rotation, int(best[1]), int(best[2]), bool(best[3])), total, cuts
+
+
+def fit(positions, rotate=rotate_wm):
+    """((rotation, cut_i, cut_j, flipped), total_error fp64 [41]) of one label map."""
+    return fit_detail(positions, rotate)[:2]
+
+
+class PlainRotator:
+    """rotate_wm through spline_rotate_values instead of scipy, the four prefilters run once per map (they do not depend on the
+    angle): `PlainRotator()(wm, angle)`."""
+
+    def __init__(self):
+        self.key, self.coeffs = None, None
+
+    def __call__(self, wm, angle):
+        if self.key is None or self.key is not wm:
+            self.key, self.coeffs = wm, [spline_coefficients((wm == i) * 255) for i in range(1, 5)]
+        res = np.zeros_like(wm)
+        for i in range(1, 5):
+            res[spline_rotate_values(self.coeffs[i - 1], angle) >= 0.5] = i
+        return res
+
+
+def source_coordinates(S, angle):
+    """fp64 (y, x) [S, S] of the input point every output pixel of a rotation by `angle` degrees samples."""
+    r = math.radians(float(angle))
+    c, s = math.cos(r), math.sin(r)
+    ctr = (S - 1) / 2.0
+    off0, off1 = ctr - (c * ctr + s * ctr), ctr - (-s * ctr + c * ctr)
+    i, j = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
+    return i * c + j * s + off0, i * (-s) + j * c + off1
 
 
 def rotate_wm_plain(wm, angle):
