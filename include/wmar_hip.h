@@ -254,8 +254,12 @@ int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* s
  * it (odd layers the other way round), RESID_OUT and HEAD read what block n_layer - 1 left; otherwise always x.  A raised in-launch
  * barrier flag is reported as WMAR_EHIP (the stages run are invalid; the engine continues on the two-launch path, as after
  * wmar_gpt_check).
- * wmar_gpt_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine).
- * Packed buffers are laid out for the MT of the step that wrote them (MT = 1 / 2 / 4 row tiles for B <= 32 / 64 / 128), sizes are
+ * wmar_gpt_probe_copy, wmar_rar_probe_copy and wmar_cham_probe_copy share one contract (stated here once): the call copies device to
+ * device between ptr_dev and the engine buffer `name` of block `layer` (to_engine != 0: into the engine, else out of it) and waits
+ * for the stream.  It returns the buffer's size in bytes, or a negative status: WMAR_EINVAL for a name the engine does not know, for
+ * a buffer this engine does not have (its shape is not eligible for the kernel that uses it) and for a `bytes` other than exactly
+ * that size; WMAR_EHIP when the copy fails.  With ptr_dev null nothing is copied and `bytes` is ignored: a size query.
+ * The buffers of wmar_gpt_probe_copy: packed buffers are laid out for the MT of the step that wrote them (MT = 1 / 2 / 4 row tiles for B <= 32 / 64 / 128), sizes are
  * for Mpad = 32 * MT(max_batch) rows:
  *   x, x2, y [D/8][MT][64][4] fp32; hbuf [4D/8][MT][64][4]; yq [D/16][2][3][64][4] u32 (bf16 planes, 64-row engines only);
  *   slabs [8] pieces of D columns, qkv_slabs [8] pieces of 3D columns (piece stride = D resp. 3D x 32 MT floats of the step's MT);
@@ -263,8 +267,6 @@ int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* s
  *   kcache, vcache [max_batch][H][block_size][head_dim] fp32 of block `layer`; xs, ys, qs [12][D], hs [12][4D] row-major fp32;
  *   wqkv, wqkvx_bx, wproj, wproj_bx, wfc1, wfc1x16, wfc1x8, wfc2, bqkv, cqkv, bproj, bfc1, cfc1, bfc2 of block `layer`;
  *   whead, bhead, chead.
- * It returns the buffer's size in bytes (also with ptr_dev null: a size query) or a negative status (a buffer this engine does
- * not have: WMAR_EINVAL); `bytes` must equal that size.
  * wmar_gpt_probe_plan writes, for a step of B rows attending to kv_len cached rows,
  *   "small=0 MT=.. S_qx=.. nkeep=.. S_qkv=.. S_proj=.. S_fc2=.. fc2_hi=.. nch=.. nch_ln2=.. pingpong=.. x_head=x|x2 attn_waves=..
  *    rowmajor=.. proj=gemm|bx|bx_xr head=ntw2|N,PER fc1_tiles=.. head_tiles=.. xcd_ok=.. xr_eligible=.. barrier_fallbacks=..
@@ -380,8 +382,7 @@ int wmar_rar_check(wmar_rar* g, void* stream);
  * ignore it) with the engine's own RarPlan and buffers, and waits for the stream.  tok_dev null selects the generate form of the
  * embedding, reading the engine's `ids`.  A raised in-launch wait flag is reported as WMAR_EHIP, not re-run (the stages run are
  * invalid; the engine continues on the two-launch pair, as after wmar_rar_check).
- * wmar_rar_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine).
- * Packed buffers are laid out for the MT of the position that wrote them, sizes are for Mpad = 32 MT(2 max_batch) rows:
+ * The buffers of wmar_rar_probe_copy (its contract: at wmar_gpt_probe_copy above): packed buffers are laid out for the MT of the position that wrote them, sizes are for Mpad = 32 MT(2 max_batch) rows:
  *   x, h, y, sc [D/8][MT][64][4] fp32 (sc: MTc row tiles); hbuf [F/8][MT][64][4]; mod [Ntot/8][MTc][64][4]; mod_u [32 ceil(T/32)][Ntot];
  *   slabs [8] pieces of D columns, qkv_slabs [S_qkv of the bx plan, else 1] pieces of 3 D columns (piece stride = columns x 32 MT floats);
  *   xq, yq [D/16][MT][3][64][4] u32 and hq [F/16][MT][3][64][4] (bf16 planes, engines with the bx plan), scq [D/16][2][3][64][4];
@@ -390,8 +391,6 @@ int wmar_rar_check(wmar_rar* g, void* stream);
  *   kcache, vcache [2 max_batch][H][image_seq_len + 2][head_dim] fp32 of block `layer`;
  *   wqkv, wproj, wfc1, wfc2 (k_pack_linear order), wqkv_bx, wproj_bx, wfc1_bx, wfc2_bx (k_pack_bx order), bqkv, bproj, bfc1, bfc2,
  *   norm1_w, norm1_b, norm2_w, norm2_b, q_norm_w, q_norm_b, k_norm_w, k_norm_b of block `layer`; wada, wada_bx, bada, whead, bhead.
- * It returns the buffer's size in bytes (also with ptr_dev null: a size query) or a negative status (a buffer this engine does
- * not have: WMAR_EINVAL); `bytes` must equal that size.
  * wmar_rar_probe_plan writes, for a position of M rows attending to kv_len cached rows,
  *   "MT=.. MTc=.. bx=.. ada_bx=.. fc1_bx=.. rowmajor=.. S_qkv=.. S_proj=.. S_fc2=.. PER_qkv=.. PER_proj=.. PER_fc2=.. nch=.. nrm=.. kpw=..
  *    fused=.. fallbacks=.. ada_tiles=.. fc1_tiles=.. head_tiles=.. attn_waves=.. stages=EMBED,ADALN,.. kernels=embed=..;adaln=..;.."
@@ -529,12 +528,11 @@ int wmar_cham_generate_image_hooked(wmar_cham* g, const int64_t* prompt_tokens_h
  *   HEAD        k_bgemm<MT,LOGITS>     logits = bf16(1/rms * (output.weight * norm.weight) x) as fp32 [M, vocab]
  * wmar_cham_probe_run runs stages first_stage..last_stage of block `layer` with the engine's own plan and buffers and waits for
  * the stream; tok_dev / pos_dev are copied in only when EMBED is among them, logits_dev is needed only for HEAD.
- * wmar_cham_probe_copy copies device to device between ptr_dev and the engine buffer `name` (to_engine != 0: into the engine):
+ * The buffers of wmar_cham_probe_copy (its contract: at wmar_gpt_probe_copy above):
  *   x, y [D/16][MT][64][8] bf16; hbuf [F/16][MT][64][8] bf16; slabs [16][D/16][MT][64][8] fp32;
  *   big_slabs [16][max(D + 2 Dkv, 2 F)/16][MT][64][8] fp32 (a piece's stride is the producing GEMM's own width);
  *   ssq [ceil(D/64)][32 MT] fp64; kcache, vcache [max_rows][Hkv][max_seq_len][head_dim] bf16 of block `layer`;
  *   rope [max_seq_len][head_dim/2] (cos, sin) fp32; wqkv, wo, w13, w2 (block `layer`), whead: packed weights [N/32][K/16][64][8] bf16.
- * It returns the buffer's size in bytes (also with ptr_dev null: a size query) or a negative status; `bytes` must equal that size.
  * wmar_cham_probe_plan writes "MT=.. sk_qkv=C,U,G sk_o=.. sk_13=.. sk_2=.. sk_head=.. kernels=k_bgemm<MT,SLAB>;k_bgemm<MT,LOGITS>;
  * k_cham_attn<HD,NWA>" for a step of M rows: the stream-K decomposition (chunks per group, units, workgroups) and the kernel
  * instantiations the dispatch launches. */

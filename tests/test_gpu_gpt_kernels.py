@@ -37,8 +37,6 @@ Rules this file applies, and why:
 
 The RAR-only variants of these kernels (k_attn_decode80, attention mode 1, k_modulate, k_resid_mod, k_bx with GELU / XF / four row
 tiles) are held stage by stage in tests/test_gpu_rar_kernels.py, through wmar_rar_probe_*."""
-import ctypes as C
-import os
 import time
 
 import numpy as np
@@ -48,15 +46,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import gpt_kernel_reference as R  # noqa: E402
+from tests.engine_probe import EngineCache, EngineProbe, dev, parse_plan, say  # noqa: E402
 from wmar_amd.utils import synth  # noqa: E402
 
-F64 = {"stats", "stats_q"}
 SENT = float(R.SENTINEL)
 GARBAGE = 3.0e30
 
 
-def _say(tag, **figs):
-    print("GPTK %-40s %s" % (tag, " ".join("%s=%s" % (k, ("%.3g" % v) if isinstance(v, float) else v) for k, v in figs.items())))
+_say = say("GPTK", 40)
 
 
 # ------------------------------------------------------------------------------------------------------------------- engines
@@ -99,111 +96,32 @@ def _dense_state(cfg, seed):
     return {k: v.float().numpy() for k, v in synth.synth_gpt_state(cfg, seed=seed, logit_scale=4.0).items()}
 
 
-class Probe:
+class Probe(EngineProbe):
     """One wmar_gpt engine and stage access to it."""
+    ENGINE = "gpt"
+    DTYPES = {"stats": torch.float64, "stats_q": torch.float64, "yq": torch.int16}
 
     def __init__(self, name, kind, env=()):
-        from wmar_amd import _lib
-        self._lib, self.L = _lib, _lib.load()
         self.name, self.kind = name, kind
         self.D, self.H, self.V, self.T, self.nl, self.Bmax = SHAPES[name]
         self.hd = self.D // self.H
         self.cfg = _cfg(name)
         self.sd = _int_state(self.cfg, 11 + self.D) if kind == "int" else _dense_state(self.cfg, 11 + self.D)
-        tensors = {k: torch.from_numpy(v).cuda().contiguous() for k, v in self.sd.items()}
-        c = _lib.GptConfig(self.V, self.T, self.nl, self.H, self.D, self.Bmax)
-        names, ptrs, n = _lib.tensor_table(tensors)
-        h = C.c_void_p()
-        for e in env:
-            os.environ[e] = "1"
-        try:
-            _lib.check(self.L.wmar_gpt_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(), C.byref(h)))
-        finally:
-            for e in env:
-                del os.environ[e]
-        torch.cuda.synchronize()
-        self.h = h
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.wmar_gpt_destroy(self.h)
-            self.h = None
-
-    # ---- raw buffers
-    def size(self, name, layer=0):
-        n = self.L.wmar_gpt_probe_copy(self.h, name.encode(), layer, None, 0, 0, self._lib.stream_ptr())
-        if n < 0:
-            self._lib.check(int(n))
-        return int(n)
-
-    def has(self, name):
-        return self.L.wmar_gpt_probe_copy(self.h, name.encode(), 0, None, 0, 0, self._lib.stream_ptr()) > 0
-
-    def _dt(self, name):
-        return torch.float64 if name in F64 else (torch.int16 if name == "yq" else torch.float32)
-
-    def get_dev(self, name, layer=0):
-        n, dt = self.size(name, layer), self._dt(name)
-        t = torch.empty(n // torch.empty(0, dtype=dt).element_size(), dtype=dt, device="cuda")
-        rc = self.L.wmar_gpt_probe_copy(self.h, name.encode(), layer, t.data_ptr(), n, 0, self._lib.stream_ptr())
-        if rc < 0:
-            self._lib.check(int(rc))
-        return t
-
-    def get(self, name, layer=0):
-        a = self.get_dev(name, layer).cpu().numpy()
-        return a.view(np.uint16) if a.dtype == np.int16 else a
-
-    def put(self, name, a, layer=0):
-        if isinstance(a, np.ndarray):
-            a = torch.from_numpy(np.ascontiguousarray(a.view(np.int16) if a.dtype == np.uint16 else a))
-        t = a.to("cuda").contiguous().view(-1)
-        assert t.dtype == self._dt(name), (name, t.dtype)
-        assert t.numel() * t.element_size() == self.size(name, layer), (name, t.numel())
-        rc = self.L.wmar_gpt_probe_copy(self.h, name.encode(), layer, t.data_ptr(), t.numel() * t.element_size(), 1, self._lib.stream_ptr())
-        if rc < 0:
-            self._lib.check(int(rc))
-
-    def fill(self, name, value, layer=0):
-        dt = self._dt(name)
-        self.put(name, torch.full((self.size(name, layer) // torch.empty(0, dtype=dt).element_size(),), value, dtype=dt, device="cuda"), layer)
+        from wmar_amd import _lib
+        self._create(_lib.GptConfig(self.V, self.T, self.nl, self.H, self.D, self.Bmax), self.sd, env)
 
     # ---- stages
-    def _checked(self, rc):
-        """a launch that fails on the device ends the session: nothing more is started on a GPU that has faulted"""
-        try:
-            self._lib.check(rc)
-        except self._lib.WmarError as e:
-            pytest.exit("stopping: %s" % e, returncode=3)
-
     def run(self, first, last, B, pos=0, layer=0, tok=None, want_logits=False):
-        lg = torch.empty(B, self.V, dtype=torch.float32, device="cuda") if want_logits else None
-        tk = torch.as_tensor(tok, dtype=torch.int64).cuda() if tok is not None else None
-        self._checked(self.L.wmar_gpt_probe_run(self.h, tk.data_ptr() if tk is not None else None, B, pos, layer, first, last,
-                                                lg.data_ptr() if want_logits else None, self._lib.stream_ptr()))
-        return lg.cpu().numpy() if want_logits else None
+        return self._call(self._run, B, self.V, dev(tok), B, pos, layer, first, last, want_logits=want_logits)
 
     def decode_step(self, tok, pos):
-        B = len(tok)
-        lg = torch.empty(B, self.V, dtype=torch.float32, device="cuda")
-        tk = torch.as_tensor(tok, dtype=torch.int64).cuda()
-        self._checked(self.L.wmar_gpt_decode_step(self.h, tk.data_ptr(), B, pos, lg.data_ptr(), self._lib.stream_ptr()))
-        torch.cuda.synchronize()
-        return lg.cpu().numpy()
+        return self._call(self.L.wmar_gpt_decode_step, len(tok), self.V, dev(tok), len(tok), pos)
 
     def plan(self, B, kv_len=1):
-        buf = C.create_string_buffer(4096)
-        self._lib.check(self.L.wmar_gpt_probe_plan(self.h, B, kv_len, buf, 4096))
-        head, kernels = buf.value.decode().split(" kernels=", 1)
-        out = {"kernels": kernels}
-        for item in head.split():
-            k, v = item.split("=", 1)
-            out[k] = v
+        out = parse_plan(self.plan_text(B, kv_len))
         for k in ("small", "MT", "S_qx", "nkeep", "S_qkv", "S_proj", "S_fc2", "fc2_hi", "nch", "nch_ln2", "pingpong", "attn_waves", "rowmajor", "fc1_tiles", "head_tiles",
                   "xcd_ok", "xr_eligible", "barrier_fallbacks"):
-            out[k] = int(out[k])
-        out["stages"] = out["stages"].split(",")
-        out["roles"] = dict(it.split("=", 1) for it in kernels.split(";"))
+            assert isinstance(out[k], int), (k, out[k])
         return out
 
     def waves(self, nwa):
@@ -214,10 +132,7 @@ class Probe:
     # ---- packed buffers as [Mpad, width] arrays of the step's MT
     def put_act(self, name, X, MT):
         """X [32 MT, K] into the front of a packed buffer sized for max_batch"""
-        flat = self.get(name)
-        p = R.pack_act(X.astype(np.float32), MT)
-        flat[:p.size] = p
-        self.put(name, flat)
+        self.put_front(name, R.pack_act(X.astype(np.float32), MT))
 
     def get_act(self, name, MT, K):
         return R.unpack_act(self.get(name)[:32 * MT * K], MT, K)
@@ -236,10 +151,7 @@ class Probe:
 
     def put_stats(self, name, st, MT):
         """st [nch][32 MT][2] into the front of the statistics buffer"""
-        flat = self.get(name)
-        flat[:] = 1e300                                          # chunks past the plan's count must not be read
-        flat[:st.size] = st.reshape(-1)
-        self.put(name, flat)
+        self.put_front(name, st.reshape(-1).astype(np.float64), rest=1e300)       # chunks past the plan's count must not be read
 
     def get_stats(self, name, nch, MT):
         return self.get(name)[:nch * 32 * MT * 2].reshape(nch, 32 * MT, 2)
@@ -248,23 +160,18 @@ class Probe:
         return self.sd[key if layer is None else "blocks.%d.%s" % (layer, key)]
 
 
-_ENGINES = {}
+_ENGINES = EngineCache()
 
 
 def _probe(name, kind, env=()):
     """the module's engines, created on first use (one per shape, weights and environment) and destroyed when the module ends"""
-    key = (name, kind, env)
-    if key not in _ENGINES:
-        _ENGINES[key] = Probe(name, kind, env)
-    return _ENGINES[key]
+    return _ENGINES.get((name, kind, env), lambda: Probe(name, kind, env))
 
 
 @pytest.fixture(scope="module", autouse=True)
 def engines():
     yield _ENGINES
-    for pr in _ENGINES.values():
-        pr.__del__()
-    _ENGINES.clear()
+    _ENGINES.close_all()
     torch.cuda.empty_cache()
 
 

@@ -26,7 +26,7 @@ What is asserted
       algebra), dense attention (the derived distance per output, 4 x an fp32 numpy evaluation per launch), the unconditional table
       (DENSE_GATE = 2 x the fp32 chain plus the SiLU distance), the dense QKV / PROJ / FC2 pieces and the head (the chain bound), the dense adaLN GEMM (k_gemm and k_bx<4,20,2>) and the dense FC1 through its GELU (k_gemm, planes, the XF k_bx).
 Row counts of the stage-level groups: R1 at 1 / 5 / 31 / 32 / 33 / 63 / 64 / 65 / 127 / 128 (not every group has all ten), Bhalf 31 / 32 / 33 / 63 / 64.
-A launch that fails on the device ends the session (pytest.exit); nothing is retried.
+A launch that fails on the device ends the session (tests/engine_probe.py: EngineProbe._checked); nothing is retried.
 
 Measured on an MI355X (365 cases, 35 s): 0 differing bits in every exact and between-paths case, 0 bytes changed in buffers a launch
 does not own; SiLU 0.15 .. 0.35 of its distance (an fp32 numpy evaluation 0.25 .. 0.49); k_modulate 0.56 .. 0.96 and k_resid_mod 0.44 ..
@@ -35,9 +35,6 @@ fold <= 0.98; appended k rows 0.02 .. 0.61 of the derived distance and 1.00 .. 1
 of the derived distance, 0 .. 2.03 x the fp32 evaluation (gate 4); table 0.24 .. 0.38 x the chain; dense pieces 0.22 .. 0.55 x, adaLN GEMM
 0.26 .. 0.43 x (k_bx<4,20,2>: 0.26) and head 0.30 .. 0.47 x the chain (gate 2); GELU 0.25 of its distance on exact pre-activations, 0.06 ..
 0.16 on dense ones (XF k_bx: 0.06 .. 0.08).  DESIGN.md section 4 has the table."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -45,17 +42,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import rar_kernel_reference as R  # noqa: E402
+from tests.engine_probe import EngineCache, EngineProbe, dev, parse_plan, say  # noqa: E402
 
 SENT = float(R.SENTINEL)
 GARBAGE = 3.0e30
 SEQ, V, NCLS = 16, 256, 8
 T = SEQ + 2
 NONE_ID = NCLS + V + 1
-F64 = {"stats"}
-U64 = {"part"}
-I64 = {"ids", "cond_ids"}
-I32 = {"ctr"}
-I16 = {"xq", "yq", "hq", "scq"}
 WORK = ["x", "h", "y", "sc", "hbuf", "slabs", "qkv_slabs", "mod", "xq", "yq", "hq", "scq"]
 
 SHAPES = {  # name: (D, H, F, L, max_batch)
@@ -72,8 +65,7 @@ HEADLINE = {
 }
 
 
-def _say(tag, **figs):
-    print("RARK %-44s %s" % (tag, " ".join("%s=%s" % (k, ("%.3g" % v) if isinstance(v, float) else v) for k, v in figs.items())))
+_say = say("RARK", 44)
 
 
 def _shapes(D, H, F, L):
@@ -126,96 +118,28 @@ def _state(name, kind):
     return sd
 
 
-class Probe:
+class Probe(EngineProbe):
     """One wmar_rar engine and stage access to it."""
+    ENGINE = "rar"
+    DTYPES = {"stats": torch.float64, "part": torch.int64, "ids": torch.int64, "cond_ids": torch.int64, "ctr": torch.int32,
+              "xq": torch.int16, "yq": torch.int16, "hq": torch.int16, "scq": torch.int16}
+    U64 = {"part"}
 
     def __init__(self, name, kind, env=()):
-        from wmar_amd import _lib
-        self._lib, self.L = _lib, _lib.load()
         self.name, self.kind, self.env = name, kind, env
         self.D, self.H, self.F, self.nl, self.Bmax = SHAPES[name]
         self.hd, self.Ntot, self.Mmax = self.D // self.H, 6 * self.D * self.nl + 2 * self.D, 2 * self.Bmax
         self.MTmax = R.mt_for(self.Mmax)
         self.sd = _state(name, kind)
-        tensors = {k: torch.from_numpy(v).cuda().contiguous() for k, v in self.sd.items()}
-        c = _lib.RarConfig(self.D, self.nl, self.H, self.F, SEQ, V, NCLS, self.Bmax)
-        names, ptrs, n = _lib.tensor_table(tensors)
-        h = C.c_void_p()
-        old = {e: os.environ.get(e) for e in env}
-        for e in env:
-            os.environ[e] = "1"
-        try:
-            _lib.check(self.L.wmar_rar_create(C.byref(c), names, ptrs, n, _lib.stream_ptr(), C.byref(h)))
-        finally:
-            for e, v in old.items():
-                if v is None:
-                    del os.environ[e]
-                else:
-                    os.environ[e] = v
-        torch.cuda.synchronize()
-        self.h = h
+        from wmar_amd import _lib
+        self._create(_lib.RarConfig(self.D, self.nl, self.H, self.F, SEQ, V, NCLS, self.Bmax), self.sd, env)
         self.wada = np.concatenate([self.sd["blocks.%d.adaLN_modulation.1.weight" % i] for i in range(self.nl)] + [self.sd["adaln_before_head.adaLN_modulation.1.weight"]])
         self.bada = np.concatenate([self.sd["blocks.%d.adaLN_modulation.1.bias" % i] for i in range(self.nl)] + [self.sd["adaln_before_head.adaLN_modulation.1.bias"]])
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.wmar_rar_destroy(self.h)
-            self.h = None
-
-    # ---- raw buffers
-    def size(self, name, layer=0):
-        n = self.L.wmar_rar_probe_copy(self.h, name.encode(), layer, None, 0, 0, self._lib.stream_ptr())
-        if n < 0:
-            self._lib.check(int(n))
-        return int(n)
-
-    def has(self, name):
-        return self.L.wmar_rar_probe_copy(self.h, name.encode(), 0, None, 0, 0, self._lib.stream_ptr()) > 0
-
-    def _dt(self, name):
-        return (torch.float64 if name in F64 else torch.int64 if name in U64 or name in I64 else torch.int32 if name in I32
-                else torch.int16 if name in I16 else torch.float32)
-
-    def get_dev(self, name, layer=0):
-        n, dt = self.size(name, layer), self._dt(name)
-        t = torch.empty(n // torch.empty(0, dtype=dt).element_size(), dtype=dt, device="cuda")
-        rc = self.L.wmar_rar_probe_copy(self.h, name.encode(), layer, t.data_ptr(), n, 0, self._lib.stream_ptr())
-        if rc < 0:
-            self._lib.check(int(rc))
-        return t
-
-    def get(self, name, layer=0):
-        a = self.get_dev(name, layer).cpu().numpy()
-        return a.view(np.uint16) if a.dtype == np.int16 else (a.view(np.uint64) if name in U64 else a)
-
-    def put(self, name, a, layer=0):
-        if isinstance(a, np.ndarray):
-            a = np.ascontiguousarray(a)
-            a = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else (a.view(np.int64) if a.dtype == np.uint64 else a))
-        t = a.to("cuda").contiguous().view(-1)
-        assert t.dtype == self._dt(name), (name, t.dtype)
-        assert t.numel() * t.element_size() == self.size(name, layer), (name, t.numel())
-        rc = self.L.wmar_rar_probe_copy(self.h, name.encode(), layer, t.data_ptr(), t.numel() * t.element_size(), 1, self._lib.stream_ptr())
-        if rc < 0:
-            self._lib.check(int(rc))
-
-    def fill(self, name, value, layer=0):
-        dt = self._dt(name)
-        self.put(name, torch.full((self.size(name, layer) // torch.empty(0, dtype=dt).element_size(),), value, dtype=dt, device="cuda"), layer)
-
-    def put_front(self, name, flat, layer=0, rest=None):
-        """flat into the front of a buffer; the rest keeps its contents, or is set to `rest`"""
-        t = self.get_dev(name, layer)
-        if rest is not None:
-            t.fill_(rest)
-        src = torch.from_numpy(np.ascontiguousarray(flat.view(np.int16) if flat.dtype == np.uint16 else flat)).cuda().view(-1)
-        t[:src.numel()] = src
-        self.put(name, t, layer)
 
     def sentinel_work(self):
         for nme in WORK:
             if self.has(nme):
-                if nme in I16:
+                if self._dt(nme) == torch.int16:
                     self.fill(nme, 0x7f7f)
                 else:
                     self.fill(nme, SENT)
@@ -238,21 +162,9 @@ class Probe:
             assert torch.equal(now.view(torch.uint8), before.view(torch.uint8)), "%s: a buffer the launch does not own changed" % n
 
     # ---- stages
-    def _checked(self, rc):
-        """a launch that fails on the device ends the session: nothing more is started on a GPU that has faulted"""
-        try:
-            self._lib.check(rc)
-        except self._lib.WmarError as e:
-            pytest.exit("stopping: %s" % e, returncode=3)
-
     def run(self, first, last, M, Bhalf=None, shared_u=0, pos=0, layer=0, tok=None, cond=None, want_logits=False):
         Bhalf = M if Bhalf is None else Bhalf
-        lg = torch.empty(M, V, dtype=torch.float32, device="cuda") if want_logits else None
-        tk = torch.as_tensor(np.asarray(tok), dtype=torch.int64).cuda() if tok is not None else None
-        cd = torch.as_tensor(np.asarray(cond), dtype=torch.int64).cuda() if cond is not None else None
-        self._checked(self.L.wmar_rar_probe_run(self.h, tk.data_ptr() if tk is not None else None, cd.data_ptr() if cd is not None else None, M, Bhalf,
-                                                shared_u, pos, layer, first, last, lg.data_ptr() if want_logits else None, self._lib.stream_ptr()))
-        return lg.cpu().numpy() if want_logits else None
+        return self._call(self._run, M, V, dev(tok), dev(cond), M, Bhalf, shared_u, pos, layer, first, last, want_logits=want_logits)
 
     def walk(self, M, Bhalf, shared_u, pos, first=R.EMBED, tok=None, cond=None):
         """the position from stage `first` (of block 0) to HEAD, one probe call per block"""
@@ -264,24 +176,13 @@ class Probe:
         return self.run(R.HEAD, R.HEAD, M, Bhalf, shared_u, pos, self.nl - 1, want_logits=True)
 
     def forward_position(self, tok, cond, pos):
-        M = len(tok)
-        lg = torch.empty(M, V, dtype=torch.float32, device="cuda")
-        tk, cd = torch.as_tensor(np.asarray(tok), dtype=torch.int64).cuda(), torch.as_tensor(np.asarray(cond), dtype=torch.int64).cuda()
-        self._checked(self.L.wmar_rar_forward_position(self.h, tk.data_ptr(), cd.data_ptr(), M, pos, lg.data_ptr(), self._lib.stream_ptr()))
-        torch.cuda.synchronize()
-        return lg.cpu().numpy()
+        return self._call(self.L.wmar_rar_forward_position, len(tok), V, dev(tok), dev(cond), len(tok), pos)
 
     def plan(self, M, Bhalf=None, shared_u=0, kv_len=1):
         """the plan for M rows, held to the restated dispatch rules and the pinned facts: a shape that silently takes another path fails"""
         Bhalf = M if Bhalf is None else Bhalf
-        buf = C.create_string_buffer(4096)
-        self._lib.check(self.L.wmar_rar_probe_plan(self.h, M, Bhalf, shared_u, kv_len, buf, 4096))
-        head, kernels = buf.value.decode().split(" kernels=", 1)
-        out = {}
-        for item in head.split():
-            k, v = item.split("=", 1)
-            out[k] = v.split(",") if k == "stages" else int(v)
-        out["roles"] = dict(it.split("=", 1) for it in kernels.split(";"))
+        out = parse_plan(self.plan_text(M, Bhalf, shared_u, kv_len))
+        assert all(isinstance(v, int) for k, v in out.items() if k not in ("stages", "kernels", "roles")), out
         want = R.expected_plan(self.D, self.H, self.F, self.nl, V, self.Bmax, M, Bhalf, shared_u, no_bx="WMAR_NO_BX" in self.env,
                                fused="WMAR_NO_XR" not in self.env)
         assert out["fallbacks"] == 0, "an in-launch wait gave up: the engine left the fused launch"
@@ -305,26 +206,23 @@ class Probe:
         return self.sd[key if layer is None else "blocks.%d.%s" % (layer, key)]
 
 
-_ENGINES = {}
+_ENGINES = EngineCache()
 
 
 def _probe(name, kind="dense", env=()):
     key = (name, kind, env)
-    if key not in _ENGINES:
-        if name in ("R3", "R4"):           # the two large shapes: one of them (and its variants) on the device at a time
-            for k in [k for k in _ENGINES if k[0] in ("R3", "R4") and k[0] != name]:
-                _ENGINES.pop(k).close()
-            torch.cuda.empty_cache()
-        _ENGINES[key] = Probe(name, kind, env)
-    return _ENGINES[key]
+    live = _ENGINES.engines
+    if key not in live and name in ("R3", "R4"):           # the two large shapes: one of them (and its variants) on the device at a time
+        for k in [k for k in live if k[0] in ("R3", "R4") and k[0] != name]:
+            live.pop(k).close()
+        torch.cuda.empty_cache()
+    return _ENGINES.get(key, lambda: Probe(name, kind, env))
 
 
 @pytest.fixture(scope="module", autouse=True)
 def engines():
     yield _ENGINES
-    for pr in _ENGINES.values():
-        pr.close()
-    _ENGINES.clear()
+    _ENGINES.close_all()
     torch.cuda.empty_cache()
 
 

@@ -181,8 +181,10 @@ def load():
     L.wmar_gpt_plan_info.argtypes = [vp, i64, C.c_char_p, i64]
     L.wmar_gpt_check.argtypes = [vp, vp]
     L.wmar_gpt_probe_run.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, vp]
-    L.wmar_gpt_probe_copy.restype = i64
-    L.wmar_gpt_probe_copy.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
+    for eng in ("gpt", "rar", "cham"):            # one contract for the three engines (include/wmar_hip.h)
+        fn = getattr(L, "wmar_%s_probe_copy" % eng)
+        fn.restype = i64
+        fn.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
     L.wmar_gpt_probe_plan.argtypes = [vp, i64, i32, C.c_char_p, i64]
     L.wmar_rar_create.argtypes = [C.POINTER(RarConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
     L.wmar_rar_destroy.argtypes = [vp]
@@ -196,8 +198,6 @@ def load():
     L.wmar_rar_check.argtypes = [vp, vp]
     L.wmar_rar_launch_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.wmar_rar_probe_run.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp]
-    L.wmar_rar_probe_copy.restype = i64
-    L.wmar_rar_probe_copy.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
     L.wmar_rar_probe_plan.argtypes = [vp, i64, i64, i32, i32, C.c_char_p, i64]
     L.wmar_gumbel_key_build.argtypes = [C.c_uint64, i64, vp, vp, vp]
     L.wmar_gumbel_sample.argtypes = [vp, i64, i64, vp, i64, i32, f32, f32, i32, vp, vp]
@@ -255,8 +255,6 @@ def load():
     L.wmar_cham_device_bytes.argtypes = [vp]
     L.wmar_cham_forward_tokens.argtypes = [vp, vp, vp, i64, vp, vp]
     L.wmar_cham_probe_run.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp]
-    L.wmar_cham_probe_copy.restype = i64
-    L.wmar_cham_probe_copy.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
     L.wmar_cham_probe_plan.argtypes = [vp, i64, C.c_char_p, i64]
     L.wmar_cham_generate_image.argtypes = [vp, C.POINTER(WmCtx), vp, vp, i64, C.POINTER(ChamSampleParams), vp, vp, i32, vp, i32, vp, vp]
     L.wmar_cham_sample.argtypes = [C.POINTER(WmCtx), vp, i64, i64, vp, i64, i64, f32, f64, f32, f32, vp, vp, i32, vp, vp, vp, vp]

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "cham_kernels.h"
+#include "probe_host.h"
 #include "sampler.h"
 
 namespace wmar {
@@ -346,9 +347,7 @@ int wmar_cham_probe_run(wmar_cham* g, const int64_t* tok_dev, const int32_t* pos
     WMAR_REQUIRE(g, "cham_probe_run: null engine");
     WMAR_REQUIRE(M >= 1 && M <= g->Mmax, "cham_probe_run: rows %lld outside 1..%d", (long long)M, g->Mmax);
     WMAR_REQUIRE(layer >= 0 && layer < g->L, "cham_probe_run: layer %d outside 0..%d", layer, g->L - 1);
-    WMAR_REQUIRE(first_stage >= WMAR_CHAM_STAGE_EMBED && last_stage <= WMAR_CHAM_STAGE_HEAD && first_stage <= last_stage,
-                 "cham_probe_run: stages %d..%d", first_stage, last_stage);
-    WMAR_REQUIRE(last_stage < WMAR_CHAM_STAGE_HEAD || logits_dev, "cham_probe_run: the HEAD stage needs logits_dev");
+    if (int rc = probe_stage_range("cham_probe_run", first_stage, last_stage, WMAR_CHAM_STAGE_HEAD, logits_dev)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (first_stage == WMAR_CHAM_STAGE_EMBED) {
         WMAR_REQUIRE(tok_dev && pos_dev, "cham_probe_run: the EMBED stage needs tok_dev and pos_dev");
@@ -371,44 +370,33 @@ int wmar_cham_probe_run(wmar_cham* g, const int64_t* tok_dev, const int32_t* pos
             default: rc = p.head(logits_dev); break;
         }
     }
-    const hipError_t e = hipStreamSynchronize(st);
-    if (rc == WMAR_OK && e != hipSuccess) { set_error("cham_probe_run: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
-    return rc;
+    return probe_wait("cham_probe_run", rc, st);
 }
 
 int64_t wmar_cham_probe_copy(wmar_cham* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine,
                              void* stream) {
     if (!g || !name) { set_error("cham_probe_copy: null argument"); return WMAR_EINVAL; }
     if (layer < 0 || layer >= g->L) { set_error("cham_probe_copy: layer %d outside 0..%d", layer, g->L - 1); return WMAR_EINVAL; }
-    const std::string n = name;
     const size_t Mpad = (size_t)g->MT * 32, D = g->D, F = g->F, Nqkv = (size_t)g->D + 2 * g->Dkv;
     const size_t lkv = (size_t)g->Mmax * g->Hkv * g->T * g->hd;
     const ChamLayer& w = g->layers[layer];
-    void* p = nullptr;
-    size_t sz = 0;
-    if (n == "x") { p = g->x; sz = Mpad * D * 2; }
-    else if (n == "y") { p = g->y; sz = Mpad * D * 2; }
-    else if (n == "hbuf") { p = g->hbuf; sz = Mpad * F * 2; }
-    else if (n == "slabs") { p = g->slabs; sz = (size_t)BG_MAXP * Mpad * D * 4; }
-    else if (n == "big_slabs") { p = g->big_slabs; sz = (size_t)BG_MAXP * Mpad * std::max(Nqkv, 2 * F) * 4; }
-    else if (n == "ssq") { p = g->ssq; sz = (size_t)((D / 16 + CHAM_STAT_KB - 1) / CHAM_STAT_KB) * Mpad * 8; }
-    else if (n == "kcache") { p = g->kcache + (size_t)layer * lkv; sz = lkv * 2; }
-    else if (n == "vcache") { p = g->vcache + (size_t)layer * lkv; sz = lkv * 2; }
-    else if (n == "rope") { p = g->rope; sz = (size_t)g->T * (g->hd / 2) * 8; }
-    else if (n == "wqkv") { p = w.wqkv; sz = Nqkv * D * 2; }
-    else if (n == "wo") { p = w.wo; sz = D * D * 2; }
-    else if (n == "w13") { p = w.w13; sz = 2 * F * D * 2; }
-    else if (n == "w2") { p = w.w2; sz = D * F * 2; }
-    else if (n == "whead") { p = g->whead; sz = (size_t)g->V * D * 2; }
-    else { set_error("cham_probe_copy: unknown buffer '%s'", name); return WMAR_EINVAL; }
-    if (!ptr_dev) return (int64_t)sz;
-    if (bytes != (int64_t)sz) { set_error("cham_probe_copy: '%s' holds %zu bytes, caller passed %lld", name, sz, (long long)bytes); return WMAR_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = to_engine ? hipMemcpyAsync(p, ptr_dev, sz, hipMemcpyDeviceToDevice, st)
-                             : hipMemcpyAsync(ptr_dev, p, sz, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("cham_probe_copy: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-    return (int64_t)sz;
+    const ProbeBuf bufs[] = {
+        {"x", g->x, Mpad * D * 2},
+        {"y", g->y, Mpad * D * 2},
+        {"hbuf", g->hbuf, Mpad * F * 2},
+        {"slabs", g->slabs, (size_t)BG_MAXP * Mpad * D * 4},
+        {"big_slabs", g->big_slabs, (size_t)BG_MAXP * Mpad * std::max(Nqkv, 2 * F) * 4},
+        {"ssq", g->ssq, (size_t)((D / 16 + CHAM_STAT_KB - 1) / CHAM_STAT_KB) * Mpad * 8},
+        {"kcache", g->kcache + (size_t)layer * lkv, lkv * 2},
+        {"vcache", g->vcache + (size_t)layer * lkv, lkv * 2},
+        {"rope", g->rope, (size_t)g->T * (g->hd / 2) * 8},
+        {"wqkv", w.wqkv, Nqkv * D * 2},
+        {"wo", w.wo, D * D * 2},
+        {"w13", w.w13, 2 * F * D * 2},
+        {"w2", w.w2, D * F * 2},
+        {"whead", g->whead, (size_t)g->V * D * 2},
+    };
+    return probe_copy("cham_probe_copy", bufs, sizeof bufs / sizeof *bufs, name, ptr_dev, bytes, to_engine, (hipStream_t)stream);
 }
 
 int wmar_cham_probe_plan(wmar_cham* g, int64_t M, char* buf, int64_t buf_len) {

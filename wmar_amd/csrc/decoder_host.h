@@ -1,7 +1,7 @@
 // Host-side scaffold shared by the decode engines (gpt.hip, rar.hip, cham.hip): weight packing and GEMM dispatch, and the
 // mechanisms every engine drives its kernels with -- captured-graph lifetime (GraphSlots), the "whole grid resident" check, the
 // block -> XCD grouping probe and the re-run behind a failed in-launch barrier.  (The allocation list and the checkpoint lookup
-// are in common.h: vqgan.hip uses them without these kernels.)
+// are in common.h: vqgan.hip uses them without these kernels.)  The test-only stage access the engines share is in probe_host.h.
 #pragma once
 #include <map>
 #include <string>

@@ -23,6 +23,7 @@
 
 #include "decoder_host.h"
 #include "decode_small.h"
+#include "probe_host.h"
 
 
 using namespace wmar;
@@ -934,9 +935,7 @@ int wmar_gpt_probe_run(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t p
     WMAR_REQUIRE(B >= 1 && B <= g->Bmax, "gpt_probe_run: batch %lld outside 1..%d", (long long)B, g->Bmax);
     WMAR_REQUIRE(pos >= 0 && pos < g->Tmax, "gpt_probe_run: position %d outside the block size %d", pos, g->Tmax);
     WMAR_REQUIRE(layer >= 0 && layer < g->L, "gpt_probe_run: layer %d outside 0..%d", layer, g->L - 1);
-    WMAR_REQUIRE(first_stage >= WMAR_GPT_STAGE_EMBED && last_stage <= WMAR_GPT_STAGE_HEAD && first_stage <= last_stage,
-                 "gpt_probe_run: stages %d..%d", first_stage, last_stage);
-    WMAR_REQUIRE(last_stage < WMAR_GPT_STAGE_HEAD || logits_dev, "gpt_probe_run: the HEAD stage needs logits_dev");
+    if (int rc = probe_stage_range("gpt_probe_run", first_stage, last_stage, WMAR_GPT_STAGE_HEAD, logits_dev)) return rc;
     WMAR_REQUIRE(first_stage > WMAR_GPT_STAGE_EMBED || tok_dev, "gpt_probe_run: the EMBED stage needs tok_dev");
     hipStream_t st = (hipStream_t)stream;
     StepIO io{(const long long*)tok_dev, 1, 0, logits_dev};
@@ -951,9 +950,7 @@ int wmar_gpt_probe_run(wmar_gpt* g, const int64_t* tok_dev, int64_t B, int32_t p
         p.xcur = p.xcur_at(s, layer);
         rc = p.run_stage(s, layer);
     }
-    const hipError_t e = hipStreamSynchronize(st);
-    if (rc == WMAR_OK && e != hipSuccess) { set_error("gpt_probe_run: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
-    if (rc != WMAR_OK) return rc;
+    if ((rc = probe_wait("gpt_probe_run", rc, st)) != WMAR_OK) return rc;
     const int f = gpt_sync_failed(g, st);
     if (f < 0) return f;
     if (f > 0) {
@@ -968,55 +965,45 @@ int64_t wmar_gpt_probe_copy(wmar_gpt* g, const char* name, int32_t layer, void* 
                             void* stream) {
     if (!g || !name) { set_error("gpt_probe_copy: null argument"); return WMAR_EINVAL; }
     if (layer < 0 || layer >= g->L) { set_error("gpt_probe_copy: layer %d outside 0..%d", layer, g->L - 1); return WMAR_EINVAL; }
-    const std::string n = name;
     const size_t Mpad = (size_t)g->MTmax * 32, D = g->D, V = g->V;
     const size_t lkv = (size_t)g->Bmax * g->H * g->Tmax * g->hd;
     const size_t fx_units = (size_t)(4 * D / 24) * (D / 16) * 64;
     const LayerW& w = g->layers[layer];
-    void* p = nullptr;
-    size_t sz = 0;
-    if (n == "x") { p = g->x; sz = Mpad * D * 4; }
-    else if (n == "x2") { p = g->x2; sz = Mpad * D * 4; }
-    else if (n == "y") { p = g->y; sz = Mpad * D * 4; }
-    else if (n == "yq") { p = g->yq; sz = D / 16 * 2 * 3 * 64 * 16; }
-    else if (n == "hbuf") { p = g->hbuf; sz = Mpad * 4 * D * 4; }
-    else if (n == "slabs") { p = g->slabs; sz = (size_t)MAX_SLABS * Mpad * D * 4; }
-    else if (n == "qkv_slabs") { p = g->qkv_slabs; sz = (size_t)MAX_SLABS * Mpad * 3 * D * 4; }
-    else if (n == "stats") { p = g->stats; sz = (size_t)STAT_CHUNKS_MAX * Mpad * 2 * 8; }
-    else if (n == "stats_q") { p = g->stats_q; sz = (size_t)QKV_SLABS_MAX * 4 * Mpad * 2 * 8; }
-    else if (n == "kcache") { p = g->kcache + (size_t)layer * lkv; sz = lkv * 4; }
-    else if (n == "vcache") { p = g->vcache + (size_t)layer * lkv; sz = lkv * 4; }
-    else if (n == "xs") { p = g->xs; sz = (size_t)SG_MAX_ROWS * D * 4; }
-    else if (n == "ys") { p = g->ys; sz = (size_t)SG_MAX_ROWS * D * 4; }
-    else if (n == "qs") { p = g->qs; sz = (size_t)SG_MAX_ROWS * D * 4; }
-    else if (n == "hs") { p = g->hs; sz = (size_t)SG_MAX_ROWS * 4 * D * 4; }
-    else if (n == "wqkv") { p = w.wqkv; sz = 3 * D * D * 4; }
-    else if (n == "wqkvx_bx") { p = w.wqkvx_bx; sz = 3 * D * D * 4; }
-    else if (n == "wproj") { p = w.wproj; sz = D * D * 4; }
-    else if (n == "wproj_bx") { p = w.wproj_bx; sz = D * D * 4; }
-    else if (n == "wfc1") { p = w.wfc1; sz = 4 * D * D * 4; }
-    else if (n == "wfc1x16") { p = w.wfc1x16; sz = fx_units * 16; }
-    else if (n == "wfc1x8") { p = w.wfc1x8; sz = fx_units * 8; }
-    else if (n == "wfc2") { p = w.wfc2; sz = 4 * D * D * 4; }
-    else if (n == "bqkv") { p = w.bqkv; sz = 3 * D * 4; }
-    else if (n == "cqkv") { p = w.cqkv; sz = 3 * D * 4; }
-    else if (n == "bproj") { p = w.bproj; sz = D * 4; }
-    else if (n == "bfc1") { p = w.bfc1; sz = 4 * D * 4; }
-    else if (n == "cfc1") { p = w.cfc1; sz = 4 * D * 4; }
-    else if (n == "bfc2") { p = w.bfc2; sz = D * 4; }
-    else if (n == "whead") { p = g->whead; sz = V * D * 4; }
-    else if (n == "bhead") { p = g->bhead; sz = V * 4; }
-    else if (n == "chead") { p = g->chead; sz = V * 4; }
-    else { set_error("gpt_probe_copy: unknown buffer '%s'", name); return WMAR_EINVAL; }
-    if (!p) { set_error("gpt_probe_copy: this engine has no buffer '%s' (its shape is not eligible for the kernel that uses it)", name); return WMAR_EINVAL; }
-    if (!ptr_dev) return (int64_t)sz;
-    if (bytes != (int64_t)sz) { set_error("gpt_probe_copy: '%s' holds %zu bytes, caller passed %lld", name, sz, (long long)bytes); return WMAR_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = to_engine ? hipMemcpyAsync(p, ptr_dev, sz, hipMemcpyDeviceToDevice, st)
-                             : hipMemcpyAsync(ptr_dev, p, sz, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("gpt_probe_copy: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-    return (int64_t)sz;
+    const ProbeBuf bufs[] = {
+        {"x", g->x, Mpad * D * 4},
+        {"x2", g->x2, Mpad * D * 4},
+        {"y", g->y, Mpad * D * 4},
+        {"yq", g->yq, D / 16 * 2 * 3 * 64 * 16},
+        {"hbuf", g->hbuf, Mpad * 4 * D * 4},
+        {"slabs", g->slabs, (size_t)MAX_SLABS * Mpad * D * 4},
+        {"qkv_slabs", g->qkv_slabs, (size_t)MAX_SLABS * Mpad * 3 * D * 4},
+        {"stats", g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2 * 8},
+        {"stats_q", g->stats_q, (size_t)QKV_SLABS_MAX * 4 * Mpad * 2 * 8},
+        {"kcache", g->kcache + (size_t)layer * lkv, lkv * 4},
+        {"vcache", g->vcache + (size_t)layer * lkv, lkv * 4},
+        {"xs", g->xs, (size_t)SG_MAX_ROWS * D * 4},
+        {"ys", g->ys, (size_t)SG_MAX_ROWS * D * 4},
+        {"qs", g->qs, (size_t)SG_MAX_ROWS * D * 4},
+        {"hs", g->hs, (size_t)SG_MAX_ROWS * 4 * D * 4},
+        {"wqkv", w.wqkv, 3 * D * D * 4},
+        {"wqkvx_bx", w.wqkvx_bx, 3 * D * D * 4},
+        {"wproj", w.wproj, D * D * 4},
+        {"wproj_bx", w.wproj_bx, D * D * 4},
+        {"wfc1", w.wfc1, 4 * D * D * 4},
+        {"wfc1x16", w.wfc1x16, fx_units * 16},
+        {"wfc1x8", w.wfc1x8, fx_units * 8},
+        {"wfc2", w.wfc2, 4 * D * D * 4},
+        {"bqkv", w.bqkv, 3 * D * 4},
+        {"cqkv", w.cqkv, 3 * D * 4},
+        {"bproj", w.bproj, D * 4},
+        {"bfc1", w.bfc1, 4 * D * 4},
+        {"cfc1", w.cfc1, 4 * D * 4},
+        {"bfc2", w.bfc2, D * 4},
+        {"whead", g->whead, V * D * 4},
+        {"bhead", g->bhead, V * 4},
+        {"chead", g->chead, V * 4},
+    };
+    return probe_copy("gpt_probe_copy", bufs, sizeof bufs / sizeof *bufs, name, ptr_dev, bytes, to_engine, (hipStream_t)stream);
 }
 
 int wmar_gpt_probe_plan(wmar_gpt* g, int64_t B, int32_t kv_len, char* buf, int64_t buf_len) {
@@ -1028,9 +1015,7 @@ int wmar_gpt_probe_plan(wmar_gpt* g, int64_t B, int32_t kv_len, char* buf, int64
     char kernels[1024];
     if (int rc = wmar_gpt_plan_info(g, B, kernels, sizeof kernels)) return rc;
     const int lrep = g->L > 1 ? 1 : 0;
-    std::string stages;
-    for (int s = WMAR_GPT_STAGE_EMBED; s <= WMAR_GPT_STAGE_HEAD; ++s)
-        if (p.has_stage(s, lrep)) stages += std::string(stages.empty() ? "" : ",") + kGptStageNames[s];
+    const std::string stages = probe_stage_list(kGptStageNames, WMAR_GPT_STAGE_HEAD + 1, [&](int s) { return p.has_stage(s, lrep); });
     std::string head = "small";
     int fc1_tiles = 0, head_tiles = 0;          // row tiles per workgroup of the k_gemm FC1 / head launches (0: another kernel)
     if (!p.small) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "decoder_host.h"
+#include "probe_host.h"
 
 namespace wmar {
 
@@ -1177,9 +1178,7 @@ int wmar_rar_probe_run(wmar_rar* g, const int64_t* tok_dev, const int64_t* cond_
     if (int rc = rar_probe_rows(g, "rar_probe_run", M, Bhalf, shared_u)) return rc;
     WMAR_REQUIRE(pos >= 0 && pos < g->T, "rar_probe_run: position %d outside 0..%d", pos, g->T - 1);
     WMAR_REQUIRE(layer >= 0 && layer < g->L, "rar_probe_run: layer %d outside 0..%d", layer, g->L - 1);
-    WMAR_REQUIRE(first_stage >= WMAR_RAR_STAGE_EMBED && last_stage <= WMAR_RAR_STAGE_HEAD && first_stage <= last_stage,
-                 "rar_probe_run: stages %d..%d", first_stage, last_stage);
-    WMAR_REQUIRE(last_stage < WMAR_RAR_STAGE_HEAD || logits_dev, "rar_probe_run: the HEAD stage needs logits_dev");
+    if (int rc = probe_stage_range("rar_probe_run", first_stage, last_stage, WMAR_RAR_STAGE_HEAD, logits_dev)) return rc;
     WMAR_REQUIRE(first_stage > WMAR_RAR_STAGE_EMBED || cond_ids_dev, "rar_probe_run: the EMBED stage needs cond_ids_dev");
     hipStream_t st = (hipStream_t)stream;
     if (shared_u) { if (int rc = rar_build_mod_u(g, st)) return rc; }
@@ -1196,9 +1195,7 @@ int wmar_rar_probe_run(wmar_rar* g, const int64_t* tok_dev, const int64_t* cond_
         else if (s == WMAR_RAR_STAGE_RESID_MLP) rc = p.poison(2 * layer + 1, 1);
     }
     if (rc == WMAR_OK) rc = p.run_stages(first_stage, last_stage, layer);
-    const hipError_t e = hipStreamSynchronize(st);
-    if (rc == WMAR_OK && e != hipSuccess) { set_error("rar_probe_run: %s", hipGetErrorString(e)); rc = WMAR_EHIP; }
-    if (rc != WMAR_OK) return rc;
+    if ((rc = probe_wait("rar_probe_run", rc, st)) != WMAR_OK) return rc;
     const int f = rar_sync_failed(g, st, true);
     if (f < 0) return f;
     if (f > 0) {
@@ -1214,68 +1211,58 @@ int wmar_rar_probe_run(wmar_rar* g, const int64_t* tok_dev, const int64_t* cond_
 int64_t wmar_rar_probe_copy(wmar_rar* g, const char* name, int32_t layer, void* ptr_dev, int64_t bytes, int32_t to_engine, void* stream) {
     if (!g || !name) { set_error("rar_probe_copy: null argument"); return WMAR_EINVAL; }
     if (layer < 0 || layer >= g->L) { set_error("rar_probe_copy: layer %d outside 0..%d", layer, g->L - 1); return WMAR_EINVAL; }
-    const std::string n = name;
     const size_t Mpad = (size_t)g->MTmax * 32, D = g->D, F = g->F, V = g->V, hd = g->hd, Ntot = (size_t)g->Ntot;
     const size_t lkv = (size_t)g->Mmax * g->H * g->T * g->hd;
     const RarLayer& w = g->layers[layer];
-    void* p = nullptr;
-    size_t sz = 0;
-    if (n == "x") { p = g->x; sz = Mpad * D * 4; }
-    else if (n == "h") { p = g->h; sz = Mpad * D * 4; }
-    else if (n == "y") { p = g->y; sz = Mpad * D * 4; }
-    else if (n == "sc") { p = g->sc; sz = Mpad * D * 4; }
-    else if (n == "hbuf") { p = g->hbuf; sz = Mpad * F * 4; }
-    else if (n == "scq") { p = g->scq; sz = D / 16 * 2 * 3 * 64 * 16; }
-    else if (n == "mod") { p = g->mod; sz = Mpad * Ntot * 4; }
-    else if (n == "mod_u") { p = g->mod_u; sz = (size_t)((g->T + 31) / 32) * 32 * Ntot * 4; }
-    else if (n == "slabs") { p = g->slabs; sz = (size_t)MAX_SLABS * Mpad * D * 4; }
-    else if (n == "qkv_slabs") { p = g->qkv_slabs; sz = (size_t)(g->bx_ok ? g->bx_qkv.S : 1) * Mpad * 3 * D * 4; }
-    else if (n == "xq") { p = g->xq; sz = D / 16 * 4 * 3 * 64 * 16; }
-    else if (n == "yq") { p = g->yq; sz = D / 16 * 4 * 3 * 64 * 16; }
-    else if (n == "hq") { p = g->hq; sz = F / 16 * 4 * 3 * 64 * 16; }
-    else if (n == "stats") { p = g->stats; sz = (size_t)STAT_CHUNKS_MAX * Mpad * 2 * 8; }
-    else if (n == "part") { p = g->part; sz = (size_t)2 * g->L * g->part_site * 8; }
-    else if (n == "logits") { p = g->logits; sz = (size_t)g->Mmax * V * 4; }
-    else if (n == "ids") { p = g->ids; sz = (size_t)g->Bmax * g->cfg.image_seq_len * 8; }
-    else if (n == "cond_ids") { p = g->cond_ids; sz = (size_t)g->Mmax * 8; }
-    else if (n == "ctr") { p = g->ctr; sz = 16; }
-    else if (n == "kcache") { p = g->kcache + (size_t)layer * lkv; sz = lkv * 4; }
-    else if (n == "vcache") { p = g->vcache + (size_t)layer * lkv; sz = lkv * 4; }
-    else if (n == "wqkv") { p = w.wqkv; sz = 3 * D * D * 4; }
-    else if (n == "wproj") { p = w.wproj; sz = D * D * 4; }
-    else if (n == "wfc1") { p = w.wfc1; sz = F * D * 4; }
-    else if (n == "wfc2") { p = w.wfc2; sz = F * D * 4; }
-    else if (n == "wqkv_bx") { p = w.wqkv_bx; sz = 3 * D * D * 4; }
-    else if (n == "wproj_bx") { p = w.wproj_bx; sz = D * D * 4; }
-    else if (n == "wfc1_bx") { p = w.wfc1_bx; sz = F * D * 4; }
-    else if (n == "wfc2_bx") { p = w.wfc2_bx; sz = F * D * 4; }
-    else if (n == "bqkv") { p = w.bqkv; sz = 3 * D * 4; }
-    else if (n == "bproj") { p = w.bproj; sz = D * 4; }
-    else if (n == "bfc1") { p = w.bfc1; sz = F * 4; }
-    else if (n == "bfc2") { p = w.bfc2; sz = D * 4; }
-    else if (n == "norm1_w") { p = w.n1w; sz = D * 4; }
-    else if (n == "norm1_b") { p = w.n1b; sz = D * 4; }
-    else if (n == "norm2_w") { p = w.n2w; sz = D * 4; }
-    else if (n == "norm2_b") { p = w.n2b; sz = D * 4; }
-    else if (n == "q_norm_w") { p = w.qnw; sz = hd * 4; }
-    else if (n == "q_norm_b") { p = w.qnb; sz = hd * 4; }
-    else if (n == "k_norm_w") { p = w.knw; sz = hd * 4; }
-    else if (n == "k_norm_b") { p = w.knb; sz = hd * 4; }
-    else if (n == "wada") { p = g->wada; sz = Ntot * D * 4; }
-    else if (n == "wada_bx") { p = g->wada_bx; sz = Ntot * D * 4; }
-    else if (n == "bada") { p = g->bada; sz = Ntot * 4; }
-    else if (n == "whead") { p = g->whead; sz = V * D * 4; }
-    else if (n == "bhead") { p = g->bhead; sz = V * 4; }
-    else { set_error("rar_probe_copy: unknown buffer '%s'", name); return WMAR_EINVAL; }
-    if (!p) { set_error("rar_probe_copy: this engine has no buffer '%s' (its shape is not eligible for the kernel that uses it)", name); return WMAR_EINVAL; }
-    if (!ptr_dev) return (int64_t)sz;
-    if (bytes != (int64_t)sz) { set_error("rar_probe_copy: '%s' holds %zu bytes, caller passed %lld", name, sz, (long long)bytes); return WMAR_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = to_engine ? hipMemcpyAsync(p, ptr_dev, sz, hipMemcpyDeviceToDevice, st)
-                             : hipMemcpyAsync(ptr_dev, p, sz, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("rar_probe_copy: %s", hipGetErrorString(e)); return WMAR_EHIP; }
-    return (int64_t)sz;
+    const ProbeBuf bufs[] = {
+        {"x", g->x, Mpad * D * 4},
+        {"h", g->h, Mpad * D * 4},
+        {"y", g->y, Mpad * D * 4},
+        {"sc", g->sc, Mpad * D * 4},
+        {"hbuf", g->hbuf, Mpad * F * 4},
+        {"scq", g->scq, D / 16 * 2 * 3 * 64 * 16},
+        {"mod", g->mod, Mpad * Ntot * 4},
+        {"mod_u", g->mod_u, (size_t)((g->T + 31) / 32) * 32 * Ntot * 4},
+        {"slabs", g->slabs, (size_t)MAX_SLABS * Mpad * D * 4},
+        {"qkv_slabs", g->qkv_slabs, (size_t)(g->bx_ok ? g->bx_qkv.S : 1) * Mpad * 3 * D * 4},
+        {"xq", g->xq, D / 16 * 4 * 3 * 64 * 16},
+        {"yq", g->yq, D / 16 * 4 * 3 * 64 * 16},
+        {"hq", g->hq, F / 16 * 4 * 3 * 64 * 16},
+        {"stats", g->stats, (size_t)STAT_CHUNKS_MAX * Mpad * 2 * 8},
+        {"part", g->part, (size_t)2 * g->L * g->part_site * 8},
+        {"logits", g->logits, (size_t)g->Mmax * V * 4},
+        {"ids", g->ids, (size_t)g->Bmax * g->cfg.image_seq_len * 8},
+        {"cond_ids", g->cond_ids, (size_t)g->Mmax * 8},
+        {"ctr", g->ctr, 16},
+        {"kcache", g->kcache + (size_t)layer * lkv, lkv * 4},
+        {"vcache", g->vcache + (size_t)layer * lkv, lkv * 4},
+        {"wqkv", w.wqkv, 3 * D * D * 4},
+        {"wproj", w.wproj, D * D * 4},
+        {"wfc1", w.wfc1, F * D * 4},
+        {"wfc2", w.wfc2, F * D * 4},
+        {"wqkv_bx", w.wqkv_bx, 3 * D * D * 4},
+        {"wproj_bx", w.wproj_bx, D * D * 4},
+        {"wfc1_bx", w.wfc1_bx, F * D * 4},
+        {"wfc2_bx", w.wfc2_bx, F * D * 4},
+        {"bqkv", w.bqkv, 3 * D * 4},
+        {"bproj", w.bproj, D * 4},
+        {"bfc1", w.bfc1, F * 4},
+        {"bfc2", w.bfc2, D * 4},
+        {"norm1_w", w.n1w, D * 4},
+        {"norm1_b", w.n1b, D * 4},
+        {"norm2_w", w.n2w, D * 4},
+        {"norm2_b", w.n2b, D * 4},
+        {"q_norm_w", w.qnw, hd * 4},
+        {"q_norm_b", w.qnb, hd * 4},
+        {"k_norm_w", w.knw, hd * 4},
+        {"k_norm_b", w.knb, hd * 4},
+        {"wada", g->wada, Ntot * D * 4},
+        {"wada_bx", g->wada_bx, Ntot * D * 4},
+        {"bada", g->bada, Ntot * 4},
+        {"whead", g->whead, V * D * 4},
+        {"bhead", g->bhead, V * 4},
+    };
+    return probe_copy("rar_probe_copy", bufs, sizeof bufs / sizeof *bufs, name, ptr_dev, bytes, to_engine, (hipStream_t)stream);
 }
 
 int wmar_rar_probe_plan(wmar_rar* g, int64_t M, int64_t Bhalf, int32_t shared_u, int32_t kv_len, char* buf, int64_t buf_len) {
@@ -1284,9 +1271,7 @@ int wmar_rar_probe_plan(wmar_rar* g, int64_t M, int64_t Bhalf, int32_t shared_u,
     WMAR_REQUIRE(kv_len >= 1 && kv_len <= g->T, "rar_probe_plan: kv_len outside 1..%d", g->T);
     RarPlan p(g, (int)M, (int)Bhalf, nullptr, nullptr, shared_u != 0);
     p.logits_out = g->logits;
-    std::string stages;
-    for (int s = WMAR_RAR_STAGE_EMBED; s <= WMAR_RAR_STAGE_HEAD; ++s)
-        if (p.has_stage(s, 0)) stages += std::string(stages.empty() ? "" : ",") + kRarStageNames[s];
+    const std::string stages = probe_stage_list(kRarStageNames, WMAR_RAR_STAGE_HEAD + 1, [&](int s) { return p.has_stage(s, 0); });
     const int ada_tiles = p.ada_bx() ? 0 : gemm_row_tiles(p.ada_mt(), (int)(g->Ntot / 32));
     const int split_tiles = gemm_split_row_tiles(p.MT);
     const int fc1_tiles = p.fc1_bx() ? 0 : gemm_row_tiles(p.MT, g->F / 32);
