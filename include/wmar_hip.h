@@ -427,6 +427,17 @@ int wmar_gumbel_key_build(uint64_t seed, int64_t vocab_size, float* rs_host, flo
 int wmar_gumbel_sample(const float* logits_dev, int64_t B, int64_t V, const float* log_rs_dev, int64_t key_row_stride,
                        int32_t use_sampling, float temp, float top_p, int32_t top_k, int64_t* tok_out_dev, void* stream);
 
+/* Probe (tests, debugging): one launch of the same sampler with the argument set the decode loop gives it (wmar_rar_generate_gumbel).
+ * logits_uncond_dev (nullable) float [B, V] and cfg_scale_dev float [n_steps]: the row sampled is u + (x - u) * cfg_scale[*step_dev];
+ * step_dev / t_dev (nullable, device int32, read as 0 when null); the token of row b lands at tok_out_dev[b * tok_out_stride + *step_dev]
+ * and, with past_append_dev, at past_append_dev[b * past_stride + *t_dev].  The call reads both counters back first and refuses
+ * (WMAR_EINVAL, nothing launched) a step or length outside those rows or the scale table; it waits for the stream. */
+int wmar_gumbel_probe_sample(const float* logits_dev, const float* logits_uncond_dev, const float* cfg_scale_dev, int32_t n_steps,
+                             const int32_t* step_dev, const int32_t* t_dev, int64_t B, int64_t V, const float* log_rs_dev,
+                             int64_t key_row_stride, int32_t use_sampling, float temp, float top_p, int32_t top_k,
+                             int64_t* tok_out_dev, int64_t tok_out_stride, int64_t* past_append_dev, int64_t past_stride,
+                             void* stream);
+
 /* gumbel_score_tok for tokens int64 [B, L]: scores_f32_dev[b,l] = -log(1 - rs)[token] and
  * scores_i64_dev[b,l] = that value truncated toward zero (what the reference returns, because it
  * accumulates into zeros_like(tokens)).  Either output may be null. */

@@ -314,6 +314,25 @@ def gumbel_vectors(args):
     print("wrote gumbel_vectors.npz", os.path.getsize(os.path.join(HERE, "gumbel_vectors.npz")), "bytes")
 
 
+def gumbel_bulk_vectors(args):
+    """5 940 decisions of engine.py's gumbel_sample on the rows of bulk_inputs.gumbel_bulk_rows: V = 37 .. 16384, logit scales
+    1 / 3 / 10 / 40, plain / half-integer / bf16-valued rows, eleven (T, top_p, top_k) settings, per-row window hashes.  Only the
+    tokens are stored; inputs are regenerated from the chunk index."""
+    import torch
+    from bulk_inputs import GUM_BULK_CHUNKS, GUM_BULK_ROWS, gumbel_bulk_rows
+    sys.path.insert(0, os.path.join(args.ref, "wmar_audio"))
+    import moshi  # noqa: F401  (engine.py imports moshi.utils.sampling)
+    from watermark import engine as E
+
+    torch.set_num_threads(8)
+    toks = np.zeros((GUM_BULK_CHUNKS, GUM_BULK_ROWS), dtype=np.int64)
+    for c in range(GUM_BULK_CHUNKS):
+        lg, h, (T, top_p, top_k) = gumbel_bulk_rows(c)
+        toks[c] = E.gumbel_sample(lg.clone(), h, use_sampling=True, temp=T, top_p=top_p, top_k=top_k).numpy()
+    np.savez_compressed(os.path.join(HERE, "gumbel_bulk.npz"), tokens=toks)
+    print("wrote gumbel_bulk.npz", os.path.getsize(os.path.join(HERE, "gumbel_bulk.npz")), "bytes")
+
+
 PROD_POS = [0, 1, 31, 32, 33, 111, 112, 113, 207, 208, 209, 255]
 PROD_RAR_STEPS = [0, 1, 2, 14, 15, 16, 17, 31, 32, 33, 62, 63, 64, 110, 111, 112, 113, 206, 207, 208, 209, 254, 255]
 
@@ -849,10 +868,13 @@ def fullsize_vq_vectors(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--only", default="", help="'gumbel' / 'chameleon' / 'prod' / 'sampler' / 'harness' / 'spatial' / 'linearh' / 'fullvq': regenerate only that fixture file")
+    ap.add_argument("--only", default="", help="'gumbel' / 'gumbelbulk' / 'chameleon' / 'prod' / 'sampler' / 'harness' / 'spatial' / 'linearh' / 'fullvq': regenerate only that fixture file")
     args = ap.parse_args()
     if args.only == "gumbel":
         gumbel_vectors(args)
+        return
+    if args.only == "gumbelbulk":
+        gumbel_bulk_vectors(args)
         return
     if args.only in ("chameleon", "prod", "sampler", "harness", "spatial", "linearh", "fullvq"):
         tmp = tempfile.mkdtemp(prefix="wmar_stubs_")
@@ -1084,6 +1106,7 @@ def main():
 
     rar_vectors(args, synth, wms, rs)
     gumbel_vectors(args)
+    gumbel_bulk_vectors(args)
     chameleon_vectors(args)
     prod_vectors(args)
     sampler_bulk_vectors(args)

@@ -26,7 +26,7 @@ SYMBOLS = [
     "wmar_vq_train_encode_backward", "wmar_vq_train_decode", "wmar_vq_train_decode_backward", "wmar_vq_train_get_grads", "wmar_mvq_create", "wmar_mvq_destroy", "wmar_mvq_device_bytes", "wmar_mvq_decode",
     "wmar_mvq_encode", "wmar_lpips_create", "wmar_lpips_destroy", "wmar_lpips_device_bytes", "wmar_lpips_forward", "wmar_lpips_backward",
     "wmar_lpips_probe_input", "wmar_lpips_probe_input_backward", "wmar_lpips_probe_relu_pool", "wmar_lpips_probe_relu_pool_backward",
-    "wmar_lpips_probe_head", "wmar_lpips_probe_head_backward", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
+    "wmar_lpips_probe_head", "wmar_lpips_probe_head_backward", "wmar_gumbel_key_build", "wmar_gumbel_sample", "wmar_gumbel_probe_sample", "wmar_gumbel_score", "wmar_gumbel_key_rows", "wmar_gumbel_score_ctx", "wmar_rar_generate_gumbel", "wmar_rar_generate_gumbel_ctx", "wmar_rar_check", "wmar_rar_launch_status",
     "wmar_cham_create", "wmar_cham_destroy", "wmar_cham_device_bytes", "wmar_cham_forward_tokens", "wmar_cham_generate_image",
     "wmar_cham_sample", "wmar_cham_probe_run", "wmar_cham_probe_copy", "wmar_cham_probe_plan",
     "wmar_rar_probe_run", "wmar_rar_probe_copy", "wmar_rar_probe_plan",
@@ -201,6 +201,7 @@ def load():
     L.wmar_rar_probe_plan.argtypes = [vp, i64, i64, i32, i32, C.c_char_p, i64]
     L.wmar_gumbel_key_build.argtypes = [C.c_uint64, i64, vp, vp, vp]
     L.wmar_gumbel_sample.argtypes = [vp, i64, i64, vp, i64, i32, f32, f32, i32, vp, vp]
+    L.wmar_gumbel_probe_sample.argtypes = [vp, vp, vp, i32, vp, vp, i64, i64, vp, i64, i32, f32, f32, i32, vp, i64, vp, i64, vp]
     L.wmar_gumbel_score.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp]
     L.wmar_gumbel_key_rows.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.wmar_gumbel_score_ctx.argtypes = [vp, i64, i64, i64, C.c_uint64, i32, vp, vp, vp, vp]

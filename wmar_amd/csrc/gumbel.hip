@@ -372,6 +372,43 @@ int wmar_gumbel_sample(const float* logits_dev, int64_t B, int64_t V, const floa
     return launch_gumbel_sample(a, (hipStream_t)stream);
 }
 
+int wmar_gumbel_probe_sample(const float* logits_dev, const float* logits_uncond_dev, const float* cfg_scale_dev, int32_t n_steps,
+                             const int32_t* step_dev, const int32_t* t_dev, int64_t B, int64_t V, const float* log_rs_dev,
+                             int64_t key_row_stride, int32_t use_sampling, float temp, float top_p, int32_t top_k,
+                             int64_t* tok_out_dev, int64_t tok_out_stride, int64_t* past_append_dev, int64_t past_stride,
+                             void* stream) {
+    WMAR_REQUIRE(logits_dev && log_rs_dev && tok_out_dev, "gumbel_probe_sample: null argument");
+    WMAR_REQUIRE(B >= 0 && B < (1ll << 31) && V >= 1 && V <= GUM_EPT * GUM_THREADS,
+                 "gumbel_probe_sample: vocabulary %lld outside 1..%d", (long long)V, GUM_EPT * GUM_THREADS);
+    WMAR_REQUIRE(key_row_stride == 0 || key_row_stride >= V, "gumbel_probe_sample: key rows of stride %lld overlap",
+                 (long long)key_row_stride);
+    WMAR_REQUIRE(!logits_uncond_dev || cfg_scale_dev, "gumbel_probe_sample: guidance without a scale table");
+    WMAR_REQUIRE(n_steps >= 1 && tok_out_stride >= 1 && (!past_append_dev || past_stride >= 1), "gumbel_probe_sample: bad strides");
+    if (B == 0) return WMAR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // the kernel indexes with what the two counters hold: read them first and refuse a write outside the buffers
+    int step = 0, t = 0;
+    if (step_dev) WMAR_HIP_CHECK(hipMemcpyAsync(&step, step_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (t_dev) WMAR_HIP_CHECK(hipMemcpyAsync(&t, t_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    WMAR_HIP_CHECK(hipStreamSynchronize(st));
+    WMAR_REQUIRE(step >= 0 && step < tok_out_stride && (!logits_uncond_dev || step < n_steps),
+                 "gumbel_probe_sample: step %d outside the token rows (%lld) or the scale table (%d)", step, (long long)tok_out_stride,
+                 n_steps);
+    WMAR_REQUIRE(!past_append_dev || (t >= 0 && t < past_stride), "gumbel_probe_sample: length %d outside the id rows (%lld)", t,
+                 (long long)past_stride);
+    GumbelArgs a{};
+    a.logits = logits_dev; a.logits_uncond = logits_uncond_dev; a.cfg_scale = cfg_scale_dev;
+    a.step_dev = (const int*)step_dev; a.t_dev = (const int*)t_dev; a.V = V; a.B = B;
+    a.log_rs = log_rs_dev; a.key_row_stride = key_row_stride;
+    a.use_sampling = use_sampling; a.temp = temp; a.top_p = top_p; a.top_k = top_k;
+    a.tok_out = (long long*)tok_out_dev; a.tok_out_stride = tok_out_stride;
+    a.past_append = (long long*)past_append_dev; a.past_stride = past_stride;
+    int rc = launch_gumbel_sample(a, st);
+    if (rc) return rc;
+    WMAR_HIP_CHECK(hipStreamSynchronize(st));
+    return WMAR_OK;
+}
+
 int wmar_gumbel_score(const int64_t* tokens_dev, int64_t B, int64_t L, int64_t V, const float* score_key_dev,
                       int64_t key_row_stride, int64_t* scores_i64_dev, float* scores_f32_dev, void* stream) {
     WMAR_REQUIRE(tokens_dev && score_key_dev, "gumbel_score: null argument");
