@@ -631,7 +631,9 @@ int wmar_vq_probe_argmin(const float* z_dev, int64_t P, int32_t E, const float* 
  * [cout, cin, ks, ks], gb_dev [cout].  The input gradient of a stride-1 conv is run_conv on the flipped, transposed weight (Hs, Ws --
  * 2 Hs, 2 Ws with up -- multiples of 8, as for any conv here), followed by a 2 x 2 sum with up; stride 2 has a gather kernel.  The
  * weight gradient is an fp32-input MFMA GEMM over K = B Ho Wo, split into K slices that a second launch adds in order.
- * kernel_buf: "dgrad=<flip+conv kernel[+k_sum2x2] | k_dgrad_s2>;wgrad=<kernel>;splits=<K slices>;bgrad=<kernel>". */
+ * gb_dev may be null (a bias-free conv, as the MaskGIT-VQGAN plan has them): the null goes to run_conv_wgrad, no bias kernel runs and
+ * the call fails if the bias part of the workspace (allocated and filled with a sentinel either way) was written.
+ * kernel_buf: "dgrad=<flip+conv kernel[+k_sum2x2] | k_dgrad_s2>;wgrad=<kernel>;splits=<K slices>;bgrad=<k_bgrad_partial | none>". */
 int wmar_vq_probe_conv_backward(const float* w_dev, int32_t cout, int32_t cin, int32_t ks, const float* x_dev, const float* gy_dev, int64_t B,
                                 int32_t Hs, int32_t Ws, int32_t stride, int32_t up, float* gx_dev, float* gw_dev, float* gb_dev,
                                 char* kernel_buf, int64_t buf_len, void* stream);

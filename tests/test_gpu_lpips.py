@@ -7,7 +7,9 @@ Gates (none measured on the code under test):
   exact layers   the input edge, ReLU, ReLU + max-pool and their backwards are bit-equal to torch's fp32 CPU result.
   head           value error normalised by the value, gradient error normalised by max|g| per image: <= 4 x the same figure of torch's
                  fp32 CPU autograd on the same data against float64, floor 4 x 2^-24 (the GroupNorm / attention gate of
-                 tests/test_gpu_vq_grad_layers.py).  The gradient at an all-zero feature vector is exactly 0.
+                 tests/test_gpu_vq_grad_layers.py).  The gradient at an all-zero feature vector is exactly 0.  Shapes: 8 x 8 (one pixel
+                 chunk), 8 x 25 (three chunks of 66 / 67 / 67 pixels) and 128 x 130 (HW / 64 = 260 chunks cut to the cap 256), with
+                 zero vectors in the first, the last and a middle chunk and next to the chunk boundaries.
   convolutions   the dense gate of tests/vq_layer_checks.py, forward and input gradient: <= 2 x a sequential fp32 chain.
   whole net      values <= 1e-5 relative; input gradient per image |got - g64|_inf / |g64|_inf <= 8 x the same figure of the fp32 CPU
                  restatement on the same data (the two gates of tests/test_gpu_vq_train.py).
@@ -166,11 +168,13 @@ def test_relu_alone_forward_and_backward_are_bit_equal_to_torch(Cc):
 
 
 # ------------------------------------------------------------------------------------------------ the head of one tap
-def _head_data(Cc, seed, B=3, H=8):
+def _head_data(Cc, seed, B=3, H=8, W=None, zero0=None):
+    """zero0: (image, y, x) of the all-zero feature vectors planted in the first operand."""
+    W = H if W is None else W
     g = torch.Generator().manual_seed(seed)
-    f0, f1 = F.relu(torch.randn(B, Cc, H, H, generator=g) + 0.3), F.relu(torch.randn(B, Cc, H, H, generator=g) + 0.3)
-    zero0 = [(0, 0, 0), (0, 3, 5), (1, 7, 7), (2, 4, 4), (2, 0, 7)]
-    zero1 = [(0, 1, 1), (1, 2, 6), (2, 4, 4)]                      # (2, 4, 4): both operands
+    f0, f1 = F.relu(torch.randn(B, Cc, H, W, generator=g) + 0.3), F.relu(torch.randn(B, Cc, H, W, generator=g) + 0.3)
+    zero0 = [(0, 0, 0), (0, 3, 5), (1, 7, 7), (2, 4, 4), (2, 0, 7)] if zero0 is None else zero0
+    zero1 = [(0, 1, 1), (1, 2, 6), zero0[3]]                       # zero0[3]: both operands
     for b, yy, xx in zero0:
         f0[b, :, yy, xx] = 0.0
     for b, yy, xx in zero1:
@@ -189,24 +193,43 @@ def _head_torch(f0, f1, w, gv, dtype):
 
 @pytest.mark.parametrize("Cc", [8, 64, 512])
 def test_head_value_and_gradient_within_four_times_torch_fp32(Cc):
+    _check_head(Cc, 8, 8, None)
+
+
+def _pixels(W, plan):
+    return [(b, p // W, p % W) for b, p in plan]
+
+
+@pytest.mark.parametrize("H,W,chunks,zeros", [
+    # 200 pixels: lp_chunks = 3, chunks [0, 66) [66, 133) [133, 200) -- zero vectors at both ends and on both sides of each boundary
+    (8, 25, 3, [(0, 0), (0, 199), (1, 100), (2, 65), (2, 66), (1, 132), (0, 133)]),
+    # 16 640 pixels: HW / 64 = 260 is cut to the cap 256, 65 pixels per chunk -- first, last and a middle chunk, and a chunk's last pixel
+    (128, 130, 256, [(0, 0), (0, 16639), (1, 128 * 65), (2, 128 * 65 - 1), (2, 64), (1, 16575)]),
+], ids=["8x25", "128x130"])
+def test_head_with_uneven_and_capped_pixel_chunks(H, W, chunks, zeros):
+    assert chunks == min(max(H * W // 64, 1), 256)               # lp_chunks restated
+    _check_head(64, H, W, _pixels(W, zeros))
+
+
+def _check_head(Cc, H, W, zero0):
     lib, L = K._lib()
-    B, H = 3, 8
-    f0, f1, w, gv, zero0 = _head_data(Cc, 300 + Cc)
+    B = 3
+    f0, f1, w, gv, zero0 = _head_data(Cc, 300 + Cc + (0 if H == W == 8 else H * W), B, H, W, zero0)
     v64, g64 = _head_torch(f0, f1, w, gv, torch.float64)
     v32, g32 = _head_torch(f0, f1, w, gv, torch.float32)
-    nz = torch.ones(B, 1, H, H, dtype=torch.bool)
+    nz = torch.ones(B, 1, H, W, dtype=torch.bool)
     for b, yy, xx in zero0:
         nz[b, 0, yy, xx] = False
         assert torch.isnan(g64[b, :, yy, xx]).all(), "float64 autograd on the bare head has no gradient at an all-zero vector"
     assert torch.isfinite(g64[nz.expand_as(g64)]).all()
     f0d, f1d, wd, gvd = _nhwc(f0), _nhwc(f1), w.cuda(), gv.cuda()
     val = torch.full((B,), float("nan"), device="cuda")
-    lib.check(L.wmar_lpips_probe_head(f0d.data_ptr(), f1d.data_ptr(), wd.data_ptr(), B, H * H, Cc, val.data_ptr(), lib.stream_ptr()))
-    g0 = torch.full((B, H, H, Cc), float("nan"), device="cuda")
-    lib.check(L.wmar_lpips_probe_head_backward(f0d.data_ptr(), f1d.data_ptr(), wd.data_ptr(), gvd.data_ptr(), B, H * H, Cc, g0.data_ptr(),
+    lib.check(L.wmar_lpips_probe_head(f0d.data_ptr(), f1d.data_ptr(), wd.data_ptr(), B, H * W, Cc, val.data_ptr(), lib.stream_ptr()))
+    g0 = torch.full((B, H, W, Cc), float("nan"), device="cuda")
+    lib.check(L.wmar_lpips_probe_head_backward(f0d.data_ptr(), f1d.data_ptr(), wd.data_ptr(), gvd.data_ptr(), B, H * W, Cc, g0.data_ptr(),
                                                lib.stream_ptr()))
-    again = torch.full((B, H, H, Cc), float("nan"), device="cuda")
-    lib.check(L.wmar_lpips_probe_head_backward(f0d.data_ptr(), f1d.data_ptr(), wd.data_ptr(), gvd.data_ptr(), B, H * H, Cc, again.data_ptr(),
+    again = torch.full((B, H, W, Cc), float("nan"), device="cuda")
+    lib.check(L.wmar_lpips_probe_head_backward(f0d.data_ptr(), f1d.data_ptr(), wd.data_ptr(), gvd.data_ptr(), B, H * W, Cc, again.data_ptr(),
                                                lib.stream_ptr()))
     assert torch.equal(g0.view(torch.int32), again.view(torch.int32)), "two runs differ"
     got = _nchw(g0, Cc).double()
@@ -218,12 +241,12 @@ def test_head_value_and_gradient_within_four_times_torch_fp32(Cc):
     scale = ref.abs().amax((1, 2, 3))
     e_g = float((d_got.abs().amax((1, 2, 3)) / scale).max())
     b_g = float((d_32.abs().amax((1, 2, 3)) / scale).max())
-    _say("head", "C=%d" % Cc, value_err=e_v, value_torch_fp32=b_v, grad_err=e_g, grad_torch_fp32=b_g)
+    _say("head", "C=%d %dx%d" % (Cc, H, W), value_err=e_v, value_torch_fp32=b_v, grad_err=e_g, grad_torch_fp32=b_g)
     assert torch.isfinite(got).all()
     for b, yy, xx in zero0:
         assert torch.all(g0[b, yy, xx] == 0), "the gradient at an all-zero feature vector must be exactly 0"
-    assert e_v <= max(TORCH_FACTOR * b_v, FLOOR), "head C=%d value: error %.3g against torch fp32's %.3g" % (Cc, e_v, b_v)
-    assert e_g <= max(TORCH_FACTOR * b_g, FLOOR), "head C=%d gradient: error %.3g against torch fp32's %.3g" % (Cc, e_g, b_g)
+    assert e_v <= max(TORCH_FACTOR * b_v, FLOOR), "head C=%d %dx%d value: error %.3g against torch fp32's %.3g" % (Cc, H, W, e_v, b_v)
+    assert e_g <= max(TORCH_FACTOR * b_g, FLOOR), "head C=%d %dx%d gradient: error %.3g against torch fp32's %.3g" % (Cc, H, W, e_g, b_g)
 
 
 # ------------------------------------------------------------------------------------------------ VGG16's convolution shapes

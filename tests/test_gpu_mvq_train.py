@@ -145,17 +145,26 @@ def test_gradients_against_float64_autograd(name, half, B):
     assert not bad, "beyond %g x torch fp32: %s" % (GATE, bad)
 
 
-def test_avgpool_backward_probe_is_bit_equal_to_torch():
+def _check_avgpool_backward(B, Ho, Wo, Cc):
     import torch.nn.functional as F
     from wmar_amd import _lib
     g = torch.Generator().manual_seed(0)
-    gy = torch.randn(2, 8, 8, 32, generator=g)                 # NHWC
-    x = torch.randn(2, 32, 16, 16, generator=g).requires_grad_(True)
+    gy = torch.randn(B, Ho, Wo, Cc, generator=g)               # NHWC
+    x = torch.randn(B, Cc, 2 * Ho, 2 * Wo, generator=g).requires_grad_(True)
     (F.avg_pool2d(x, kernel_size=2, stride=2) * gy.permute(0, 3, 1, 2)).sum().backward()
     gyd = gy.cuda().contiguous()
-    gx = torch.full((2, 16, 16, 32), float("nan"), device="cuda")
-    _lib.check(_lib.load().wmar_vq_probe_avgpool_backward(gyd.data_ptr(), 2, 8, 8, 32, gx.data_ptr(), _lib.stream_ptr(gx.device)))
+    gx = torch.full((B, 2 * Ho, 2 * Wo, Cc), float("nan"), device="cuda")
+    _lib.check(_lib.load().wmar_vq_probe_avgpool_backward(gyd.data_ptr(), B, Ho, Wo, Cc, gx.data_ptr(), _lib.stream_ptr(gx.device)))
     assert torch.equal(gx.cpu().permute(0, 3, 1, 2), x.grad)
+
+
+def test_avgpool_backward_probe_is_bit_equal_to_torch():
+    _check_avgpool_backward(2, 8, 8, 32)
+
+
+def test_avgpool_backward_probe_non_square_with_nine_channel_quads():
+    """Ho != Wo (the kernel divides a pixel index by 2 Wo and indexes the window with Wo) and C / 4 = 9, not a power of two."""
+    _check_avgpool_backward(2, 8, 12, 36)
 
 
 def test_image_edge_backward_probes_are_bit_equal_to_torch():

@@ -45,25 +45,42 @@ def _dgrad(x_shape, w, g, stride, up, step):
     return acc[:, :, off:off + Hc, off:off + Wc]
 
 
-def conv2d_backward(x, w, g, stride=1, up=False):
-    """x [B, Cin, H, W], w [Cout, Cin, ks, ks], g [B, Cout, Ho, Wo] = dL/dy -> (g_x, g_w, g_b) in float64."""
-    x, w, g = (np.asarray(t, dtype=F64) for t in (x, w, g))
-    ks = w.shape[2]
+def conv2d_wgrad(x, g, ks, stride=1, up=False):
+    """g_w [Cout, Cin, ks, ks] in float64: per tap, the contraction of g with the window of the (upsampled, padded) input."""
+    x, g = np.asarray(x, dtype=F64), np.asarray(g, dtype=F64)
     Ho, Wo = g.shape[2:]
     xp = R._prepare(x, ks, stride, up)
-    gw = np.zeros_like(w)
+    gw = np.zeros((g.shape[1], x.shape[1], ks, ks), dtype=F64)
     for dy in range(ks):
         for dx in range(ks):
             win = xp[:, :, dy:dy + stride * Ho:stride, dx:dx + stride * Wo:stride]
-            gw[:, :, dy, dx] = np.einsum("bohw,bchw->oc", g, win)
+            gw[:, :, dy, dx] = np.einsum("bohw,bchw->oc", g, win, optimize=True)
+    return gw
 
-    def step(acc, a, b):
-        return np.zeros(a, dtype=F64) if acc is None else acc + a * b
 
-    gx = _dgrad(x.shape, w, g, stride, up, step)
+def conv2d_dgrad(x_shape, w, g, stride=1, up=False):
+    """g_x [B, Cin, H, W] in float64: per tap, g contracted with that tap's weights over the output channels and scattered into the
+    frame; with `up` the 2 x 2 blocks are then summed.  (The same sum `_dgrad` forms one output channel at a time; written per tap
+    so that the wide layers take a matrix product, not Cout ks^2 passes.)"""
+    w, g = np.asarray(w, dtype=F64), np.asarray(g, dtype=F64)
+    ks = w.shape[2]
+    Ho, Wo = g.shape[2:]
+    shape, off = _frame(np.empty(x_shape), ks, stride, up)
+    acc = np.zeros(shape, dtype=F64)
+    for dy in range(ks):
+        for dx in range(ks):
+            acc[:, :, dy:dy + stride * Ho:stride, dx:dx + stride * Wo:stride] += np.einsum("bohw,oc->bchw", g, w[:, :, dy, dx], optimize=True)
+    Hc, Wc = x_shape[2] * (2 if up else 1), x_shape[3] * (2 if up else 1)
+    gx = acc[:, :, off:off + Hc, off:off + Wc]
     if up:
         gx = gx[:, :, 0::2, 0::2] + gx[:, :, 0::2, 1::2] + gx[:, :, 1::2, 0::2] + gx[:, :, 1::2, 1::2]
-    return gx, gw, g.sum((0, 2, 3))
+    return gx
+
+
+def conv2d_backward(x, w, g, stride=1, up=False):
+    """x [B, Cin, H, W], w [Cout, Cin, ks, ks], g [B, Cout, Ho, Wo] = dL/dy -> (g_x, g_w, g_b) in float64."""
+    g = np.asarray(g, dtype=F64)
+    return conv2d_dgrad(np.shape(x), w, g, stride, up), conv2d_wgrad(x, g, np.shape(w)[2], stride, up), g.sum((0, 2, 3))
 
 
 def conv2d_backward_abs(x, w, g, stride=1, up=False):
@@ -71,9 +88,10 @@ def conv2d_backward_abs(x, w, g, stride=1, up=False):
     return conv2d_backward(np.abs(x), np.abs(w), np.abs(g), stride, up)
 
 
-def conv2d_wgrad_chain(x, g, ks, stride=1, up=False, skip_tap=None, skip_image=None):
+def conv2d_wgrad_chain(x, g, ks, stride=1, up=False, skip_tap=None, skip_image=None, k_stop=None):
     """g_w as one sequential fp32 chain per weight over the K = B Ho Wo products in (b, oy, ox) order; also g_b the same way.
-    skip_tap / skip_image: a kernel that forgets that tap's weights / that image (what the dense gate must catch)."""
+    skip_tap / skip_image / k_stop: a kernel that forgets that tap's weights / that image / every product k >= k_stop, k the
+    position in (b, oy, ox) order -- the last K slice of run_conv_wgrad (what the dense gate must catch)."""
     x, g = np.asarray(x, dtype=np.float32), np.asarray(g, dtype=np.float32)
     B, Cout, Ho, Wo = g.shape
     xp = R._prepare(x, ks, stride, up)
@@ -85,6 +103,8 @@ def conv2d_wgrad_chain(x, g, ks, stride=1, up=False, skip_tap=None, skip_image=N
             continue
         for oy in range(Ho):
             for ox in range(Wo):
+                if k_stop is not None and (b * Ho + oy) * Wo + ox >= k_stop:
+                    continue
                 patch = xp[b, :, oy * stride:oy * stride + ks, ox * stride:ox * stride + ks]
                 gw = (gw.astype(F64) + g64[b, :, oy, ox][:, None, None, None] * patch[None]).astype(np.float32)
                 gb = (gb.astype(F64) + g64[b, :, oy, ox]).astype(np.float32)

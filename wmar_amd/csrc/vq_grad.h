@@ -595,7 +595,7 @@ extern "C" {
 int wmar_vq_probe_conv_backward(const float* w_dev, int32_t cout, int32_t cin, int32_t ks, const float* x_dev, const float* gy_dev, int64_t B,
                                 int32_t Hs, int32_t Ws, int32_t stride, int32_t up, float* gx_dev, float* gw_dev, float* gb_dev,
                                 char* kernel_buf, int64_t buf_len, void* stream) {
-    WMAR_REQUIRE(w_dev && x_dev && gy_dev && gx_dev && gw_dev && gb_dev && kernel_buf && buf_len > 0, "vq_probe_conv_backward: null argument");
+    WMAR_REQUIRE(w_dev && x_dev && gy_dev && gx_dev && gw_dev && kernel_buf && buf_len > 0, "vq_probe_conv_backward: null argument");
     WMAR_REQUIRE(cout >= 1 && cin >= 1 && (ks == 1 || ks == 3) && B >= 1 && B <= 1024 && Hs >= 1 && Ws >= 1, "vq_probe_conv_backward: bad shape");
     WMAR_REQUIRE(stride == 1 || (stride == 2 && ks == 3 && !up), "vq_probe_conv_backward: stride %d (2 only for 3 x 3 without upsampling)", stride);
     hipStream_t st = (hipStream_t)stream;
@@ -611,12 +611,29 @@ int wmar_vq_probe_conv_backward(const float* w_dev, int32_t cout, int32_t cin, i
     float *ups = nullptr, *ws = nullptr;
     if (stride == 1) WMAR_TRY(make_dgrad_conv(mem, w_dev, cout, cin, ks, st, &dg));
     if (up) WMAR_TRY(mem.alloc(&ups, (size_t)B * Hc * Wc * pad8(cin)));
-    WMAR_TRY(mem.alloc(&ws, wgrad_ws_elems((int)K64, cout, cin, ks)));
+    // The workspace always has the size a conv with a bias needs and starts as all-ones bytes (a NaN pattern no sum produces): a
+    // bias-free call (gb_dev null, the MaskGIT plan's convs) must leave the bias part of it as it was.
+    const size_t ws_elems = wgrad_ws_elems((int)K64, cout, cin, ks);
+    const size_t tail = (size_t)bgrad_chunks((int)K64) * cout;
+    WMAR_TRY(mem.alloc(&ws, ws_elems));
+    if (rc == WMAR_OK && hipMemsetAsync(ws, 0xff, ws_elems * sizeof(float), st) != hipSuccess) {
+        set_error("vq_probe_conv_backward: workspace memset failed"); rc = WMAR_EHIP;
+    }
     WMAR_TRY(run_conv_dgrad(stride == 1 ? &dg : nullptr, w_dev, cout, cin, ks, gy_dev, gx_dev, ups, (int)B, Hs, Ws, stride, up, st));
     WMAR_TRY(run_conv_wgrad(gy_dev, x_dev, gw_dev, gb_dev, ws, cout, cin, ks, (int)B, Hs, Ws, stride, up, st));
+    if (rc == WMAR_OK && !gb_dev) {
+        std::vector<uint32_t> host(tail);
+        const hipError_t e = hipMemcpyAsync(host.data(), ws + (ws_elems - tail), tail * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("vq_probe_conv_backward: reading the workspace back failed"); rc = WMAR_EHIP; }
+        for (size_t i = 0; rc == WMAR_OK && i < tail; ++i)
+            if (host[i] != 0xffffffffu) {
+                set_error("vq_probe_conv_backward: a bias-free weight gradient wrote the bias workspace (element %zu of %zu)", i, tail);
+                rc = WMAR_EINVAL;
+            }
+    }
     if (rc == WMAR_OK) {
-        const int n = snprintf(kernel_buf, (size_t)buf_len, "dgrad=%s;wgrad=%s;splits=%d;bgrad=k_bgrad_partial", g_dgrad_path, g_wgrad_kernel,
-                               g_wgrad_splits);
+        const int n = snprintf(kernel_buf, (size_t)buf_len, "dgrad=%s;wgrad=%s;splits=%d;bgrad=%s", g_dgrad_path, g_wgrad_kernel, g_wgrad_splits,
+                               gb_dev ? "k_bgrad_partial" : "none");
         if (!(n > 0 && n < buf_len)) { set_error("vq_probe_conv_backward: buffer of %lld bytes too small", (long long)buf_len); rc = WMAR_EINVAL; }
     }
     return probe_finish(rc, st);
