@@ -47,13 +47,13 @@ struct wmar_cham {
     long long *tok = nullptr, *ids = nullptr;
     float2* rope = nullptr;
     int *pos = nullptr, *ctr = nullptr;     // ctr: [unused, step, len]
-    // wmar_cham_generate_image waits for its stream before it returns (it frees the prompt tables): no replay outlives the call,
-    // so it never marks the graph as replaying
+    // wmar_cham_generate_image waits for its stream before it returns (it frees the prompt tables): no replay outlives the call.
+    // The shared loops (gen_loop.h) mark the graphs as replaying all the same; the drop() that then waits finds the event passed.
     GraphSlots<1> gr;
     // hooked generation (wmar_cham_generate_image_hooked): graph A (token bookkeeping + model step + guidance mix) and graph B
     // (sampler + counters) in slots and under a key of their own: kept across calls, untouched by the fused calls
     GraphSlots<2> grh;
-    unsigned long long hook_key[16] = {0};
+    GraphKey hook_key;
 };
 
 namespace {
@@ -487,93 +487,50 @@ static int cham_generate_image(wmar_cham* g, const wmar_wm_ctx* wm, const int64_
                            (const long long*)nullptr, 0ll, (const int*)nullptr, (int)B, 0);
         rc = p.step(j == maxlen - 1, g->logits);
     }
-    hipLaunchKernelGGL(k_cham_set3, dim3(1), dim3(1), 0, st, g->ctr, 0, 0, CTX);    // step = 0, len(ids row) = CTX
+    hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, 0, 0, CTX);    // step = 0, len(ids row) = CTX
     if (rc == WMAR_OK) rc = launch_status("k_set3");
 
-    SampArgs a{};
-    a.wm = make_wm(wm);
-    a.logits = hk ? hk->logits : g->logits; a.V = V; a.past = ids; a.past_stride = ids_stride; a.t_dev = g->ctr + 2;
-    a.temperature = sp->temperature; a.top_k = 0; a.use_top_p = sp->top_p >= 0; a.top_p_thr = (float)(1.0 - sp->top_p);
-    a.q = q_dev; a.q_step_stride = (long long)B * V; a.step_dev = g->ctr + 1;
-    a.scratch = a.V > 65536 ? g->scratch : nullptr;   /* rows up to 65536 entries live in the sampler's registers */
-    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = n_tokens;
-    a.past_append = ids; a.trace = nullptr; a.B = B;
+    SampArgs a = loop_samp_args(wm, hk ? hk->logits : g->logits, V, ids, ids_stride, g->ctr, sp->temperature, q_dev, B, g->scratch,
+                                (long long*)tokens_out_dev, n_tokens);
+    a.use_top_p = sp->top_p >= 0; a.top_p_thr = (float)(1.0 - sp->top_p);
     // hooked mode: the guidance mix has left the sampler (k_cfg_mix in front of the hook); allow-only and the row compaction stay
     // behind it (chameleon.py:313-327: CFG -> processors -> allow-only -> temperature -> top-p)
     if (!hk) { a.logits_img = g->logits + (long long)B * V; a.logits_uncond = g->logits + 2ll * B * V; }
     a.g_text = sp->guidance_scale_text; a.g_image = sp->guidance_scale_image; a.allow = allow_dev;
     if (allow_ids_dev && n_allow > 0) { a.gather = allow_ids_dev; a.Vsrc = V; a.V = n_allow; }
 
-    auto sample = [&](hipStream_t s) -> int {
-        int r = launch_sample_fused(a, s);
-        if (r) return r;
-        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->ctr);
-        return launch_status("k_advance3");
-    };
-    auto one_step = [&](hipStream_t s) -> int {      // consume the token sampled last, produce the next one
+    auto sample = [&](hipStream_t s) { return sample_then_advance(a, g->ctr, s); };
+    auto model_step = [&](hipStream_t s) -> int {    // consume the token sampled last -> logits of the next one
         hipLaunchKernelGGL(k_cham_step, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, g->tok, g->pos, (const long long*)nullptr,
                            (const int*)nullptr, 0, M, (const long long*)tokens_out_dev, (long long)n_tokens, (const int*)(g->ctr + 1),
                            (int)B, 1);
         ChamPlan q(g, M, s);
-        int r = q.step(true, g->logits);
-        if (r) return r;
-        return sample(s);
+        return q.step(true, g->logits);
     };
-    CfgMixArgs mx{};
-    mx.cond = g->logits; mx.img = g->logits + (long long)B * V; mx.uncond = g->logits + 2ll * B * V; mx.V = V; mx.B = B;
-    mx.g_text = sp->guidance_scale_text; mx.g_image = sp->guidance_scale_image;
-    if (hk) {
-        mx.out = hk->logits;
-        auto step_a = [&](hipStream_t s) -> int {         // consume the token sampled last -> mixed logits of the next one
-            hipLaunchKernelGGL(k_cham_step, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, g->tok, g->pos, (const long long*)nullptr,
-                               (const int*)nullptr, 0, M, (const long long*)tokens_out_dev, (long long)n_tokens, (const int*)(g->ctr + 1),
-                               (int)B, 1);
-            ChamPlan q(g, M, s);
-            if (int r = q.step(true, g->logits)) return r;
+    if (hk && rc == WMAR_OK) {
+        CfgMixArgs mx{};
+        mx.cond = g->logits; mx.img = g->logits + (long long)B * V; mx.uncond = g->logits + 2ll * B * V; mx.V = V; mx.B = B;
+        mx.g_text = sp->guidance_scale_text; mx.g_image = sp->guidance_scale_image; mx.out = hk->logits;
+        auto step_a = [&](hipStream_t s, int n) -> int {      // mixed logits of image token n: the first one from the prefill logits
+            if (n > 0) { if (int r = model_step(s)) return r; }
             return launch_cfg_mix(mx, s);
         };
-        if (rc == WMAR_OK && sp->use_graph) {
-            unsigned long long key[16] = {(unsigned long long)B, (unsigned long long)n_tokens, (unsigned long long)(uintptr_t)q_dev,
-                                          (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)hk->logits,
-                                          (unsigned long long)(uintptr_t)hk->past, (unsigned long long)ids_stride,
-                                          (unsigned long long)(uintptr_t)allow_dev, (unsigned long long)(uintptr_t)allow_ids_dev,
-                                          (unsigned long long)n_allow, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-            memcpy(&key[10], &sp->temperature, 4); memcpy(&key[11], &sp->top_p, 8);
-            memcpy(&key[12], &sp->guidance_scale_text, 4); memcpy(&key[13], &sp->guidance_scale_image, 4);
-            if (memcmp(key, g->hook_key, sizeof(key)) != 0 || !g->grh.exec[0] || !g->grh.exec[1]) {
-                g->grh.drop();
-                memset(g->hook_key, 0, sizeof(g->hook_key));
-                rc = g->grh.capture(0, step_a);
-                if (rc == WMAR_OK) rc = g->grh.capture(1, sample);
-                if (rc == WMAR_OK) memcpy(g->hook_key, key, sizeof(key));
-            }
-        }
-        for (int n = 0; n < n_tokens && rc == WMAR_OK; ++n) {
-            if (n == 0) rc = launch_cfg_mix(mx, st);       // first image token from the prefill logits
-            else rc = sp->use_graph ? g->grh.replay(0, st) : step_a(st);
-            if (rc == WMAR_OK) rc = call_hook(*hk, n, (long long)maxlen + n);
-            if (rc == WMAR_OK) rc = sp->use_graph ? g->grh.replay(1, st) : sample(st);
-        }
-    } else {
-    if (rc == WMAR_OK) rc = sample(st);                 // first image token from the prefill logits
-    if (rc == WMAR_OK && n_tokens > 1) {
-        if (sp->use_graph) {
-            // groups of four steps per captured graph (the seam between two replays is ~10 us, gpt.hip); the steps that do not
-            // fill a group are enqueued directly in front of the replays
-            const int gs = 4, lead = (n_tokens - 1) % gs;
-            for (int n = 0; n < lead && rc == WMAR_OK; ++n) rc = one_step(st);
-            if (rc == WMAR_OK && n_tokens - 1 - lead > 0) {
-                rc = g->gr.capture(0, [&](hipStream_t s) {
-                    int r = WMAR_OK;
-                    for (int k = 0; k < gs && r == WMAR_OK; ++k) r = one_step(s);
-                    return r;
-                });
-                for (int n = 1 + lead; n < n_tokens && rc == WMAR_OK; n += gs) rc = g->gr.replay(0, st);
-            }
-        } else {
-            for (int n = 1; n < n_tokens && rc == WMAR_OK; ++n) rc = one_step(st);
-        }
-    }
+        GraphKey key;
+        key.u64((uint64_t)B).u64((uint64_t)n_tokens).ptr(q_dev).ptr(tokens_out_dev).ptr(hk->logits).ptr(hk->past).u64((uint64_t)ids_stride);
+        key.ptr(allow_dev).ptr(allow_ids_dev).i32(n_allow).f32(sp->temperature).f64(sp->top_p);
+        key.f32(sp->guidance_scale_text).f32(sp->guidance_scale_image);
+        rc = hooked_loop(g->grh, g->hook_key, key, sp->use_graph != 0, n_tokens, [](int n) { return n > 0 ? 0 : -1; }, step_a,
+                         [&](int n) { return call_hook(*hk, n, (long long)maxlen + n); }, sample, st);
+    } else if (rc == WMAR_OK) {
+        // step 0 samples the first image token from the prefill logits, step n > 0 runs the model on the token sampled last.  Groups
+        // of four steps per captured graph (the seam between two replays is ~10 us, gpt.hip); step 0 and the steps that do not fill
+        // a group are enqueued directly in front of the replays.  Captured by every call.
+        const int gs = 4, lead = 1 + (n_tokens - 1) % gs;
+        rc = grouped_loop(g->gr, nullptr, GraphKey(), sp->use_graph != 0, n_tokens, lead, gs, [](int) { return 0; },
+                          [&](hipStream_t s, int n) -> int {
+                              if (n > 0) { if (int r = model_step(s)) return r; }
+                              return sample(s);
+                          }, st);
     }
     // the prompt tables are read by the prefill only; it has been enqueued on `st`, free after it ran
     hipError_t e2 = hipStreamSynchronize(st);

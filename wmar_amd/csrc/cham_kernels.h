@@ -709,7 +709,6 @@ __global__ __launch_bounds__(NWA * 64) void k_cham_attn(ChamAttnArgs a) {
     }
 }
 
-static __global__ void k_cham_set3(int* p, int a, int b, int c) { p[0] = a; p[1] = b; p[2] = c; }
 
 // per-row step bookkeeping of the generation loop
 //   mode 0: (tok, pos)[m] = table row *step of the prefill tables

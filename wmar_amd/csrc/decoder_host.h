@@ -1,13 +1,17 @@
 // Host-side scaffold shared by the decode engines (gpt.hip, rar.hip, cham.hip): weight packing and GEMM dispatch, and the
 // mechanisms every engine drives its kernels with -- captured-graph lifetime (GraphSlots), the "whole grid resident" check, the
-// block -> XCD grouping probe and the re-run behind a failed in-launch barrier.  (The allocation list and the checkpoint lookup
-// are in common.h: vqgan.hip uses them without these kernels.)  The test-only stage access the engines share is in probe_host.h.
+// block -> XCD grouping probe, the re-run behind a failed in-launch barrier and the sampler + counters tail of a generation step.
+// The generation loop itself -- graph key, capture rule, hooked and grouped step order -- is in gen_loop.h, free of HIP so that it
+// is tested on the CPU; the sampler arguments every loop fills are loop_samp_args (sampler.h).  (The allocation list and the
+// checkpoint lookup are in common.h: vqgan.hip uses them without these kernels.)  The test-only stage access the engines share
+// is in probe_host.h.
 #pragma once
 #include <map>
 #include <string>
 #include <vector>
 
 #include "decoder_kernels.h"
+#include "gen_loop.h"
 
 namespace wmar {
 
@@ -116,14 +120,16 @@ inline int stat_chunks(int KB) { const int n = (KB + WMAR_STAT_CHUNK - 1) / WMAR
 // Captured graphs of one engine: N graph / exec slots on one capture stream, and the rule for their lifetime -- an exec that may
 // still be replaying (`pending`, until the `done` event recorded behind the last replays has passed) is waited for before it is
 // destroyed, and a capture that fails leaves no graph behind.  Which slot is captured when, and when graphs are reused, is the
-// engine's policy.  Declared BEHIND the engine's DeviceArena, so that the graphs are dropped before the memory they use is freed.
+// policy of gen_loop.h.  Declared BEHIND the engine's DeviceArena, so that the graphs are dropped before the memory they use is freed.
 template <int N>
 struct GraphSlots {
+    static constexpr int n_slots = N;
     hipStream_t cap = nullptr;
     hipEvent_t done = nullptr;
     hipGraph_t graph[N] = {};
     hipGraphExec_t exec[N] = {};
     bool pending = false;
+    bool has(int slot) const { return exec[slot] != nullptr; }
     int init() {
         WMAR_HIP_CHECK(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
         WMAR_HIP_CHECK(hipEventCreate(&done));
@@ -220,6 +226,16 @@ int run_with_fallback(const char* still_up, Run&& run, Failed&& failed) {
     }
     set_error("%s", still_up);
     return WMAR_EHIP;
+}
+
+// the tail of a generation step: the sampler, then pos, step and len (ctr[0..3)) move on by one
+inline int advance3(int* ctr, hipStream_t st) {
+    hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, st, ctr);
+    return launch_status("k_advance3");
+}
+inline int sample_then_advance(const SampArgs& a, int* ctr, hipStream_t st) {
+    if (int rc = launch_sample_fused(a, st)) return rc;
+    return advance3(ctr, st);
 }
 
 }  // namespace wmar

@@ -103,6 +103,7 @@ static __global__ __launch_bounds__(64) void k_fold_bias(const float* __restrict
 }
 
 static __global__ void k_set_int(int* p, int v) { *p = v; }
+static __global__ void k_set3(int* p, int a, int b, int c) { p[0] = a; p[1] = b; p[2] = c; }
 static __global__ void k_advance3(int* p) { p[0] += 1; p[1] += 1; p[2] += 1; }  // pos, step, len
 
 // --------------------------------------------------- residual update + LayerNorm statistics

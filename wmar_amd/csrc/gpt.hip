@@ -74,9 +74,9 @@ struct wmar_gpt {
     // hooked generation (wmar_gpt_generate_hooked): the model step per attention phase (graph A), then the sampler + counters
     // (graph B, slot N_PHASE) -- slots and key of their own, so that fused and hooked calls do not evict each other's graphs
     GraphSlots<N_PHASE + 1> grh;
-    unsigned long long hook_key[12] = {0};
+    GraphKey hook_key;
     int att_nw = 2;                // waves per attention workgroup of the step being enqueued
-    unsigned long long graph_key[12] = {0};
+    GraphKey graph_key;
     // phase of the step that attends to `kv` cached rows (including the new one)
     // Measured at batch 64 with the QKV projection arriving in 7 split-K pieces (round 2): one wave per (sequence, head) is the
     // fastest variant at every cache length up to 256 (the prologue that sums the pieces runs in wave 0 while the others
@@ -1130,95 +1130,54 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
     hipStream_t st = (hipStream_t)stream;
     const long long pstride = g->Tmax + 1;
     if (int rc = gpt_inject(g, st)) return rc;
-    // past[b][0] = conditioning token; position and step counters to 0
+    // past[b][0] = conditioning token; pos = 0, step = 0, len(past row) = 1: the sampler appends at pos + 1
     WMAR_HIP_CHECK(hipMemcpy2DAsync(g->past, pstride * 8, cond_dev, 8, 8, (size_t)B, hipMemcpyDeviceToDevice, st));
-    WMAR_HIP_CHECK(hipMemsetAsync(g->pos_dev, 0, 8, st));
+    hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->pos_dev, 0, 0, 1);
 
-    SampArgs a{};
-    a.wm = make_wm(wm);
-    a.logits = g->logits; a.V = g->V; a.past = g->past; a.past_stride = pstride;
-    a.t_dev = g->step_dev;      // filled below: current length = step + 1
-    a.temperature = sp->temperature; a.top_k = sp->top_k; a.use_top_p = sp->top_p >= 0;
-    a.top_p_thr = (float)(1.0 - sp->top_p);
-    a.q = q_dev; a.q_step_stride = (long long)B * g->V; a.step_dev = g->step_dev;
-    a.scratch = a.V > 65536 ? g->scratch : nullptr;   /* rows up to 65536 entries live in the sampler's registers */
-    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = steps;
-    a.past_append = g->past; a.trace = logits_trace_dev; a.B = B;
-    // sampler reads its length from pos_dev+... : length of past at step n is n+1 == pos+1.
-    // k_sample_fused takes t from *t_dev, so point it at a dedicated counter kept at pos+1.
-    int* len_dev = g->pos_dev + 2;
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, len_dev, 1);
-    a.t_dev = len_dev;
+    SampArgs a = loop_samp_args(wm, g->logits, g->V, g->past, pstride, g->pos_dev, sp->temperature, q_dev, B, g->scratch,
+                                (long long*)tokens_out_dev, steps);
+    a.top_k = sp->top_k; a.use_top_p = sp->top_p >= 0; a.top_p_thr = (float)(1.0 - sp->top_p);
+    a.trace = logits_trace_dev;
 
     StepIO io{g->past, pstride, 1, g->logits};
-    auto one_step = [&](hipStream_t s, int phase) -> int {
-        g->att_nw = wmar_gpt::phase_waves(phase);
+    auto phase_of = [&](int n) { return g->att_phase(n + 1, B); };
+    auto one_step = [&](hipStream_t s, int n) -> int {
+        g->att_nw = wmar_gpt::phase_waves(phase_of(n));
         int rc = enqueue_step(g, B, io, s);
         if (rc) return rc;
         g->span_begin(WMAR_T_SAMPLE, s);
         rc = launch_sample_fused(a, s);
         g->span_end(s);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->pos_dev);
-        return launch_status("k_advance3");
+        return advance3(g->pos_dev, s);
     };
 
+    // Steps per captured graph: a run that stays in ONE attention phase (the default schedule) replays groups of
+    // WMAR_GRAPH_STEPS_DEFAULT steps, so that the ~10 us seam between two graph launches is paid once per group.
+    bool one_phase = true;
+    for (int n = 1; n < steps; ++n) one_phase = one_phase && phase_of(n) == phase_of(0);
+    const int gs = (one_phase && steps % WMAR_GRAPH_STEPS_DEFAULT == 0) ? WMAR_GRAPH_STEPS_DEFAULT : 1;
+    // The captured step only depends on pointers and scalars: the instantiated graphs are reused when a call repeats them (bench /
+    // harness loops) and its steps pass through attention phases that have one.
+    GraphKey key;
+    key.u64((uint64_t)B).u64((uint64_t)steps | (uint64_t)gs << 32).ptr(q_dev).ptr(tokens_out_dev).ptr(logits_trace_dev);
+    key.ptr(wm ? wm->table_dev : nullptr).u64(wm ? (uint64_t)wm->n_rows : 0);
+    key.u64(wm ? ((uint64_t)wm->seed_strategy << 40) | ((uint64_t)wm->context_size << 20) | (uint64_t)wm->spatial_dim : 0);
+    key.f32(wm ? wm->delta : 0.f).f32(sp->temperature).i32(sp->top_k).f64(sp->top_p);
+
     if (g->timing) WMAR_HIP_CHECK(hipEventRecord(g->ev0, st));
+    g->span_on = g->timing != 0 && !sp->use_graph;       // per-launch spans: eager mode only
+    const int rc = grouped_loop(g->gr, &g->graph_key, key, sp->use_graph != 0, steps, 0, gs, phase_of, one_step, st);
+    g->span_on = false;
+    if (rc) return rc;
     if (sp->use_graph) {
-        // The captured step only depends on pointers and scalars: reuse the instantiated graph
-        // when a call repeats them (bench / harness loops), re-capture otherwise.
-        unsigned long long key[12] = {(unsigned long long)B, (unsigned long long)steps, (unsigned long long)(uintptr_t)q_dev,
-                                      (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)logits_trace_dev,
-                                      wm ? (unsigned long long)(uintptr_t)wm->table_dev : 0ull,
-                                      wm ? (unsigned long long)wm->n_rows : 0ull,
-                                      wm ? ((unsigned long long)wm->seed_strategy << 40) | ((unsigned long long)wm->context_size << 20) | (unsigned long long)wm->spatial_dim : 0ull,
-                                      0ull, 0ull, (unsigned long long)sp->top_k, 0ull};
-        float fd = wm ? wm->delta : 0.f, ft = sp->temperature;
-        memcpy(&key[8], &fd, 4); memcpy(&key[9], &ft, 4); memcpy(&key[11], &sp->top_p, 8);
-        bool need[wmar_gpt::N_PHASE] = {false, false, false};
-        for (int n = 0; n < steps; ++n) need[g->att_phase(n + 1, B)] = true;
-        // Steps per captured graph: a run that stays in ONE attention phase (the default schedule) replays groups of `gs` steps, so
-        // the seam between two graph launches is paid once per group.
-        int gs = 1;
-        {
-            const int want = WMAR_GRAPH_STEPS_DEFAULT;
-            const int n_need = (int)need[0] + (int)need[1] + (int)need[2];
-            if (n_need == 1 && want > 1 && steps % want == 0) gs = want;
-        }
-        key[1] |= (unsigned long long)gs << 32;
-        if (memcmp(key, g->graph_key, sizeof(key)) != 0) g->gr.drop();
-        bool have = true;
-        for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) have = have && (!need[ph] || g->gr.exec[ph]);
-        if (!have) {
-            g->gr.drop();
-            for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) {
-                if (!need[ph]) continue;          // only the phases this run passes through are captured
-                const int rc = g->gr.capture(ph, [&](hipStream_t s) {
-                    int r = WMAR_OK;
-                    for (int k = 0; k < gs && r == WMAR_OK; ++k) r = one_step(s, ph);
-                    return r;
-                });
-                if (rc) return rc;
-            }
-            memcpy(g->graph_key, key, sizeof(key));
-        }
-        for (int n = 0; n < steps; n += gs)
-            if (int rc = g->gr.replay(g->att_phase(n + 1, B), st)) return rc;
-        if (int rc = g->gr.replayed(st)) return rc;      // (gr.done also ends the timed span)
         note_replayed(g, B, io);
-        // asynchronous: the caller's stream orders everything after the replays
+        // asynchronous: the caller's stream orders everything after the replays; gr.done behind them also ends the timed span
         if (g->timing) WMAR_HIP_CHECK(hipEventSynchronize(g->gr.done));
-    } else {
-        g->span_on = g->timing != 0;
-        int rc = WMAR_OK;
-        for (int n = 0; n < steps && rc == WMAR_OK; ++n) rc = one_step(st, g->att_phase(n + 1, B));
-        g->span_on = false;
-        if (rc) return rc;
-        if (g->timing) {
-            WMAR_HIP_CHECK(hipEventRecord(g->gr.done, st));
-            WMAR_HIP_CHECK(hipStreamSynchronize(st));
-            g->span_collect();
-        }
+    } else if (g->timing) {
+        WMAR_HIP_CHECK(hipEventRecord(g->gr.done, st));
+        WMAR_HIP_CHECK(hipStreamSynchronize(st));
+        g->span_collect();
     }
     if (g->timing) {
         float ms = 0;
@@ -1255,64 +1214,26 @@ static int gpt_generate_hooked_once(wmar_gpt* g, const wmar_sample_params* sp, c
     const long long pstride = hk.past_stride;
     if (int rc = gpt_inject(g, st)) return rc;
     WMAR_HIP_CHECK(hipMemcpy2DAsync(hk.past, pstride * 8, cond_dev, 8, 8, (size_t)B, hipMemcpyDeviceToDevice, st));
-    WMAR_HIP_CHECK(hipMemsetAsync(g->pos_dev, 0, 8, st));
-    int* len_dev = g->pos_dev + 2;
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, len_dev, 1);
+    hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->pos_dev, 0, 0, 1);      // pos = 0, step = 0, len(past row) = 1
 
-    SampArgs a{};
-    a.wm = make_wm(nullptr);
-    a.logits = hk.logits; a.V = g->V; a.past = hk.past; a.past_stride = pstride; a.t_dev = len_dev;
-    a.temperature = sp->temperature; a.top_k = sp->top_k; a.use_top_p = sp->top_p >= 0;
-    a.top_p_thr = (float)(1.0 - sp->top_p);
-    a.q = q_dev; a.q_step_stride = (long long)B * g->V; a.step_dev = g->step_dev;
-    a.scratch = a.V > 65536 ? g->scratch : nullptr;
-    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = steps;
-    a.past_append = hk.past; a.trace = nullptr; a.B = B;
+    SampArgs a = loop_samp_args(nullptr, hk.logits, g->V, hk.past, pstride, g->pos_dev, sp->temperature, q_dev, B, g->scratch,
+                                (long long*)tokens_out_dev, steps);
+    a.top_k = sp->top_k; a.use_top_p = sp->top_p >= 0; a.top_p_thr = (float)(1.0 - sp->top_p);
 
     StepIO io{hk.past, pstride, 1, hk.logits};
-    auto step_a = [&](hipStream_t s, int phase) -> int {
-        g->att_nw = wmar_gpt::phase_waves(phase);
+    auto phase_of = [&](int n) { return g->att_phase(n + 1, B); };
+    auto step_a = [&](hipStream_t s, int n) -> int {
+        g->att_nw = wmar_gpt::phase_waves(phase_of(n));
         return enqueue_step(g, B, io, s);
     };
-    auto step_b = [&](hipStream_t s) -> int {
-        if (int rc = launch_sample_fused(a, s)) return rc;
-        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->pos_dev);
-        return launch_status("k_advance3");
-    };
-    constexpr int SLOT_B = wmar_gpt::N_PHASE;
-    if (sp->use_graph) {
-        unsigned long long key[12] = {(unsigned long long)B, (unsigned long long)steps, (unsigned long long)(uintptr_t)q_dev,
-                                      (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)hk.logits,
-                                      (unsigned long long)(uintptr_t)hk.past, (unsigned long long)pstride, 0ull, 0ull, 0ull,
-                                      (unsigned long long)sp->top_k, 0ull};
-        const float ft = sp->temperature;
-        memcpy(&key[9], &ft, 4); memcpy(&key[11], &sp->top_p, 8);
-        bool need[wmar_gpt::N_PHASE] = {false, false, false};
-        for (int n = 0; n < steps; ++n) need[g->att_phase(n + 1, B)] = true;
-        if (memcmp(key, g->hook_key, sizeof(key)) != 0) g->grh.drop();
-        bool have = g->grh.exec[SLOT_B] != nullptr;
-        for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) have = have && (!need[ph] || g->grh.exec[ph]);
-        if (!have) {
-            g->grh.drop();
-            memset(g->hook_key, 0, sizeof(g->hook_key));
-            for (int ph = 0; ph < wmar_gpt::N_PHASE; ++ph) {
-                if (!need[ph]) continue;
-                if (int rc = g->grh.capture(ph, [&](hipStream_t s) { return step_a(s, ph); })) return rc;
-            }
-            if (int rc = g->grh.capture(SLOT_B, step_b)) return rc;
-            memcpy(g->hook_key, key, sizeof(key));
-        }
-    }
+    GraphKey key;
+    key.u64((uint64_t)B).u64((uint64_t)steps).ptr(q_dev).ptr(tokens_out_dev).ptr(hk.logits).ptr(hk.past).u64((uint64_t)pstride);
+    key.f32(sp->temperature).i32(sp->top_k).f64(sp->top_p);
     note_replayed(g, B, io);
-    int rc = WMAR_OK;
-    for (int n = 0; n < steps && rc == WMAR_OK; ++n) {
-        const int ph = g->att_phase(n + 1, B);
-        rc = sp->use_graph ? g->grh.replay(ph, st) : step_a(st, ph);
-        if (rc == WMAR_OK) rc = call_hook(hk, n, (long long)n + 1);
-        if (rc == WMAR_OK) rc = sp->use_graph ? g->grh.replay(SLOT_B, st) : step_b(st);
-    }
-    if (sp->use_graph) { if (int r = g->grh.replayed(st)) return rc ? rc : r; }
-    return rc;
+    // slots 0 .. N_PHASE - 1: the model step of an attention phase; the last slot: sampler + counters
+    return hooked_loop(g->grh, g->hook_key, key, sp->use_graph != 0, steps, phase_of, step_a,
+                       [&](int n) { return call_hook(hk, n, (long long)n + 1); },
+                       [&](hipStream_t s) { return sample_then_advance(a, g->pos_dev, s); }, st);
 }
 
 int wmar_gpt_generate_hooked(wmar_gpt* g, const wmar_sample_params* sp, const int64_t* cond_dev, int64_t B, int32_t steps,

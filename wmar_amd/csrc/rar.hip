@@ -362,9 +362,6 @@ static __global__ void k_rar_cond_rows(float4* sc, const float* emb, const float
     sc[((long long)kb * MT + mt) * 64 + lane] = make_float4(cv[0], cv[1], cv[2], cv[3]);
 }
 
-// tok_out[b] replicated to the unconditional half happens implicitly: ids are shared by b % B.
-static __global__ void k_set3(int* p, int a, int b, int c) { p[0] = a; p[1] = b; p[2] = c; }
-
 }  // namespace wmar
 
 using namespace wmar;
@@ -439,7 +436,7 @@ struct wmar_rar {
     // hooked generation (wmar_rar_generate_hooked): graph A (position + guidance mix) and graph B (sampler + counters) in slots and
     // under a key of their own: kept across calls, untouched by the fused calls
     GraphSlots<2> grh;
-    unsigned long long hook_key[12] = {0};
+    GraphKey hook_key;
 };
 
 namespace {
@@ -952,47 +949,20 @@ static int rar_hooked_loop(wmar_rar* g, const HookIO& hk, int M, int B, bool sha
     CfgMixArgs mx{};
     mx.cond = g->logits; mx.uncond = g->logits + (long long)B * V; mx.out = hk.logits; mx.V = V; mx.B = B;
     mx.scale = g->cfg_scale; mx.step_dev = g->ctr + 1;
-    SampArgs a{};
-    a.wm = make_wm(nullptr);
-    a.logits = hk.logits; a.V = V; a.past = hk.past; a.past_stride = hk.past_stride; a.t_dev = g->ctr + 2;
-    a.temperature = temperature; a.top_k = 0; a.use_top_p = 0; a.top_p_thr = 0.f;
-    a.q = q_dev; a.q_step_stride = (long long)B * V; a.step_dev = g->ctr + 1;
-    a.scratch = a.V > 65536 ? g->scratch : nullptr;
-    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = L;
-    a.past_append = hk.past; a.trace = nullptr; a.B = B;
-    auto step_a = [&](hipStream_t s) -> int {
+    const SampArgs a = loop_samp_args(nullptr, hk.logits, V, hk.past, hk.past_stride, g->ctr, temperature, q_dev, B, g->scratch,
+                                      (long long*)tokens_out_dev, L);
+    auto step_a = [&](hipStream_t s, int) -> int {
         RarPlan p = plan(s);
         if (!guided) return p.position(true, hk.logits);
         if (int rc = p.position(true, g->logits)) return rc;
         return launch_cfg_mix(mx, s);
     };
-    auto step_b = [&](hipStream_t s) -> int {
-        if (int rc = launch_sample_fused(a, s)) return rc;
-        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->ctr);
-        return launch_status("k_advance3");
-    };
-    if (use_graph) {
-        unsigned long long key[12] = {(unsigned long long)M, (unsigned long long)B, (unsigned long long)(uintptr_t)q_dev,
-                                      (unsigned long long)(uintptr_t)tokens_out_dev, (unsigned long long)(uintptr_t)hk.logits,
-                                      (unsigned long long)(uintptr_t)hk.past, (unsigned long long)hk.past_stride, 0ull,
-                                      (unsigned long long)shared_u, (unsigned long long)g->rm_fused, 0ull, 0ull};
-        memcpy(&key[7], &temperature, 4);
-        if (memcmp(key, g->hook_key, sizeof(key)) != 0 || !g->grh.exec[0] || !g->grh.exec[1]) {
-            g->grh.drop();
-            memset(g->hook_key, 0, sizeof(g->hook_key));
-            if (int rc = g->grh.capture(0, step_a)) return rc;
-            if (int rc = g->grh.capture(1, step_b)) return rc;
-            memcpy(g->hook_key, key, sizeof(key));
-        }
-    }
-    int rc = WMAR_OK;
-    for (int n = 0; n < L && rc == WMAR_OK; ++n) {
-        rc = use_graph ? g->grh.replay(0, st) : step_a(st);
-        if (rc == WMAR_OK) rc = call_hook(hk, n, (long long)n);
-        if (rc == WMAR_OK) rc = use_graph ? g->grh.replay(1, st) : step_b(st);
-    }
-    if (use_graph) { if (int r = g->grh.replayed(st)) return rc ? rc : r; }
-    return rc;
+    GraphKey key;
+    key.u64((uint64_t)M).u64((uint64_t)B).ptr(q_dev).ptr(tokens_out_dev).ptr(hk.logits).ptr(hk.past).u64((uint64_t)hk.past_stride);
+    key.f32(temperature).u64(shared_u).u64(g->rm_fused);
+    return hooked_loop(g->grh, g->hook_key, key, use_graph != 0, L, [](int) { return 0; }, step_a,
+                       [&](int n) { return call_hook(hk, n, (long long)n); },
+                       [&](hipStream_t s) { return sample_then_advance(a, g->ctr, s); }, st);
 }
 
 // The unconditional adaLN table mod_u [T][Ntot] (built once per engine): every unconditional row carries the "none" condition, so its
@@ -1059,14 +1029,7 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
     if (int rc = p.position(false, nullptr)) return rc;
     hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, st, g->ctr, 1, 0, 0);   // pos = 1, step = 0, len(ids) = 0
 
-    SampArgs a{};
-    a.wm = make_wm(wm);
-    a.logits = g->logits; a.V = V; a.past = g->ids; a.past_stride = L; a.t_dev = g->ctr + 2;
-    a.temperature = temperature; a.top_k = 0; a.use_top_p = 0; a.top_p_thr = 0.f;
-    a.q = q_dev; a.q_step_stride = (long long)B * V; a.step_dev = g->ctr + 1;
-    a.scratch = a.V > 65536 ? g->scratch : nullptr;   /* rows up to 65536 entries live in the sampler's registers */
-    a.tok_out = (long long*)tokens_out_dev; a.tok_out_stride = L;
-    a.past_append = g->ids; a.trace = nullptr; a.B = B;
+    SampArgs a = loop_samp_args(wm, g->logits, V, g->ids, L, g->ctr, temperature, q_dev, B, g->scratch, (long long*)tokens_out_dev, L);
     if (use_guidance) { a.logits_uncond = g->logits + (long long)B * V; a.cfg_scale = g->cfg_scale; }
     GumbelArgs ga{};
     ga.logits = g->logits; ga.logits_uncond = a.logits_uncond; ga.cfg_scale = a.cfg_scale; ga.step_dev = g->ctr + 1;
@@ -1079,32 +1042,17 @@ static int rar_generate_once(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* 
     gc.ids = g->ids; gc.ids_stride = L; gc.step_dev = g->ctr + 1; gc.h0 = h0; gc.ngram = ngram; gc.u = u_dev; gc.V = V; gc.B = B;
     gc.log_rs_out = g->gum_keys;
 
-    auto one_step = [&](hipStream_t s) -> int {
+    auto one_step = [&](hipStream_t s, int) -> int {
         RarPlan q(g, M, (int)B, nullptr, s, shared_u);
         int rc = q.position(true, g->logits);
         if (rc) return rc;
         if (ngram > 0 && (rc = launch_gumbel_ctx_keys(gc, s))) return rc;
         if ((rc = log_rs_dev ? launch_gumbel_sample(ga, s) : launch_sample_fused(a, s))) return rc;
-        hipLaunchKernelGGL(k_advance3, dim3(1), dim3(1), 0, s, g->ctr);
-        return launch_status("k_advance3");
+        return advance3(g->ctr, s);
     };
-    if (use_graph) {
-        // groups of four positions per captured graph (the seam between two replays is ~10 us, gpt.hip)
-        const int gs = (L % 4 == 0) ? 4 : 1;
-        const int rc = g->gr.capture(0, [&](hipStream_t s) {
-            int r = WMAR_OK;
-            for (int k = 0; k < gs && r == WMAR_OK; ++k) r = one_step(s);
-            return r;
-        });
-        if (rc) return rc;
-        for (int n = 0; n < L; n += gs)
-            if (int r = g->gr.replay(0, st)) return r;
-        if (int r = g->gr.replayed(st)) return r;
-    } else {
-        for (int n = 0; n < L; ++n)
-            if (int rc = one_step(st)) return rc;
-    }
-    return WMAR_OK;
+    // groups of four positions per captured graph (the seam between two replays is ~10 us, gpt.hip); captured by every call
+    const int gs = (L % 4 == 0) ? 4 : 1;
+    return grouped_loop(g->gr, nullptr, GraphKey(), use_graph != 0, L, 0, gs, [](int) { return 0; }, one_step, st);
 }
 
 static int rar_generate_impl(wmar_rar* g, const wmar_wm_ctx* wm, const int64_t* class_ids_dev, int64_t B,

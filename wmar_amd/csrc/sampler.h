@@ -67,6 +67,22 @@ struct SampArgs {
 
 int launch_sample_fused(const SampArgs& a, hipStream_t st);
 
+// The sampler of a generation loop, as far as the engines agree: rows `logits` [B, V], the token row `past` the watermark reads and
+// the sampler appends to, the counters ctr = [pos, step, len] on the device (noise and output column follow step, the append
+// follows len), tok_out[b * tok_out_stride + step].  Guidance, top-k / top-p, trace, allow-only: the engine's own, set behind this.
+inline SampArgs loop_samp_args(const wmar_wm_ctx* wm, const float* logits, long long V, long long* past, long long past_stride,
+                               const int* ctr, float temperature, const float* q, long long B, float* scratch, long long* tok_out,
+                               long long tok_out_stride) {
+    SampArgs a{};
+    a.wm = make_wm(wm);
+    a.logits = logits; a.V = V; a.past = past; a.past_stride = past_stride; a.past_append = past;
+    a.step_dev = ctr + 1; a.t_dev = ctr + 2;
+    a.temperature = temperature; a.q = q; a.q_step_stride = B * V; a.B = B;
+    a.scratch = V > 65536 ? scratch : nullptr;      // rows up to 65536 entries live in the sampler's registers
+    a.tok_out = tok_out; a.tok_out_stride = tok_out_stride;
+    return a;
+}
+
 // Guidance as a launch of its own (k_cfg_mix, watermark.hip): what k_sample_fused does to its rows in front of the watermark bias,
 // written out as fp32 [B, V] -- the hooked generation mode hands that buffer to the host's logit processor.
 struct CfgMixArgs {

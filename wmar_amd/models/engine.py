@@ -145,9 +145,8 @@ class GPTEngine(_Engine):
                                                     _lib.stream_ptr(self.device)))
         return logits
 
-    def generate(self, cond: torch.Tensor, steps: int, q: torch.Tensor, temperature=1.0, top_k=None, top_p=None,
-                 wm_ctx: Optional[_lib.WmCtx] = None, use_graph: bool = True, trace_logits: bool = False):
-        """sample_with_past: cond int64 [B], q float32 [steps, B, V] -> tokens int64 [B, steps]."""
+    def _staging(self, cond: torch.Tensor, steps: int, q: torch.Tensor, temperature, top_k, top_p, use_graph: bool):
+        """Arguments both generate calls share: cond int64 [B], B, V, the token buffer [B, steps] and the sampling parameters."""
         _require_cuda(cond, "conditioning")
         _require_cuda(q, "q")
         cond = cond.to(torch.int64).contiguous().view(-1)
@@ -155,9 +154,15 @@ class GPTEngine(_Engine):
         V = self.cfg.vocab_size
         assert q.shape == (steps, B, V) and q.dtype == torch.float32 and q.is_contiguous()
         out = torch.empty(B, steps, dtype=torch.int64, device=self.device)
-        trace = torch.empty(steps, B, V, dtype=torch.float32, device=self.device) if trace_logits else None
         sp = _lib.SampleParams(float(temperature), int(top_k) if top_k else 0,
                                float(top_p) if top_p is not None else -1.0, 1 if use_graph else 0)
+        return cond, B, V, out, sp
+
+    def generate(self, cond: torch.Tensor, steps: int, q: torch.Tensor, temperature=1.0, top_k=None, top_p=None,
+                 wm_ctx: Optional[_lib.WmCtx] = None, use_graph: bool = True, trace_logits: bool = False):
+        """sample_with_past: cond int64 [B], q float32 [steps, B, V] -> tokens int64 [B, steps]."""
+        cond, B, V, out, sp = self._staging(cond, steps, q, temperature, top_k, top_p, use_graph)
+        trace = torch.empty(steps, B, V, dtype=torch.float32, device=self.device) if trace_logits else None
         with torch.cuda.device(self.device):
             _lib.check(self._L.wmar_gpt_generate(
                 self._h, C.byref(wm_ctx) if wm_ctx is not None else None, C.byref(sp), cond.data_ptr(), B, int(steps),
@@ -171,15 +176,7 @@ class GPTEngine(_Engine):
                         use_graph: bool = True) -> torch.Tensor:
         """``generate`` with a reference-style ``logit_processor`` between the model step and the sampler (mingpt.py:348-350):
         ``processor(past_ids=int64 [B, n+1] (class token, then the n tokens so far), logits=float32 [B, V] raw head output)``."""
-        _require_cuda(cond, "conditioning")
-        _require_cuda(q, "q")
-        cond = cond.to(torch.int64).contiguous().view(-1)
-        B = cond.shape[0]
-        V = self.cfg.vocab_size
-        assert q.shape == (steps, B, V) and q.dtype == torch.float32 and q.is_contiguous()
-        out = torch.empty(B, steps, dtype=torch.int64, device=self.device)
-        sp = _lib.SampleParams(float(temperature), int(top_k) if top_k else 0,
-                               float(top_p) if top_p is not None else -1.0, 1 if use_graph else 0)
+        cond, B, V, out, sp = self._staging(cond, steps, q, temperature, top_k, top_p, use_graph)
         with torch.cuda.device(self.device):
             hook = _LogitsHook(processor, B, V, steps + 1, self.device, positional=False)
             hook.finish(self._L.wmar_gpt_generate_hooked(
@@ -432,23 +429,20 @@ class ChameleonEngine(_Engine):
         if allow_ids is not None:
             _require_cuda(allow_ids, "allow ids")
             assert allow is not None and allow_ids.dtype == torch.int32 and allow_ids.is_contiguous()
-        if processor is not None:
-            assert wm_ctx is None, "a logit processor replaces the fused watermark"
-            P = int(lens.max())
-            with torch.cuda.device(self.device):
-                hook = _LogitsHook(processor, B, V, P + int(n_tokens), self.device, positional=True)
-                hook.finish(self._L.wmar_cham_generate_image_hooked(
-                    self._h, flat.ctypes.data, lens.ctypes.data, B, C.byref(sp), allow.data_ptr() if allow is not None else None,
-                    allow_ids.data_ptr() if allow_ids is not None else None, int(allow_ids.numel()) if allow_ids is not None else 0,
-                    q.data_ptr(), int(n_tokens), out.data_ptr(), hook.logits.data_ptr(), hook.past.data_ptr(), hook.past.stride(0),
-                    hook.cfunc, None, _lib.stream_ptr(self.device)))
-            return out
+        # what both entry points take between the engine (and the watermark) in front and the hook buffers / the stream behind
+        args = (flat.ctypes.data, lens.ctypes.data, B, C.byref(sp), allow.data_ptr() if allow is not None else None,
+                allow_ids.data_ptr() if allow_ids is not None else None, int(allow_ids.numel()) if allow_ids is not None else 0,
+                q.data_ptr(), int(n_tokens), out.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(self._L.wmar_cham_generate_image(
-                self._h, C.byref(wm_ctx) if wm_ctx is not None else None, flat.ctypes.data, lens.ctypes.data, B, C.byref(sp),
-                allow.data_ptr() if allow is not None else None, allow_ids.data_ptr() if allow_ids is not None else None,
-                int(allow_ids.numel()) if allow_ids is not None else 0, q.data_ptr(), int(n_tokens), out.data_ptr(),
-                _lib.stream_ptr(self.device)))
+            if processor is not None:
+                assert wm_ctx is None, "a logit processor replaces the fused watermark"
+                hook = _LogitsHook(processor, B, V, int(lens.max()) + int(n_tokens), self.device, positional=True)
+                hook.finish(self._L.wmar_cham_generate_image_hooked(
+                    self._h, *args, hook.logits.data_ptr(), hook.past.data_ptr(), hook.past.stride(0), hook.cfunc, None,
+                    _lib.stream_ptr(self.device)))
+            else:
+                _lib.check(self._L.wmar_cham_generate_image(self._h, C.byref(wm_ctx) if wm_ctx is not None else None, *args,
+                                                            _lib.stream_ptr(self.device)))
         return out
 
     def generate_image_hooked(self, prompts, q: torch.Tensor, n_tokens: int, processor, temperature: float, top_p: Optional[float],
