@@ -133,6 +133,19 @@ typedef struct wmar_gpt wmar_gpt;
 
 int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const void* const* tensors_dev,
                     int32_t n_tensors, void* stream, wmar_gpt** out);
+/* The same with creation-time options (a bit set; 0 = exactly wmar_gpt_create -- wmar_gpt_config keeps its layout, so the options
+ * travel beside it).  Unknown bits: WMAR_EINVAL.  An option is fixed for the engine's life, so every captured graph of the engine
+ * was captured under it.
+ *   WMAR_GPT_OPT_FC2X   steps of 33..64 rows whose QKV launch is the fused k_qkvx_bx, on n_embd a multiple of 384: FC2 runs as k_fc2x
+ *                       (24-column tiles x one 32-row tile x half of K: equal workgroups, TWO uniform slabs instead of 5 / 6) and the
+ *                       next block's QKV launch (k_qkvx_bx<2>) and RESID_OUT fold two slabs.  Same products, another summation
+ *                       order of FC2's K.  Costs a second packing of mlp.2.weight, 16 n_embd^2 bytes per block (37.7 MB at 1536;
+ *                       counted by wmar_gpt_device_bytes), allocated only with the option.  Other row counts and ineligible shapes
+ *                       keep the default plan; wmar_gpt_plan_info / wmar_gpt_probe_plan report what runs (S_fc2=2 fc2_hi=0,
+ *                       fc2=k_fc2x, qkv=k_qkvx_bx<2>). */
+#define WMAR_GPT_OPT_FC2X 1u
+int wmar_gpt_create_opt(const wmar_gpt_config* cfg, uint32_t options, const char* const* names, const void* const* tensors_dev,
+                        int32_t n_tensors, void* stream, wmar_gpt** out);
 void wmar_gpt_destroy(wmar_gpt* g);
 int64_t wmar_gpt_device_bytes(const wmar_gpt* g);
 
@@ -242,7 +255,8 @@ int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* s
  *   PROJ        k_gemm / k_bx / k_bx_xr  slabs = K slices of Wproj y; k_bx_xr also folds them: x += bproj + slabs, stats (16 chunks)
  *   RESID_ATTN  k_resid_stats            x += bproj + slabs, stats                          (absent behind k_bx_xr)
  *   FC1         k_fc1x / k_gemm<GELU>    hbuf = gelu(LN2 algebra on (Wfc1 * ln2.weight) x + bfc1)
- *   FC2         k_gemm<EPI_PACKED>       slabs = S_fc2 K slices of Wfc2 hbuf (+ 1 for the first fc2_hi column tiles)
+ *   FC2         k_gemm<EPI_PACKED>       slabs = S_fc2 K slices of Wfc2 hbuf (+ 1 for the first fc2_hi column tiles);  or k_fc2x
+ *                                        (WMAR_GPT_OPT_FC2X): slab s = K half s of Wfc2 hbuf, S_fc2 = 2, fc2_hi = 0
  *   RESID_OUT   k_resid_stats            behind the last layer: x += bfc2[L-1] + slabs, stats
  *   HEAD        k_gemm<EPI_LOGITS,LN>    logits = ln_f algebra on (Whead * ln_f.weight) x + bhead
  * Small-batch plan (1..12 rows, n_embd 1536, head_dim 64): EMBED k_sembed, QKV / PROJ / FC1 / FC2 / HEAD k_sgemv<..>, ATTN k_sattn on
@@ -265,7 +279,7 @@ int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* s
  *   slabs [8] pieces of D columns, qkv_slabs [8] pieces of 3D columns (piece stride = D resp. 3D x 32 MT floats of the step's MT);
  *   stats [64][Mpad][2] fp64, stats_q [32][Mpad][2] fp64 (chunk stride = 32 MT rows of the step's MT);
  *   kcache, vcache [max_batch][H][block_size][head_dim] fp32 of block `layer`; xs, ys, qs [12][D], hs [12][4D] row-major fp32;
- *   wqkv, wqkvx_bx, wproj, wproj_bx, wfc1, wfc1x16, wfc1x8, wfc2, bqkv, cqkv, bproj, bfc1, cfc1, bfc2 of block `layer`;
+ *   wqkv, wqkvx_bx, wproj, wproj_bx, wfc1, wfc1x16, wfc1x8, wfc2, wfc2x16, wfc2x8, bqkv, cqkv, bproj, bfc1, cfc1, bfc2 of block `layer`;
  *   whead, bhead, chead.
  * wmar_gpt_probe_plan writes, for a step of B rows attending to kv_len cached rows,
  *   "small=0 MT=.. S_qx=.. nkeep=.. S_qkv=.. S_proj=.. S_fc2=.. fc2_hi=.. nch=.. nch_ln2=.. pingpong=.. x_head=x|x2 attn_waves=..

@@ -37,4 +37,7 @@ for r in range(rounds):
         res[v] += [float(x) for x in line[0].split()[1:]]
 for v in variants:
     if res[v]:
-        print(f"{v:24s} min {min(res[v]):.4f}  median {statistics.median(res[v]):.4f}  max {max(res[v]):.4f} ms/step  (n={len(res[v])})")
+        med = statistics.median(res[v])
+        mad = statistics.median([abs(x - med) for x in res[v]])
+        print(f"{v:24s} min {min(res[v]):.4f}  median {med:.4f}  MAD {mad:.4f}  max {max(res[v]):.4f} ms/step  (n={len(res[v])})")
+        print(f"{'':24s} runs " + " ".join("%.4f" % x for x in res[v]))

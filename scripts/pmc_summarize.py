@@ -3,12 +3,13 @@
 import csv, glob, json, re, sys
 
 ALG = {"attn": ("k_attn_decode", 2.0 * 64 * 1536 * 4 * 128 + 64 * 3 * 1536 * 4 * 7, "K and V rows of 128 cached positions for 64 x 24 (sequence, head) pairs + the 7 QKV pieces of the new token"),
-       "qkv": ("k_qkvx_bx", 3 * 1536 * 1536 * 4 + 7 * 64 * 1536 * 4 + 64 * 1536 * 4 + 7 * 64 * 4608 * 4, "QKV weights + x and 6 FC2 slabs (read once) + x' + 7 split-K pieces written"),
+       # (the wrappers' plan since the two-slab FC2 / QKV seam: k_qkvx_bx<2> behind k_fc2x; WMAR_NO_FC2X=1 restores 6 slabs and k_gemm)
+       "qkv": ("k_qkvx_bx", 3 * 1536 * 1536 * 4 + 3 * 64 * 1536 * 4 + 64 * 1536 * 4 + 7 * 64 * 4608 * 4, "QKV weights + x and 2 FC2 slabs (read once) + x' + 7 split-K pieces written"),
        "fc1": ("k_fc1x", 4 * 1536 * 1536 * 4 + 64 * 1536 * 4 + 64 * 6144 * 4, "FC1 weights (both packings of a tile are read: 24-column tiles) + x (read once; every workgroup re-reads it from L2) + the hidden activation written"),
-       "fc2": ("k_gemm", 4 * 1536 * 1536 * 4 + 64 * 6144 * 4 + (16 * 6 + 32 * 5) / 48 * 64 * 1536 * 4, "FC2 weights + the hidden activation (read once) + 5.33 split-K slabs written"),
+       "fc2": ("k_fc2x", 4 * 1536 * 1536 * 4 + 64 * 6144 * 4 + 2 * 64 * 1536 * 4, "FC2 weights (read once: the two row-tile workgroups of a tile share them) + the hidden activation (read once) + 2 split-K slabs written"),
        # round 4: k_bx_xr = projection + XCD-local reduction + residual fold + LN2 statistics in one launch
        "proj": ("k_bx_xr", 1536 * 1536 * 4 + 64 * 1536 * 6 + 4 * 64 * 1536 * 4 + 2 * 64 * 1536 * 4, "proj weights + the attention output as bf16 pieces (read once) + 4 split-K slabs written (read back inside the XCD: L2) + the residual stream read and written")}
-ROUND = 6
+ROUND = 7
 for role in sys.argv[1:]:
     kname, alg, what = ALG[role]
     vals = {}

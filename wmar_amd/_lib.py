@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "libwmar_hip.so")
 SYMBOLS = [
     "wmar_last_error", "wmar_version", "wmar_key_row_words", "wmar_key_table_rows", "wmar_key_table_build",
     "wmar_key_greenlist", "wmar_wm_process_logits", "wmar_sample_fused", "wmar_detect", "wmar_detect_num_ngrams",
-    "wmar_gpt_create", "wmar_gpt_destroy", "wmar_gpt_device_bytes", "wmar_gpt_decode_step", "wmar_gpt_generate",
+    "wmar_gpt_create", "wmar_gpt_create_opt", "wmar_gpt_destroy", "wmar_gpt_device_bytes", "wmar_gpt_decode_step", "wmar_gpt_generate",
     "wmar_gpt_set_timing", "wmar_gpt_set_attention_phases", "wmar_gpt_get_timing", "wmar_gpt_profile_role", "wmar_gpt_plan_info", "wmar_gpt_check",
     "wmar_gpt_probe_run", "wmar_gpt_probe_copy", "wmar_gpt_probe_plan", "wmar_rar_create", "wmar_rar_destroy",
     "wmar_rar_device_bytes", "wmar_rar_forward_position", "wmar_rar_generate", "wmar_vq_create", "wmar_vq_destroy", "wmar_vq_device_bytes",
@@ -40,6 +40,7 @@ SYMBOLS = [
 WMAR_ESHORT = -3
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR = 1, 2      # WMAR_RESAMPLE_* (Pillow's numbers)
 WMAR_ECALLBACK = -6
+GPT_OPT_FC2X = 1                                # WMAR_GPT_OPT_FC2X (wmar_gpt_create_opt)
 
 # wmar_logits_hook (include/wmar_hip.h): int (*)(void* user, int32_t step, int64_t t)
 LOGITS_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64)
@@ -168,6 +169,7 @@ def load():
     L.wmar_comm_destroy.argtypes = [vp]
     L.wmar_comm_destroy.restype = None
     L.wmar_gpt_create.argtypes = [C.POINTER(GptConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
+    L.wmar_gpt_create_opt.argtypes = [C.POINTER(GptConfig), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
     L.wmar_gpt_destroy.argtypes = [vp]
     L.wmar_gpt_destroy.restype = None
     L.wmar_gpt_device_bytes.restype = i64

@@ -787,6 +787,151 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
 #endif
 }
 
+// --------------------------------------------------------- FC2 on 24-column tiles x ONE row tile x half of K (plan variant)
+// k_gemm's FC2 at 64 rows cuts 48 column tiles 5 / 6 ways: 5.33 slabs per layer that the next layer's QKV launch re-sums in every
+// one of its 36 column groups, and workgroups of 4 or 5 pipeline rounds in one launch.  Here a workgroup owns 24 columns x one
+// 32-row tile x one HALF of K: (N / 24) x 2 x 2 equal workgroups (256 at n_embd 1536) and two uniform slabs.  The K loop is
+// k_fc1x's for a single row tile (same MFMA mix, same four-unit register ring, same refill and sched_barrier discipline), the
+// weights are mlp.2.weight in k_pack_fc1x's packing (no gamma), the hidden activation is read as it lies ([K/8][2][64], row tile
+// i only).  Epilogue: the raw partial sums as slab s in the packed layout k_gemm<EPI_PACKED> writes -- no LayerNorm algebra, no
+// GELU, no statistics.  The two row-tile workgroups of one (tile, slice) are blocks b and b + 8: equal blockIdx % 8 (one XCD
+// where the device groups blocks that way) and neighbours in dispatch order, so the second read of a weight line can hit that
+// XCD's L2 -- speed only, nothing depends on it.
+struct Fc2xArgs {
+    const float4* W16;         // [N/24][K/16][64] x 4 registers (k_pack_fc1x)
+    const float2* W8;          // [N/24][K/16][64] x 2 registers
+    const float4* Xp;          // hidden activation, packed [K/8][2][64]
+    float4* out;               // slab s at out + s * slab_stride, packed [N/8][2][64]
+    long long slab_stride;     // float4 units
+    int KU;                    // K / 16 (host: a multiple of 32 -- two slices x four waves x the four-unit ring)
+    int tiles;                 // N / 24 (host: a multiple of 4: the grid 4 * tiles is cut in groups of 16 blocks)
+    unsigned long long* trace; // dev only (-DWMAR_STAMPS)
+};
+
+static __global__ __launch_bounds__(256) void k_fc2x(Fc2xArgs a) {
+    __shared__ __attribute__((aligned(16))) float4 red[4][3][64];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // blocks b and b + 8 of a group of 16: row tiles 0 and 1 of the same (tile, slice)
+    const int bid = (int)blockIdx.x;
+    const int i = (bid >> 3) & 1;
+    const int p = ((bid >> 4) << 3) | (bid & 7);
+    const int s = p / a.tiles, tile = p - s * a.tiles;
+    // K units (16 k) of this wave inside slice s; the walk starts at a tile-dependent unit and wraps (see k_fc1x)
+    const int per = a.KU >> 3;
+    const int u0 = (s * 4 + w) * per;
+    const int rot = (tile * 5) % per;
+#define WMAR_F2_UNIT(I) (u0 + (((I) + rot) >= per ? (I) + rot - per : (I) + rot))
+
+    f32x16 acc16;
+    f32x4 acc4a, acc4b;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc16[r] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { acc4a[r] = 0.f; acc4b[r] = 0.f; }
+
+    const float4* W16 = a.W16 + (long long)tile * a.KU * 64 + lane;
+    const float2* W8 = a.W8 + (long long)tile * a.KU * 64 + lane;
+    const float4* Xp = a.Xp + i * 64 + lane;            // k-block kb of row tile i: Xp[kb * 128]
+    float4 xA[2], xB[2], xC[2], xD[2], wqA, wqB, wqC, wqD;
+    float2 w8A, w8B, w8C, w8D;
+#define WMAR_F2_LOAD(XB, WQ, W8V, UNIT)                                                          \
+    {                                                                                             \
+        const int un = (UNIT);                                                                    \
+        WQ = ld_nt(W16 + (long long)un * 64);                                                     \
+        W8V = ld_nt2(W8 + (long long)un * 64);                                                    \
+        _Pragma("unroll") for (int kb = 0; kb < 2; ++kb) XB[kb] = Xp[(long long)(un * 2 + kb) * 128]; \
+    }
+    auto fx16 = [&](f32x16& c16, float bv, float aq, int sel) {          // 32 cycles; sel = pair & 1
+        if (sel == 0) c16 = __builtin_amdgcn_mfma_f32_16x16x1f32(aq, bv, c16, 1, 0, 0);
+        if (sel == 1) c16 = __builtin_amdgcn_mfma_f32_16x16x1f32(aq, bv, c16, 1, 1, 0);
+    };
+    auto fx4 = [&](f32x4& c4a, f32x4& c4b, float bv, const float2& w8v, int pair) {     // 2 x 8 cycles
+#define WMAR_F2_CASE(PV)                                                                          \
+        if (pair == PV) {                                                                         \
+            c4a = __builtin_amdgcn_mfma_f32_4x4x1f32(w8v.x, bv, c4a, 3, PV, 0);                   \
+            c4b = __builtin_amdgcn_mfma_f32_4x4x1f32(w8v.y, bv, c4b, 3, PV, 0);                   \
+        }
+        WMAR_F2_CASE(0) WMAR_F2_CASE(1) WMAR_F2_CASE(2) WMAR_F2_CASE(3) WMAR_F2_CASE(4) WMAR_F2_CASE(5) WMAR_F2_CASE(6) WMAR_F2_CASE(7)
+#undef WMAR_F2_CASE
+    };
+// One unit (16 k = 8 pairs x 3 MFMAs); the four loads of the unit three ahead ride one per pair behind a 16x16 MFMA
+#define WMAR_F2_MMA(XC, WQ, W8V, XL, WQL, W8L, UNITL, LOADQ)                                     \
+    {                                                                                             \
+        const int un_ = (UNITL);                                                                  \
+        _Pragma("unroll") for (int pair = 0; pair < 8; ++pair) {                                  \
+            const int kb = pair >> 2, j = pair & 3, q = pair >> 1;                                \
+            const float aq = q == 0 ? WQ.x : (q == 1 ? WQ.y : (q == 2 ? WQ.z : WQ.w));            \
+            const float b0 = j == 0 ? XC[kb].x : (j == 1 ? XC[kb].y : (j == 2 ? XC[kb].z : XC[kb].w)); \
+            fx16(acc16, b0, aq, pair & 1);                                                        \
+            if (LOADQ) {                                                                          \
+                if (pair == 0) WQL = ld_nt(W16 + (long long)un_ * 64);                            \
+                if (pair == 1) W8L = ld_nt2(W8 + (long long)un_ * 64);                            \
+                if (pair == 2 || pair == 3) XL[pair - 2] = Xp[(long long)(un_ * 2 + (pair - 2)) * 128]; \
+            }                                                                                     \
+            __builtin_amdgcn_sched_barrier(0);   /* as in k_fc1x: keep the load behind its MFMA */ \
+            fx4(acc4a, acc4b, b0, W8V, pair);                                                     \
+            __builtin_amdgcn_sched_barrier(0);                                                    \
+        }                                                                                         \
+    }
+
+    WMAR_ST_BEGIN
+    WMAR_F2_LOAD(xA, wqA, w8A, WMAR_F2_UNIT(0))
+    WMAR_F2_LOAD(xB, wqB, w8B, WMAR_F2_UNIT(1))
+    WMAR_F2_LOAD(xC, wqC, w8C, WMAR_F2_UNIT(2))
+    __builtin_amdgcn_sched_barrier(0);
+    WMAR_ST_LANDED(2)
+    int it = 0;
+    for (; it + 4 < per; it += 4) {
+        WMAR_F2_MMA(xA, wqA, w8A, xD, wqD, w8D, WMAR_F2_UNIT(it + 3), true)
+        WMAR_F2_MMA(xB, wqB, w8B, xA, wqA, w8A, WMAR_F2_UNIT(it + 4), true)
+        WMAR_F2_MMA(xC, wqC, w8C, xB, wqB, w8B, WMAR_F2_UNIT(it + 5), true)
+        WMAR_F2_MMA(xD, wqD, w8D, xC, wqC, w8C, WMAR_F2_UNIT(it + 6), true)
+    }
+    // the last four units: only the first still has a unit to request (nothing is read past the wave's K range)
+    WMAR_F2_MMA(xA, wqA, w8A, xD, wqD, w8D, WMAR_F2_UNIT(it + 3), true)
+    WMAR_F2_MMA(xB, wqB, w8B, xA, wqA, w8A, 0, false)
+    WMAR_F2_MMA(xC, wqC, w8C, xB, wqB, w8B, 0, false)
+    WMAR_F2_MMA(xD, wqD, w8D, xC, wqC, w8C, 0, false)
+#undef WMAR_F2_LOAD
+#undef WMAR_F2_MMA
+#undef WMAR_F2_UNIT
+    WMAR_ST(3)
+    // "k" + "k+4" partial sums, then the cross-wave K reduction in LDS (wave order), packed store of slab s.
+    // red[w][g]: g = 0 / 1: 16x16 part, rows 16 g + lane%16, columns 4*(lane/16)..+3;  g = 2: lanes 0-31 = rows at columns 16-19,
+    // lanes 32-63 = the same rows at columns 20-23 (lanes l and l+32 of a 4x4 accumulator hold the two partial sums of row l: the swap
+    // lines them up as [columns 16-19 | columns 20-23])
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+        red[w][b][lane] = make_float4(acc16[4 * b + 0] + acc16[4 * b + 8], acc16[4 * b + 1] + acc16[4 * b + 9],
+                                      acc16[4 * b + 2] + acc16[4 * b + 10], acc16[4 * b + 3] + acc16[4 * b + 11]);
+    {
+        float v4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc4a[r]), __float_as_uint(acc4b[r]), false, false);
+            v4[r] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+        }
+        red[w][2][lane] = make_float4(v4[0], v4[1], v4[2], v4[3]);
+    }
+    __syncthreads();
+    if (w < 3) {
+        const int gi = w;
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) {
+            const float4 t = red[ww][gi][lane];
+            o[0] += t.x; o[1] += t.y; o[2] += t.z; o[3] += t.w;
+        }
+        // packed [N/8][2][64]: column n, row m of tile i -> ((n / 8) * 2 + i) * 64 + m + 32 * ((n / 4) & 1); 24 columns = k-blocks
+        // 3 tile .. 3 tile + 2: the 16x16 part fills the first two (column 4*(lane/16)), the 4x4 part the third, lane for lane
+        const int kbn = gi < 2 ? tile * 3 + (lane >> 5) : tile * 3 + 2;
+        const int ln = gi < 2 ? 16 * gi + (lane & 15) + 32 * ((lane >> 4) & 1) : lane;
+        st_out(a.out + (long long)s * a.slab_stride + ((long long)kbn * 2 + i) * 64 + ln, make_float4(o[0], o[1], o[2], o[3]));
+    }
+    WMAR_ST_END(a.trace, blockIdx.x)
+}
+
 // ------------------------------------------------- residual fold + LN1 statistics + QKV projection in ONE launch
 // The QKV GEMM of layer l consumes the residual stream  x' = x + bias + sum_s slab[s]  of layer l-1's FC2 (k_resid_stats does
 // that fold as a launch of its own for the other consumers).  Here the fold happens while the operand is staged:

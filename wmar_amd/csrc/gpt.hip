@@ -33,6 +33,8 @@ struct LayerW {
     float4 *wqkv, *wproj, *wfc1, *wfc2;
     float4* wfc1x16 = nullptr;   // FC1 in k_fc1x's 24-column packing (null: shape not eligible)
     float2* wfc1x8 = nullptr;
+    float4* wfc2x16 = nullptr;   // FC2 in the same packing for k_fc2x (null: WMAR_GPT_OPT_FC2X not asked for, or shape not eligible)
+    float2* wfc2x8 = nullptr;
     float4* wqkvx_bx = nullptr;  // QKV weights in k_qkvx_bx's 16-k step order (null: shape not eligible)
     float4* wproj_bx = nullptr;  // output projection in k_pack_bx order for k_bx (null: shape not eligible)
     float *bqkv, *bproj, *bfc1, *bfc2, *cqkv, *cfc1;
@@ -182,6 +184,7 @@ struct StepPlan {
     ResidArgs r{};
     int S_qkv = 1, S_proj = 1, S_fc2 = 1;
     int fc2_hi = 0;      // FC2: the first fc2_hi column tiles take S_fc2 + 1 K slices so that exactly 256 workgroups exist
+    bool fc2_x = false;  // plan variant (WMAR_GPT_OPT_FC2X at creation): FC2 = k_fc2x, two uniform slabs, QKV and RESID_OUT fold two
     // fused residual fold + QKV projection (k_qkvx): column groups x K slices; 0 = not applicable to this shape (k_gemm path)
     int S_qx = 0;
     float4* xcur = nullptr;   // residual stream buffer the next launch reads (the fused fold ping-pongs between x and x2)
@@ -224,6 +227,9 @@ struct StepPlan {
         if (proj_bx) S_proj = D / BX_KSLICE;
         proj_xr = xr_shape() && g->xcd_ok;
         nch_ln2 = proj_xr ? 16 : nch;
+        // the FC2 / QKV seam on two slabs: 64-row steps whose QKV launch is the fused k_qkvx_bx, on an engine created with the option
+        // (the second packing of W2 exists only then); every other row count keeps the plan above
+        if (g->layers[0].wfc2x16 && MT == 2 && D % 384 == 0 && g->force_s[2] <= 0 && qkv_bx()) { fc2_x = true; S_fc2 = 2; fc2_hi = 0; }
     }
     void dbg(const void* p, long long bytes) {
 #ifdef WMAR_DEV_KNOBS
@@ -447,6 +453,16 @@ struct StepPlan {
             g->span_end(st);
             return rc;
         }
+        if (fc2_x) {
+            Fc2xArgs x{};
+            x.W16 = g->layers[l].wfc2x16; x.W8 = g->layers[l].wfc2x8; x.Xp = g->hbuf; x.out = g->slabs; x.slab_stride = act;
+            x.KU = 4 * D / 16; x.tiles = D / 24;
+            x.trace = g->stamp_slot(l, 4);
+            g->span_begin(WMAR_T_FC2, st);
+            hipLaunchKernelGGL(k_fc2x, dim3((unsigned)(4 * x.tiles)), dim3(256), 0, st, x);
+            g->span_end(st);
+            return launch_status("k_fc2x");
+        }
         GemmArgs q = base();
         q.Wp = g->layers[l].wfc2; q.Xp = g->hbuf; q.KB = KBF; q.NT = D / 32;
         q.out_packed = g->slabs; q.slab_stride = act; q.n_hi = fc2_hi;
@@ -594,6 +610,12 @@ extern "C" {
 
 int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const void* const* tensors_dev,
                     int32_t n_tensors, void* stream, wmar_gpt** out) {
+    return wmar_gpt_create_opt(cfg, 0u, names, tensors_dev, n_tensors, stream, out);
+}
+
+int wmar_gpt_create_opt(const wmar_gpt_config* cfg, uint32_t options, const char* const* names, const void* const* tensors_dev,
+                        int32_t n_tensors, void* stream, wmar_gpt** out) {
+    WMAR_REQUIRE((options & ~(uint32_t)WMAR_GPT_OPT_FC2X) == 0, "gpt_create: unknown option bits 0x%x", options);
     WMAR_REQUIRE(cfg && names && tensors_dev && out, "gpt_create: null argument");
     WMAR_REQUIRE(cfg->n_embd % cfg->n_head == 0, "n_embd %% n_head != 0");
     const int D = cfg->n_embd, H = cfg->n_head, hd = D / H, V = cfg->vocab_size, L = cfg->n_layer;
@@ -699,6 +721,17 @@ int wmar_gpt_create(const wmar_gpt_config* cfg, const char* const* names, const 
         WMAR_TRY(g->mem.alloc(&w.wfc2, (size_t)4 * D * D / 4));
         WMAR_TRY(pack(f2w, w.wfc2, D, 4 * D, 0, st));
         WMAR_TRY(copy_vec(g, &w.bfc2, f2b, D, st));
+        if ((options & WMAR_GPT_OPT_FC2X) && D % 384 == 0 && g->MTmax >= 2) {
+            // 33..64 rows under the option: FC2 on 24-column tiles (k_fc2x), W2 once more in k_fc1x's packing, no gamma (16 D^2 bytes
+            // per layer; the 32-column packing above serves every other batch size)
+            const size_t units = (size_t)(D / 24) * (4 * D / 16) * 64;
+            WMAR_TRY(g->mem.alloc(&w.wfc2x16, units));
+            WMAR_TRY(g->mem.alloc(&w.wfc2x8, units));
+            if (rc == WMAR_OK) {
+                hipLaunchKernelGGL(k_pack_fc1x, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, f2w, (const float*)nullptr, w.wfc2x16, w.wfc2x8, D, 4 * D);
+                rc = launch_status("k_pack_fc1x");
+            }
+        }
     }
     // small-batch path (decode_small.h): the weights once more in the checkpoint's row-major layout (LayerNorm not folded), 5.5 GB at
     // 48 layers x 1536.  Shapes: n_embd = two K segments of 768, head_dim 64.  WMAR_NO_SMALL=1 at creation keeps 1..12 rows on the
@@ -913,7 +946,8 @@ int wmar_gpt_plan_info(wmar_gpt* g, int64_t B, char* buf, int64_t buf_len) {
     else snprintf(proj, sizeof proj, "k_gemm<EPI_PACKED> (fp32 MFMA, %d K slices)", p.S_proj);
     if (p.fc1_x()) snprintf(fc1, sizeof fc1, "k_fc1x (fp32 MFMA, 24-column tiles, whole K)");
     else snprintf(fc1, sizeof fc1, "k_gemm<EPI_GELU,LN> (fp32 MFMA, whole K)");
-    snprintf(fc2, sizeof fc2, "k_gemm<EPI_PACKED> (fp32 MFMA, %d%s K slices)", p.S_fc2, p.fc2_hi > 0 ? "/+1" : "");
+    if (p.fc2_x) snprintf(fc2, sizeof fc2, "k_fc2x (fp32 MFMA, 24-column tiles x one row tile, %d K slices)", p.S_fc2);
+    else snprintf(fc2, sizeof fc2, "k_gemm<EPI_PACKED> (fp32 MFMA, %d%s K slices)", p.S_fc2, p.fc2_hi > 0 ? "/+1" : "");
     // attention: the waves per (sequence, head) follow the cache length (att_phase); reported at 1, block_size / 2 and block_size rows
     char attn[96];
     const int w0 = wmar_gpt::phase_waves(g->att_phase(1, B)), w1 = wmar_gpt::phase_waves(g->att_phase(g->Tmax / 2, B)),
@@ -968,6 +1002,7 @@ int64_t wmar_gpt_probe_copy(wmar_gpt* g, const char* name, int32_t layer, void* 
     const size_t Mpad = (size_t)g->MTmax * 32, D = g->D, V = g->V;
     const size_t lkv = (size_t)g->Bmax * g->H * g->Tmax * g->hd;
     const size_t fx_units = (size_t)(4 * D / 24) * (D / 16) * 64;
+    const size_t f2_units = (size_t)(D / 24) * (4 * D / 16) * 64;
     const LayerW& w = g->layers[layer];
     const ProbeBuf bufs[] = {
         {"x", g->x, Mpad * D * 4},
@@ -993,6 +1028,8 @@ int64_t wmar_gpt_probe_copy(wmar_gpt* g, const char* name, int32_t layer, void* 
         {"wfc1x16", w.wfc1x16, fx_units * 16},
         {"wfc1x8", w.wfc1x8, fx_units * 8},
         {"wfc2", w.wfc2, 4 * D * D * 4},
+        {"wfc2x16", w.wfc2x16, f2_units * 16},
+        {"wfc2x8", w.wfc2x8, f2_units * 8},
         {"bqkv", w.bqkv, 3 * D * 4},
         {"cqkv", w.cqkv, 3 * D * 4},
         {"bproj", w.bproj, D * 4},

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Optional
 
 import numpy as np
@@ -21,9 +22,10 @@ class _Engine:
 
     _prefix = ""  # "wmar_gpt", ...
 
-    def _create(self, config, state: Dict[str, torch.Tensor], keep, device, max_batch: int, dtype=torch.float32):
+    def _create(self, config, state: Dict[str, torch.Tensor], keep, device, max_batch: int, dtype=torch.float32, options=None):
         """Creates the engine from the entries of `state` whose name `keep` accepts, moved to `device` as contiguous `dtype`
-        (the engine repacks them into its own HBM buffers: the copies made here are dropped on return)."""
+        (the engine repacks them into its own HBM buffers: the copies made here are dropped on return).  `options`: the bit set of
+        `<prefix>_create_opt` instead of `<prefix>_create`."""
         self.device = torch.device(device)
         self.max_batch = int(max_batch)
         self._L = _lib.load()
@@ -31,8 +33,12 @@ class _Engine:
         names, ptrs, n = _lib.tensor_table(tensors)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(getattr(self._L, self._prefix + "_create")(C.byref(config), names, ptrs, n, _lib.stream_ptr(self.device),
-                                                                  C.byref(h)))
+            if options is None:
+                rc = getattr(self._L, self._prefix + "_create")(C.byref(config), names, ptrs, n, _lib.stream_ptr(self.device), C.byref(h))
+            else:
+                rc = getattr(self._L, self._prefix + "_create_opt")(C.byref(config), int(options), names, ptrs, n,
+                                                                    _lib.stream_ptr(self.device), C.byref(h))
+            _lib.check(rc)
         self._h = h
 
     def __del__(self):
@@ -128,11 +134,19 @@ class GPTEngine(_Engine):
     (deps/taming/modules/transformer/mingpt.py:183-214, 326-368)."""
 
     _prefix = "wmar_gpt"
+    DEFAULT_FC2X = True     # the measured A/B decides this (DESIGN section 6)
 
-    def __init__(self, cfg: GPTConfig, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda"):
+    def __init__(self, cfg: GPTConfig, state: Dict[str, torch.Tensor], max_batch: int = 64, device="cuda", fc2x: Optional[bool] = None):
+        """fc2x: ask for the two-slab FC2 / QKV seam at 33..64 rows (WMAR_GPT_OPT_FC2X, include/wmar_hip.h; the library applies it
+        only where the shape is eligible).  None: DEFAULT_FC2X, unless WMAR_NO_FC2X is set in the environment (A/B runs) or
+        max_batch <= 32 (the second packing of mlp.2.weight would never be read)."""
         self.cfg = cfg
+        if fc2x is None:
+            fc2x = self.DEFAULT_FC2X and not os.environ.get("WMAR_NO_FC2X") and int(max_batch) > 32
+        self.fc2x = bool(fc2x)
         c = _lib.GptConfig(cfg.vocab_size, cfg.block_size, cfg.n_layer, cfg.n_head, cfg.n_embd, int(max_batch))
-        self._create(c, state, lambda k: not k.endswith("attn.mask"), device, max_batch)
+        self._create(c, state, lambda k: not k.endswith("attn.mask"), device, max_batch,
+                     options=_lib.GPT_OPT_FC2X if self.fc2x else 0)
 
     def decode_step(self, tok: torch.Tensor, pos: int) -> torch.Tensor:
         """One token per sequence at position `pos` -> logits [B, V]."""
