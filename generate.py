@@ -60,6 +60,10 @@ def get_parser():
                         help="with --sync true: 'pkg.module:callable'; callable(args, device) returns a SyncManager-like object "
                              "(add_sync / remove_sync) or a WAM-like one (embed(imgs, msg) -> {'imgs_w'}, detect(imgs) -> {'preds'}) "
                              "instead of the networks --syncpath names")
+    parser.add_argument("--sync_embedder", type=str, default="torch", choices=["torch", "native"],
+                        help="with --sync true and a WAM --syncpath (wam_mit*.pth): 'native' runs add_sync's embedder on the device "
+                             "(wmar_wam_add_sync) from the checkpoint's embedder.* tensors, without the WAM checkout; the extractor "
+                             "of remove_sync still comes from the checkout or from --sync_factory")
     parser.add_argument("--seed", type=int, nargs="?", help="seed", default=42)
     parser.add_argument("--synthetic", type=str2bool, default=False, help="random-init weights instead of checkpoints")
     parser.add_argument("--synthetic_config", type=str, default="full", choices=["full", "harness"],
@@ -92,6 +96,12 @@ def check_wm_args(args):
         raise ValueError(f"--sync_factory {sync_factory!r}: expected pkg.module:callable")
     if getattr(args, "sync", False) and not sync_factory and not getattr(args, "syncpath", None):
         raise ValueError("--sync true needs --syncpath (wam_mit.pth | syncmodel.jit.pt) or --sync_factory")
+    if getattr(args, "sync_embedder", "torch") == "native":
+        if not getattr(args, "sync", False):
+            raise ValueError("--sync_embedder native is only read with --sync true")
+        if "wam_mit" not in str(getattr(args, "syncpath", None) or ""):
+            raise ValueError(f"--sync_embedder native needs a WAM checkpoint (--syncpath .../wam_mit*.pth), got {getattr(args, 'syncpath', None)!r}: "
+                             "SyncSeal has no native embedder")
 
 
 def main():

@@ -905,6 +905,62 @@ int wmar_sync_fit(const int8_t* positions_dev, int64_t B, int32_t S, int32_t* au
 int wmar_sync_rotate_labels(const int8_t* positions_dev, int64_t B, int32_t S, int32_t angle, uint8_t* out_dev, void* workspace_dev,
                             int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ synchronisation layer (WAM embedder)
+ * deps/watermark_anything: models/embedder.py VAEEmbedder (modules/vae.py VAEEncoder / VAEDecoder with tanh_out, modules/
+ * msg_processor.py "binary+concat"), modules/jnd.py JND (in_channels 1, out_channels 3) and models/wam.py Wam.blend / Wam.embed, for
+ * images of the network's own size (no resize).  Tensors by key name relative to `embedder.` (encoder.*, decoder.*,
+ * msg_processor.msg_embeddings.weight [2 nbits, 2 nbits]).  The network runs through the VQGAN engines' layer plan and kernels
+ * (csrc/vq_plan.h plan_wam); refused with a text: ch % 32 != 0, a latent size that is not a multiple of 8, nbits outside 1..64.
+ * max_batch counts decoder rows (one per image and message); longer calls are walked in chunks.  attenuation: 0 none, 1 jnd_1_3,
+ * 2 jnd_1_3_blue, applied in [0, 1] space between unnormalize_img and normalize_img (utils/inference_utils.py:64).  Images are
+ * float [B, 3, R, R] (NCHW), messages int32 (a bit is set when it is not 0).  R other than `resolution` is WMAR_EINVAL and nothing
+ * is launched.  No call but the probes waits for its launches; two runs give the same bits. */
+typedef struct wmar_wam_config {
+    int32_t ch, num_res_blocks, resolution, z_channels, nbits;
+    int32_t n_levels;
+    int32_t ch_mult[8];
+    int32_t n_attn_res;
+    int32_t attn_resolutions[8];
+    int32_t max_batch;
+    float scaling_w, scaling_i;
+    int32_t attenuation;
+} wmar_wam_config;
+
+typedef struct wmar_wam wmar_wam;
+
+int wmar_wam_create(const wmar_wam_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                    wmar_wam** out);
+void wmar_wam_destroy(wmar_wam* w);
+int64_t wmar_wam_device_bytes(const wmar_wam* w);
+
+/* Wam.embed (models/wam.py:147-192): imgs_norm_dev in WAM-normalised space, msgs_dev int32 [B, nbits] (one message per image) ->
+ * imgs_w_dev [B, 3, R, R] = blend(imgs, preds_w), preds_w_dev (nullable) [B, 3, R, R] = tanh(decoder output).  No clamp. */
+int wmar_wam_embed(wmar_wam* w, const float* imgs_norm_dev, int64_t B, int32_t R, const int32_t* msgs_dev, float* imgs_w_dev,
+                   float* preds_w_dev, void* stream);
+/* WamSync.add_sync (wmar/watermarking/synchronization.py:299-316): imgs_pm1_dev in [-1, 1], msgs_dev int32 [K, nbits], masks_dev uint8
+ * [K, R, R] of 0 / 1 (the caller checks), 1 <= K <= 8.  Normalise, one encoder pass per image, one decoder row per (image, message),
+ * blend in message order -- a later mask overrides an earlier one, as multi * (1 - m) + w * m does for 0 / 1 masks; where no mask is
+ * set the image itself -- then unnormalise, * 2 - 1, clamp to [-1, 1] into out_pm1_dev [B, 3, R, R]. */
+int wmar_wam_add_sync(wmar_wam* w, const float* imgs_pm1_dev, int64_t B, int32_t R, const int32_t* msgs_dev, int32_t K,
+                      const uint8_t* masks_dev, float* out_pm1_dev, void* stream);
+
+/* Probes (tests, debugging): one kernel of the embedder at a time; none is used by an engine path; each waits for the stream.
+ * wmar_wam_probe_jnd: imgs01_dev [B, 3, R, R] in [0, 1], R a multiple of 4 -> heat_dev [B, R, R] = JND.heatmaps / its one channel
+ * (the blue weights (0.5, 0.5, 1.0) belong to the tail).
+ * wmar_wam_probe_latent_msg: the decoder input out_dev [rows, S, S, pad8(z_channels + 2 nbits)] (NHWC): row r takes its first
+ * z_channels channels from image r / img_div of latents_dev [n_images, S, S, pad8(z_channels)], the next 2 nbits channels from
+ * sum_j table[2 j + bit_j] (ascending j, fp32) of message (msg_mod ? r % msg_mod : r) of msgs_dev int32 [n_msgs, nbits]; padding 0.
+ * wmar_wam_probe_tail: the tail on given decoder outputs y_dev [rows, R, R, 8] (NHWC, 3 real channels) and images imgs_dev
+ * [B, 3, R, R] (in_mode 1: WAM-normalised, 2: in [-1, 1]).  masks_dev null: embed form, rows = B, out_dev [B, 3, R, R] = imgs_w and
+ * preds_dev (nullable) = tanh(y).  masks_dev uint8 [K, R, R]: add_sync form, rows = B * K (row = image * K + message), out_dev in
+ * [-1, 1].  The heat maps (attenuation != 0) are computed by the call. */
+int wmar_wam_probe_jnd(const float* imgs01_dev, int64_t B, int32_t R, float* heat_dev, void* stream);
+int wmar_wam_probe_latent_msg(const float* latents_dev, int64_t n_images, int32_t S, int32_t z_channels, int32_t nbits,
+                              const float* table_dev, const int32_t* msgs_dev, int64_t n_msgs, int64_t rows, int32_t img_div,
+                              int32_t msg_mod, float* out_dev, void* stream);
+int wmar_wam_probe_tail(const float* y_dev, const float* imgs_dev, int32_t in_mode, int64_t B, int32_t R, const uint8_t* masks_dev,
+                        int32_t K, float scaling_w, float scaling_i, int32_t attenuation, float* out_dev, float* preds_dev, void* stream);
+
 /* ------------------------------------------------------------------------ exchange step (RCCL over xGMI)
  * The sharded job (one process per GPU; rank r == the reference's `--chunk_id r --num_chunks world`, generate.py:204, :304) has no
  * data-path collective.  Its two exchanges -- the finished key table from rank 0 once, the per-image records once per step

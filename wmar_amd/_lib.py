@@ -34,6 +34,8 @@ SYMBOLS = [
     "wmar_augment", "wmar_augment_backward", "wmar_jpeg_workspace_bytes", "wmar_jpeg", "wmar_resample_coeffs", "wmar_image_ingest",
     "wmar_resample_coeffs_filtered", "wmar_image_ingest_filtered", "wmar_vq_train_create_frozen", "wmar_mvq_train_create_frozen",
     "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
+    "wmar_wam_create", "wmar_wam_destroy", "wmar_wam_device_bytes", "wmar_wam_embed", "wmar_wam_add_sync",
+    "wmar_wam_probe_jnd", "wmar_wam_probe_latent_msg", "wmar_wam_probe_tail",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
 
@@ -85,6 +87,13 @@ class MvqConfig(C.Structure):
     _fields_ = [("hidden_channels", C.c_int32), ("num_res_blocks", C.c_int32), ("resolution", C.c_int32),
                 ("num_channels", C.c_int32), ("z_channels", C.c_int32), ("num_embeddings", C.c_int32),
                 ("n_levels", C.c_int32), ("channel_mult", C.c_int32 * 8), ("max_batch", C.c_int32)]
+
+
+class WamConfig(C.Structure):
+    _fields_ = [("ch", C.c_int32), ("num_res_blocks", C.c_int32), ("resolution", C.c_int32), ("z_channels", C.c_int32),
+                ("nbits", C.c_int32), ("n_levels", C.c_int32), ("ch_mult", C.c_int32 * 8), ("n_attn_res", C.c_int32),
+                ("attn_resolutions", C.c_int32 * 8), ("max_batch", C.c_int32), ("scaling_w", C.c_float), ("scaling_i", C.c_float),
+                ("attenuation", C.c_int32)]
 
 
 class LpipsConfig(C.Structure):
@@ -238,6 +247,16 @@ def load():
         L.wmar_vq_train_decode.argtypes = [vp, vp, i64, vp, vp]
         L.wmar_vq_train_decode_backward.argtypes = [vp, vp, i64, vp, vp]
         L.wmar_vq_train_get_grads.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(vp), i32, i32, vp]
+        L.wmar_wam_create.argtypes = [C.POINTER(WamConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
+        L.wmar_wam_destroy.argtypes = [vp]
+        L.wmar_wam_destroy.restype = None
+        L.wmar_wam_device_bytes.restype = i64
+        L.wmar_wam_device_bytes.argtypes = [vp]
+        L.wmar_wam_embed.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+        L.wmar_wam_add_sync.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, vp]
+        L.wmar_wam_probe_jnd.argtypes = [vp, i64, i32, vp, vp]
+        L.wmar_wam_probe_latent_msg.argtypes = [vp, i64, i32, i32, i32, vp, vp, i64, i64, i32, i32, vp, vp]
+        L.wmar_wam_probe_tail.argtypes = [vp, vp, i32, i64, i32, vp, i32, f32, f32, i32, vp, vp, vp]
         L.wmar_lpips_create.argtypes = [C.POINTER(LpipsConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
         L.wmar_lpips_destroy.argtypes = [vp]
         L.wmar_lpips_destroy.restype = None

@@ -72,7 +72,11 @@ def build_sync_manager(args, device):
         return None
     from .watermarking.synchronization import SyncManager, WamSync
     factory = getattr(args, "sync_factory", None)
+    # --sync_embedder native: add_sync's embedder from the checkpoint's embedder.* tensors on the device (wam_embedder.py)
+    native = {"embedder": "native"} if getattr(args, "sync_embedder", "torch") == "native" else {}
     if not factory:
+        if native:
+            return SyncManager(args.syncpath, device, sync=WamSync(args.syncpath, device, **native))
         return SyncManager(args.syncpath, device)
     import importlib
     module, _, name = factory.partition(":")
@@ -80,5 +84,5 @@ def build_sync_manager(args, device):
     if hasattr(made, "add_sync") and hasattr(made, "remove_sync"):
         return made if isinstance(made, SyncManager) else SyncManager(args.syncpath, device, sync=made)
     if hasattr(made, "embed") and hasattr(made, "detect"):
-        return SyncManager(args.syncpath, device, sync=WamSync(args.syncpath, device, wam=made))
+        return SyncManager(args.syncpath, device, sync=WamSync(args.syncpath, device, wam=made, **native))
     raise TypeError(f"--sync_factory {factory}: {type(made).__name__} has neither add_sync / remove_sync nor embed / detect")

@@ -274,4 +274,83 @@ inline VqPlan plan_mvq(const wmar_mvq_config& c, const std::string& who) {
     return p;
 }
 
+// The WAM embedder (deps/watermark_anything/modules/vae.py:176-381, models/embedder.py:45-98): Taming's encoder and decoder without
+// a quantizer.  Half 0 ends at the encoder's conv_out (z_channels, no double_z); half 1 starts from the z_channels + 2 * nbits
+// channels the message processor ("binary+concat") hands the decoder and ends at its conv_out (the tanh belongs to the tail kernel).
+// Tensor names are the checkpoint's keys relative to `embedder.`.
+inline VqPlan plan_wam(const wmar_wam_config& c, const std::string& who) {
+    if (!(c.n_levels >= 1 && c.n_levels <= 8)) return vq_plan_refused(who + ": bad ch_mult length");
+    if (!(c.max_batch >= 1)) return vq_plan_refused(who + ": max_batch");
+    if (c.ch <= 0 || c.ch % 32 != 0) return vq_plan_refused("ch must be a multiple of 32 (GroupNorm has 32 groups)");
+    if (!(c.nbits >= 1 && c.nbits <= 64)) return vq_plan_refused(who + ": nbits " + std::to_string(c.nbits) + " outside 1..64");
+    if (!(c.z_channels >= 1 && c.num_res_blocks >= 1)) return vq_plan_refused(who + ": z_channels and num_res_blocks must be positive");
+    if (!(c.n_attn_res >= 0 && c.n_attn_res <= 8)) return vq_plan_refused(who + ": bad attn_resolutions length");
+    for (int i = 0; i < c.n_attn_res; ++i)
+        if (c.attn_resolutions[i] <= 0) return vq_plan_refused(who + ": attn_resolutions must be positive");
+    for (int i = 0; i < c.n_levels; ++i)
+        if (c.ch_mult[i] <= 0) return vq_plan_refused(who + ": ch_mult must be positive");
+    const int L = c.n_levels, S = vq_latent_size(c.resolution, L);
+    if (!S) return vq_plan_refused("latent size " + std::to_string(c.resolution >> (L - 1)) + " must be a multiple of 8");
+    VqPlan p;
+    p.resolution = c.resolution; p.S = S; p.in_channels = 3; p.out_ch = 3; p.max_batch = c.max_batch;
+    VqPlanBuilder b{p};
+    const int ch = c.ch, z = c.z_channels;
+    auto attn_at = [&](int res) {
+        for (int i = 0; i < c.n_attn_res; ++i)
+            if (c.attn_resolutions[i] == res) return true;
+        return false;
+    };
+    {
+        int res = c.resolution, block_in = ch;
+        int x = b.begin(0, 3, res);
+        x = b.step("encoder.conv_in", 3, ch, 3, x);
+        for (int lvl = 0; lvl < L; ++lvl) {
+            const std::string q = "encoder.down." + std::to_string(lvl) + ".";
+            block_in = ch * (lvl == 0 ? 1 : c.ch_mult[lvl - 1]);
+            const int block_out = ch * c.ch_mult[lvl];
+            for (int i = 0; i < c.num_res_blocks; ++i) {
+                x = b.res(q + "block." + std::to_string(i) + ".", block_in, block_out, x);
+                block_in = block_out;
+                if (attn_at(res)) x = b.attn(q + "attn." + std::to_string(i) + ".", block_in, x);
+            }
+            if (lvl != L - 1) {
+                x = b.step(q + "downsample.conv", block_in, block_in, 3, x, 2);
+                res /= 2;
+            }
+        }
+        x = b.res("encoder.mid.block_1.", block_in, block_in, x);
+        x = b.attn("encoder.mid.attn_1.", block_in, x);
+        x = b.res("encoder.mid.block_2.", block_in, block_in, x);
+        p.half[0].last = b.out_conv("encoder.", block_in, z, 3, x);
+    }
+    {
+        const int zin = z + 2 * c.nbits;
+        int res = S, block_in = ch * c.ch_mult[L - 1];
+        int x = b.begin(1, zin, S);
+        x = b.step("decoder.conv_in", zin, block_in, 3, x);
+        x = b.res("decoder.mid.block_1.", block_in, block_in, x);
+        x = b.attn("decoder.mid.attn_1.", block_in, x);
+        x = b.res("decoder.mid.block_2.", block_in, block_in, x);
+        for (int lvl = L - 1; lvl >= 0; --lvl) {
+            const std::string q = "decoder.up." + std::to_string(lvl) + ".";
+            const int block_out = ch * c.ch_mult[lvl];
+            for (int i = 0; i <= c.num_res_blocks; ++i) {
+                x = b.res(q + "block." + std::to_string(i) + ".", block_in, block_out, x);
+                block_in = block_out;
+                if (attn_at(res)) x = b.attn(q + "attn." + std::to_string(i) + ".", block_in, x);
+            }
+            if (lvl != 0) {
+                x = b.step(q + "upsample.conv", block_in, block_in, 3, x, 1, 1);
+                res *= 2;
+            }
+        }
+        p.half[1].last = b.out_conv("decoder.", block_in, 3, 3, x);
+    }
+    int amax = S, cam = 0;
+    for (int i = 0; i < c.n_attn_res; ++i) amax = c.attn_resolutions[i] > amax ? c.attn_resolutions[i] : amax;
+    for (int lvl = 0; lvl < L; ++lvl) cam = ch * c.ch_mult[lvl] > cam ? ch * c.ch_mult[lvl] : cam;
+    p.zbias_elems = (size_t)amax * amax > (size_t)cam ? (size_t)amax * amax : (size_t)cam;
+    return p;
+}
+
 }  // namespace wmar

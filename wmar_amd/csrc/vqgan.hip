@@ -1679,3 +1679,6 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 #include "vq_grad.h"
 #include "vq_train.h"
 #include "lpips.h"
+
+// ============================================================================ the WAM embedder (synchronisation layer)
+#include "wam.h"

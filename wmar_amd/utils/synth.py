@@ -272,6 +272,65 @@ def synth_vq_state_fast(cfg: VQConfig, seed: int = 0, device="cuda"):
     return out
 
 
+# ----------------------------------------------------------------------------- WAM embedder (synchronisation layer)
+@dataclasses.dataclass
+class WamConfig:
+    """The embedder of the released WAM checkpoint (deps/watermark_anything/params.json: embedder_model vae_small of
+    configs/embedder.yaml, nbits 32, scaling_w 2.0, scaling_i 1.0, attenuation jnd_1_3_blue)."""
+    ch: int = 32
+    ch_mult: Tuple[int, ...] = (1, 1, 1, 2)
+    num_res_blocks: int = 2
+    attn_resolutions: Tuple[int, ...] = ()
+    resolution: int = 256
+    z_channels: int = 4
+    nbits: int = 32
+    scaling_w: float = 2.0
+    scaling_i: float = 1.0
+    attenuation: str = "jnd_1_3_blue"          # "none" | "jnd_1_3" | "jnd_1_3_blue"
+
+    @property
+    def num_resolutions(self) -> int:
+        return len(self.ch_mult)
+
+    @property
+    def latent_size(self) -> int:
+        return self.resolution // (2 ** (self.num_resolutions - 1))
+
+    def _vq(self, z_channels: int) -> VQConfig:
+        return VQConfig(ch=self.ch, ch_mult=tuple(self.ch_mult), num_res_blocks=self.num_res_blocks,
+                        attn_resolutions=tuple(self.attn_resolutions), resolution=self.resolution, in_channels=3, out_ch=3,
+                        z_channels=z_channels, embed_dim=0, n_embed=0)
+
+
+WAM_RELEASED = WamConfig()
+# the same widths at 64 x 64: an 8 x 8 latent and a 64-token middle attention
+WAM_SMALL = WamConfig(resolution=64)
+
+
+def wam_shapes(cfg: WamConfig) -> Dict[str, Tuple[int, ...]]:
+    """Keys relative to ``embedder.`` (models/embedder.py:45-98): VAEEncoder without double_z, VAEDecoder from
+    z_channels + 2 * nbits channels, the message table."""
+    s: Dict[str, Tuple[int, ...]] = {}
+    for k, v in encoder_shapes(cfg._vq(cfg.z_channels)).items():
+        s["encoder." + k] = v
+    for k, v in decoder_shapes(cfg._vq(cfg.z_channels + 2 * cfg.nbits)).items():
+        s["decoder." + k] = v
+    s["msg_processor.msg_embeddings.weight"] = (2 * cfg.nbits, 2 * cfg.nbits)
+    return s
+
+
+def synth_wam_state(cfg: WamConfig, seed: int = 0, device="cpu") -> Dict[str, torch.Tensor]:
+    """Random-init embedder tensors keyed like the WAM checkpoint's ``embedder.*`` minus the prefix (the message table is
+    N(0, 1), as nn.Embedding initialises it)."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed + 104729)
+    shapes = wam_shapes(cfg)
+    table = "msg_processor.msg_embeddings.weight"
+    out = _fill({k: v for k, v in shapes.items() if k != table}, g, device, "vq")
+    out[table] = torch.randn(shapes[table], generator=g).to(torch.float32).to(device)
+    return out
+
+
 # ----------------------------------------------------------------------------- RAR
 @dataclasses.dataclass
 class RARConfig:

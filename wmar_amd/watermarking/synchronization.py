@@ -2,7 +2,8 @@
 ``SyncManager`` with the reference's public surface, for the MI355X build.
 
 The neural half (the WAM embedder / extractor, the SyncSeal TorchScript) is ordinary PyTorch and is NOT part of this package: it is
-bound from the user's own checkout or handed in as an object.  What the reference computes on the host per image -- the message
+bound from the user's own checkout or handed in as an object -- except the WAM embedder, which ``WamSync(..., embedder=...)`` runs on
+the device from the checkpoint's ``embedder.*`` tensors (wam_embedder.py, wmar_amd/csrc/wam.h: ``wmar_wam_add_sync``).  What the reference computes on the host per image -- the message
 label of every pixel, and ``fit_best_aug``: four label masks rotated by 41 angles with ``scipy.ndimage.rotate``, thresholded, counted
 and searched for the best cut and flip (2.3 s per 256 x 256 image) -- runs here as kernels over the whole batch
 (wmar_amd/csrc/sync.hip: ``wmar_sync_positions``, ``wmar_sync_fit``, ``wmar_sync_rotate_labels``), and ``remove_sync`` copies one
@@ -69,9 +70,21 @@ def _positions_arg(positions, device):
 
 
 class WamSync:
-    def __init__(self, syncpath, device, wam=None):
+    def __init__(self, syncpath, device, wam=None, embedder=None):
+        """``embedder``: a ``WamEmbedder`` (wam_embedder.py), or "native" to build one from ``syncpath``.  With one, ``add_sync`` on
+        images of its resolution is one device call and the PyTorch network is only loaded at the first ``remove_sync`` (or the
+        first ``add_sync`` of another image size)."""
         self.device = device
-        self.wam = wam if wam is not None else _load_wam(syncpath, device)
+        self.syncpath = syncpath
+        if isinstance(embedder, str):
+            if embedder != "native":
+                raise ValueError(f"embedder {embedder!r}: a WamEmbedder or 'native'")
+            from .wam_embedder import WamEmbedder
+            embedder = WamEmbedder.from_checkpoint(syncpath, device)
+        self.embedder = embedder
+        self._wam = wam
+        if wam is None and embedder is None:
+            self._wam = _load_wam(syncpath, device)
         self.epsilon = 1
         self.min_samples = 500
         self.wm_msgs = torch.tensor([[0] * 32, [0] * 16 + [1] * 16, [1] * 16 + [0] * 16, [1] * 32]).to(device)
@@ -79,6 +92,18 @@ class WamSync:
         self._mean = torch.tensor(IMAGENET_MEAN, dtype=torch.float32, device=device).view(1, 3, 1, 1)
         self._std = torch.tensor(IMAGENET_STD, dtype=torch.float32, device=device).view(1, 3, 1, 1)
         self._flip, self._rotate = HorizontalFlip(), Rotate()
+
+    @property
+    def wam(self):
+        """The PyTorch network (embed / detect): handed in, loaded at construction, or -- with a native embedder -- loaded from the
+        user's checkout when it is first needed."""
+        if self._wam is None:
+            self._wam = _load_wam(self.syncpath, self.device)
+        return self._wam
+
+    @wam.setter
+    def wam(self, value):
+        self._wam = value
 
     # transfer to WAM space, [-1, 1] -> [0, 1] + normalized
     def normalize(self, imgs):
@@ -221,6 +246,14 @@ class WamSync:
     @torch.no_grad()
     def add_sync(self, imgs, return_masks=False):
         orig_device = imgs.device
+        emb = self.embedder
+        if emb is not None and imgs.dim() == 4 and imgs.shape[-1] == emb.cfg.resolution and imgs.shape[-2] == emb.cfg.resolution:
+            # the whole method as one call: normalise, 1 encoder + K decoder passes, blend, unnormalise (wmar_wam_add_sync)
+            dev = getattr(emb, "device", self.device)
+            x = imgs.to(dev)
+            masks = self.create_grid_mask(x[-1], num_masks=len(self.wm_msgs))
+            ret = emb.add_sync(x, self.wm_msgs.to(dev), masks).to(orig_device)
+            return (ret, masks) if return_masks else ret
         imgs = self.normalize(imgs.to(self.device))
         masks = self.create_grid_mask(imgs[-1], num_masks=len(self.wm_msgs))
         multi = imgs.clone()
