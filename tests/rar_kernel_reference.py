@@ -3,7 +3,7 @@
 The packed layouts, the GEMM decompositions and the attention bounds are those of tests/gpt_kernel_reference.py and are imported
 from there, not copied; this file adds what only RAR has.  numpy only, nothing from wmar_amd/csrc.
 tests/test_rar_kernel_reference.py shows on the CPU that each check built from these statements catches the fault it is there
-for (the `fault=` arguments below exist for that file alone); tests/test_gpu_rar_kernels.py holds the kernels to them.
+for (the `fault=` arguments below exist for that file alone); tests/test_gpu_rar_kernels.py and tests/test_gpu_rar_released.py hold the kernels to them.
 
 M rows, MT = 1 / 2 / 4 row tiles for M <= 32 / 64 / 128, KB = D / 8 k-blocks, Ntot = 6 D L + 2 D adaLN columns.
 
@@ -275,6 +275,8 @@ def gated_fold32(x, gate, bias, slabs, fault=None):
     """x' = x + gate (bias + (s0 + s1 + ..)) in fp32, slab order.  Exact on integer operands with power-of-two gates (every
     intermediate is an integer multiple of the gate below 2^24 of it), with or without a fused multiply-add."""
     use = slabs[:-1] if fault == "missing_slab" and len(slabs) > 1 else slabs
+    if fault == "missing_slab6":                                  # slab 6 of 8 (the k_bx<2,8,4> FC2 of RAR-L leaves 8)
+        use = [s for i, s in enumerate(slabs) if i != 5]
     acc = fold_slabs([s.astype(np.float32) for s in use])
     if fault == "missing_slab" and len(slabs) == 1:
         acc = np.zeros_like(acc)
@@ -318,6 +320,39 @@ def piece_sum32(P, RPI):
     return groups[0]
 
 
+def two_sum32(a, b):
+    """fp32 a + b and what the addition rounded away (Knuth's TwoSum, the kernels' two_sum)"""
+    f = np.float32
+    a, b = np.asarray(a, dtype=f), np.asarray(b, dtype=f)
+    s = (a + b).astype(f)
+    bb = (s - a).astype(f)
+    return s, ((a - (s - bb).astype(f)).astype(f) + (b - bb).astype(f)).astype(f)
+
+
+def piece_sum32c(P, RPI, bias):
+    """the prologue's sum of the q and k pieces plus bias (MODE 1): the order of piece_sum32, every addition's rounding error
+    carried along in a second fp32 value (csum4_add), both folded into the result behind the bias (csum4_finish)"""
+    f = np.float32
+    S = P.shape[0]
+    groups = []
+    for g in range(RPI):
+        s, c = np.zeros(P.shape[1:], dtype=f), np.zeros(P.shape[1:], dtype=f)
+        for p in range(g, S, RPI):
+            s, e = two_sum32(s, P[p])
+            c = (c + e).astype(f)
+        groups.append((s, c))
+    while len(groups) > 1:
+        nxt = []
+        for i in range(0, len(groups), 2):
+            (s, c), (ps, pc) = groups[i], groups[i + 1]
+            s, e = two_sum32(s, ps)
+            nxt.append((s, (c + (pc + e).astype(f)).astype(f)))
+        groups = nxt
+    s, c = groups[0]
+    t, e = two_sum32(s, np.broadcast_to(bias.astype(f), s.shape))
+    return (t + (c + e).astype(f)).astype(f)
+
+
 def head_sum32(v):
     """the prologue's fp32 sum over the hd values of a head: four values per lane ((a + b) + c) + d, the lanes (padded with zeros to
     8 / 16 / 32) in an xor butterfly.  [.., hd] -> [.., 1]"""
@@ -337,12 +372,19 @@ def head_sum32(v):
 
 def attn_prologue(P, bias, qn_w, qn_b, kn_w, kn_b, H, hd, fault=None):
     """The prologue of k_attn_decode<.., MODE 1> / k_attn_decode80: r = (sum of the pieces) + bias, q and k LayerNorm-ed over the hd
-    values of their head (eps 1e-6, affine), v as it is.  P [S][M, 3 D] fp32.
+    values of their head (eps 1e-6, affine), v as it is.  The q and k pieces are added with their rounding errors carried along
+    (piece_sum32c: with several pieces an element that cancels would otherwise keep roundings the norm scales up), v plainly;
+    at head_dim 80 (k_attn_decode80, RAR-XL: tokens pinned against the oracle) q and k take the plain sum as well.
+    P [S][M, 3 D] fp32.
     Returns float64 (q, k, v) [M, H, hd], the same in an fp32 numpy evaluation, and the normalisers of q and k."""
+    if fault == "drop_piece3":                                    # S = 3 on four row groups (head_dim 48): group 2's piece never added
+        P = P[:2]
     S, M, N = P.shape
     D = N // 3
     r64 = P.astype(np.float64).sum(0) + bias.astype(np.float64)[None, :]
-    r32 = (piece_sum32(P, attn_row_groups(hd)) + bias.astype(np.float32)[None, :]).astype(np.float32)
+    r32 = (piece_sum32(P, attn_row_groups(hd)) + bias.astype(np.float32)[None, :]).astype(np.float32)       # v: the plain sum
+    if hd != 80:                                                  # q, k: errors carried (k_attn_decode80 keeps the plain sum)
+        r32[:, :2 * D] = piece_sum32c(P[:, :, :2 * D], attn_row_groups(hd), bias[:2 * D])
     out64, out32, norms = [], [], []
     for which, (w, b) in enumerate(((qn_w, qn_b), (kn_w, kn_b), (None, None))):
         if which == 1 and fault == "knorm_with_qnorm":
@@ -392,6 +434,50 @@ def attn_mode1_ref(q64, K64, V64, hd, fault=None, E=None):
     return np.einsum("...t,...td->...d", w / w.sum(-1, keepdims=True), V64)
 
 
+def attn_loop_rows(T, E, hd, fault=None):
+    """The streaming loop of k_attn_decode<.., 1, 1> / k_attn_decode80<1> (one wave, two buffers) as the list of rows it weighs:
+    chunk c holds rows c E .. c E + E - 1; buffer A takes the even chunks and buffer B the odd ones, each refilled two chunks ahead;
+    loads clamp to row T - 1; the slot of row T - 1 is replaced by the new row from registers; slots at or past T are masked.
+    Returns [(t, src, tail_src)]: row t weighed with the K / V of `src` (-1: the new row held in registers, else that cache row as it
+    lies in front of the launch) and, at head_dim 80, the score's tail partial (floats 64..79) taken from `tail_src`.
+    `fault` plants what tests/test_gpu_rar_released.py exists for (tests/test_rar_kernel_reference.py shows each caught)."""
+    nchunk = -(-T // E)
+    out = []
+    for c in range(nchunk):
+        if fault == "skip_last_odd" and nchunk % 2 == 1 and c == nchunk - 1:
+            continue
+        cs = 1 if (fault == "refill_b_chunk1" and c % 2 == 1 and c >= 3) else c         # buffer B's refill reads chunk 1 again
+        for j in range(E):
+            t = c * E + j
+            if t >= T:
+                continue
+            stale = fault == "stale_append" and 2 <= (T - 1) % E <= 5
+            src = -1 if (t >= T - 1 and not stale) else min(cs * E + j, T - 1)
+            tail = src
+            if fault == "tail_wrong_row" and hd == 80:                                  # quad u of the neighbouring 16-lane row
+                j2 = 4 * (j // 4) + ((j % 4) ^ 1)
+                t2 = c * E + j2
+                tail = -1 if t2 >= T - 1 else min(cs * E + j2, T - 1)
+            out.append((t, src, tail))
+    return out
+
+
+def attn_loop64(q, Kc, Vc, knew, vnew, T, hd, E, fault=None):
+    """softmax(q K^T / sqrt(hd)) V in float64 over the rows of attn_loop_rows.  q, knew, vnew [.., hd]; Kc, Vc [.., Tmax, hd]: the
+    cache in front of the launch (rows at or past T - 1 stale)."""
+    rows = attn_loop_rows(T, E, hd, fault)
+    f8 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
+    q, Kc, Vc, knew, vnew = f8(q), f8(Kc), f8(Vc), f8(knew), f8(vnew)
+    pick = lambda C, new, r: new if r < 0 else C[..., r, :]  # noqa: E731
+    nm = min(hd, 64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = np.stack([(q[..., :nm] * pick(Kc, knew, src)[..., :nm]).sum(-1) + (q[..., nm:] * pick(Kc, knew, tl)[..., nm:]).sum(-1)
+                      for _, src, tl in rows], -1) / np.sqrt(hd)
+        V = np.stack([pick(Vc, vnew, src) for _, src, _ in rows], -2)
+        w = np.exp(s - s.max(-1, keepdims=True))
+        return np.einsum("...t,...td->...d", w / w.sum(-1, keepdims=True), V)
+
+
 # ------------------------------------------------------------------------------------------------------------------- GELU
 def gelu_tanh64(v):
     v = np.asarray(v, dtype=np.float64)
@@ -420,6 +506,18 @@ def check_gelu(got, pre32, what="GELU", pre_tol=None):
 def bx_ranges(NT, S, PER):
     """K slice s of a k_bx launch with PER 16-k steps per wave: 4 waves x PER x 16 = 64 PER features = 8 PER k-blocks"""
     return uniform_ranges(NT, lambda s: (s * 8 * PER, (s + 1) * 8 * PER), S)
+
+
+def bx_pieces64(Wg, X, NT, S, PER, fault=None):
+    """float64 pieces [S][M, N] of a k_bx launch.  A slab's 8 PER k-blocks go to four waves of PER 16-feature steps (2 PER k-blocks)
+    each; fault "drop_steps_5_8": every wave stops behind its fourth step (what a PER 8 instance with a PER 4 loop would leave)."""
+    if fault is None:
+        return gemm_pieces(Wg, X, bx_ranges(NT, S, PER))[0]
+    assert fault == "drop_steps_5_8" and PER >= 8
+    out = 0.0
+    for w in range(4):
+        out = out + gemm_pieces(Wg, X, uniform_ranges(NT, lambda s: (s * 8 * PER + w * 2 * PER, s * 8 * PER + w * 2 * PER + 8), S))[0]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------- the plan
@@ -488,7 +586,60 @@ def expected_plan(D, H, F, L, V, max_batch, M, Bhalf, shared_u, no_bx=False, fus
     return out
 
 
+# The released sizes of RarARMMWrapper (wmar_amd/models/rar_wrapper.py: _RAR_SIZES gives width, depth, F; 16 heads each) and two
+# synthetic shapes that select the remaining launch_bx4 cases, as (D, H, F), and what their plans at max_batch 64 must say: written
+# down by hand from the dispatch, NOT computed by expected_plan -- the CPU test holds expected_plan to it, the GPU tests the engine.
+RELEASED_SHAPES = {"RB": (768, 16, 3072), "RL": (1024, 16, 4096), "RXL": (1280, 16, 5120), "RXXL": (1408, 16, 6144),
+                   "P16": (256, 4, 8192), "P20": (256, 4, 6400)}
+RELEASED_WRAPPER = {"rar_b": ("RB", 24), "rar_l": ("RL", 24), "rar_xl": ("RXL", 32), "rar_xxl": ("RXXL", 40)}
+
+
+def released_pins():
+    """{(engine, rows): facts}; `roles` holds kernel names by role"""
+    pins = {}
+    for M in (20, 64):
+        mt = 1 if M <= 32 else 2
+        for name, hd, Sp, Sf, nch in (("RB", 48, 3, 8, 6), ("RL", 64, 4, 8, 8), ("RXL", 80, 5, 6, 10), ("RXXL", 88, 5, 5, 11)):
+            pins[(name, M)] = dict(bx=0, S_qkv=1, S_proj=Sp, S_fc2=Sf, nch=nch, nrm=4 * nch, roles=dict(
+                fc2="k_gemm<%d,EPI_PACKED>" % mt, resid_attn="k_resid_mod<%d,1,0>" % Sp, resid_mlp="k_resid_mod<%d,1,0>" % Sf,
+                fc1="k_gemm<%d,EPI_GELU>" % mt, attn="k_attn_decode80<1>" if hd == 80 else "k_attn_decode<%d,1,1>" % hd))
+    for M in (97, 127, 128):
+        pins[("RB", M)] = dict(bx=1, S_qkv=3, PER_qkv=4, S_proj=3, PER_proj=4, S_fc2=6, PER_fc2=8, nch=6, nrm=24, rowmajor=0, roles=dict(
+            qkv="k_bx<2,4,4>", proj="k_bx<1,4,4>", fc2="k_bx<2,8,4>", resid_attn="k_resid_mod<3,1,0>", resid_mlp="k_resid_mod<6,1,0>",
+            fc1="k_gemm<2,EPI_GELU> planes", attn="k_attn_decode<48,1,1>"))
+        pins[("RL", M)] = dict(bx=1, S_qkv=4, PER_qkv=4, S_proj=4, PER_proj=4, S_fc2=8, PER_fc2=8, nch=8, nrm=32, rowmajor=0, roles=dict(
+            qkv="k_bx<2,4,4>", proj="k_bx<1,4,4>", fc2="k_bx<2,8,4>", resid_attn="k_resid_mod<4,1,0>", resid_mlp="k_resid_mod<8,1,0>",
+            fc1="k_gemm<2,EPI_GELU> planes", attn="k_attn_decode<64,1,1>"))
+        pins[("RXL", M)] = dict(bx=1, fc1_bx=1, rowmajor=1, S_qkv=4, PER_qkv=5, S_proj=5, PER_proj=4, S_fc2=8, PER_fc2=10, nch=10, nrm=40,
+                                roles=dict(qkv="k_bx<2,5,4> rowmajor", fc2="k_bx<2,10,4>", fc1="k_bx<1,10,4,GELU,8,XF>",
+                                           resid_mlp="k_resid_mod<8,1,0>", attn="k_attn_decode80<1> rowmajor"))
+        pins[("RXXL", M)] = dict(bx=0, S_qkv=1, S_proj=5, S_fc2=8, nch=11, nrm=44, roles=dict(
+            qkv="k_gemm<2,EPI_PACKED>", fc2="k_gemm<2,EPI_PACKED>", resid_attn="k_resid_mod<5,1,0>", resid_mlp="k_resid_mod<8,1,0>",
+            fc1="k_gemm<4,EPI_GELU>", attn="k_attn_decode<88,1,1>"))
+        for name, S, PER in (("P16", 8, 16), ("P20", 5, 20)):
+            pins[(name, M)] = dict(bx=1, S_qkv=1, PER_qkv=4, S_proj=1, PER_proj=4, S_fc2=S, PER_fc2=PER, roles=dict(
+                fc2="k_bx<2,%d,4>" % PER, resid_mlp="k_resid_mod<%d,1,0>" % S, fc1="k_gemm<4,EPI_GELU> planes", attn="k_attn_decode<64,1,1>"))
+    return pins
+
+
+def check_pins(plan, pins, what=""):
+    for k, v in pins.items():
+        if k == "roles":
+            for role, kern in v.items():
+                assert plan["roles"][role] == kern, (what, role, plan["roles"][role], kern)
+        else:
+            assert plan[k] == v, (what, k, plan[k], v)
+
+
 # ------------------------------------------------------------------------------------------------------------------- composition
+def _gelu64_torch(v):
+    """gelu64 through torch's float64 erf: the same values to a few 2^-53, without a Python call per element (the composition
+    at released widths evaluates 128 x 6144 of them per position)"""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
+    return (0.5 * t * (1.0 + torch.erf(t * 0.70710678118654752440))).numpy()
+
+
 def position64(sd, cfg, tk, cond, p, kc, vc):
     """One position in float64 numpy, composed of the statements above (the CPU test holds it to oracle.rar_oracle.rar_position).
     sd: numpy state dict with the checkpoint's keys; tk [M] token ids (-1 cls); kc / vc: per block [M, H, t, hd] or None."""
@@ -523,7 +674,7 @@ def position64(sd, cfg, tk, cond, p, kc, vc):
         y = attn_mode1_ref(q, kk, vv, hd).reshape(M, d)
         x = x + ch["gate_msa"] * (y @ f8(pre + "attn.proj.weight").T + f8(pre + "attn.proj.bias"))
         h2 = ln(x, f8(pre + "norm2.weight"), f8(pre + "norm2.bias"), ch["scale_mlp"], ch["shift_mlp"])
-        h2 = gelu64(h2 @ f8(pre + "mlp.fc1.weight").T + f8(pre + "mlp.fc1.bias"))
+        h2 = _gelu64_torch(h2 @ f8(pre + "mlp.fc1.weight").T + f8(pre + "mlp.fc1.bias"))
         x = x + ch["gate_mlp"] * (h2 @ f8(pre + "mlp.fc2.weight").T + f8(pre + "mlp.fc2.bias"))
     fm = sc @ f8("adaln_before_head.adaLN_modulation.1.weight").T + f8("adaln_before_head.adaLN_modulation.1.bias")
     fo = final_offsets(0, d)

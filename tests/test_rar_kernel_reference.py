@@ -1,7 +1,10 @@
 """CPU proof that the checks of tests/rar_kernel_reference.py bite: each test plants ONE fault into the numpy statement of a
 kernel's output -- the faults a 5e-4 logit gate behind a LayerNorm lets through -- and shows its check failing, and passing on the
 unmodified statement.  The "kernel outputs" are fp32 numpy evaluations built from the reference module's own statements.  The
-composition of the float64 statements is held to oracle.rar_oracle.rar_position."""
+composition of the float64 statements is held to oracle.rar_oracle.rar_position (head_dim 32, 48 and 88).  The plans of the four
+released sizes are pinned against a table written down by hand, and the faults tests/test_gpu_rar_released.py exists for -- a k_bx
+that stops behind step 4 at PER 8, slab 6 of 8, the third QKV piece, buffer B's refill, the last chunk of an odd count, a stale
+appended row at chunk phase 2..5, the tail partial of the wrong lane row -- are planted into the loop statement attn_loop64."""
 import numpy as np
 import pytest
 import torch
@@ -290,12 +293,15 @@ def test_expected_plan_pins_the_paths_of_the_test_engines():
     assert p((128, 4, 512, 2), 128, fused=False)["roles"]["resid_attn"] == "k_resid_mod<1,1,1>+k_resid_mod<1,1,2>"
 
 
-def test_composition_against_the_oracle():
-    """the float64 statements composed into one position against oracle.rar_oracle.rar_position.  The oracle is fp32 torch; the
-    yardstick is what fp32 costs it: the same torch code evaluated in float64"""
+@pytest.mark.parametrize("hidden,heads", [(64, 2), (96, 2), (176, 2)], ids=["hd32", "hd48", "hd88"])
+def test_composition_against_the_oracle(hidden, heads):
+    """the float64 statements composed into one position against oracle.rar_oracle.rar_position (head_dim 32, and 48 / 88 as in RAR-B /
+    RAR-XXL: lanes padded to 16 / 32 in head_sum32).  The oracle is fp32 torch; the yardstick is what fp32 costs it: the same torch
+    code evaluated in float64"""
     from oracle.rar_oracle import rar_position
     from wmar_amd.utils.synth import RARConfig, synth_rar_state
-    cfg = RARConfig(hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=128, image_seq_len=8, codebook_size=32, condition_num_classes=4)
+    cfg = RARConfig(hidden_size=hidden, num_hidden_layers=2, num_attention_heads=heads, intermediate_size=128, image_seq_len=8, codebook_size=32,
+                    condition_num_classes=4)
     sd32 = synth_rar_state(cfg, seed=3, logit_scale=4.0)
     sd64 = {k: v.double() for k, v in sd32.items()}
     sdn = {k: v.numpy() for k, v in sd32.items()}
@@ -316,3 +322,199 @@ def test_composition_against_the_oracle():
         assert np.abs(ln - l32.numpy()).max() <= 2.0 * cost, (p, float(np.abs(ln - l32.numpy()).max()), cost)
         for i in range(cfg.num_hidden_layers):
             assert np.abs(kcn[i] - kc64[i].numpy()).max() <= 1e-11 and np.abs(vcn[i] - vc64[i].numpy()).max() <= 1e-11
+
+
+# ------------------------------------------------------------------------------------------------------------------- the released sizes
+def test_the_wrapper_still_ships_the_pinned_sizes():
+    """the (width, depth, F) the pins below stand for are the ones RarARMMWrapper builds; 16 heads each"""
+    from wmar_amd.models import rar_wrapper
+    assert set(rar_wrapper._RAR_SIZES) == set(R.RELEASED_WRAPPER)
+    for size, (name, depth) in R.RELEASED_WRAPPER.items():
+        Dm, Hm, F = R.RELEASED_SHAPES[name]
+        assert tuple(rar_wrapper._RAR_SIZES[size]) == (Dm, depth, F), size
+        assert (Hm, Dm // Hm) == (16, {"RB": 48, "RL": 64, "RXL": 80, "RXXL": 88}[name])
+
+
+PINS = R.released_pins()
+
+
+@pytest.mark.parametrize("name,M", sorted(PINS), ids=str)
+def test_expected_plan_pins_the_released_sizes(name, M):
+    """the plan of every released size at 20 / 64 / 97 / 127 / 128 rows (max_batch 64, one block, vocabulary 256) and of the two
+    synthetic k_bx<2,16,4> / <2,20,4> shapes, against the table written down by hand: a dispatch change shows without a GPU"""
+    Dm, Hm, F = R.RELEASED_SHAPES[name]
+    plan = R.expected_plan(Dm, Hm, F, 1, 256, 64, M, M, 0)
+    R.check_pins(plan, PINS[(name, M)], (name, M))
+    assert plan["kpw"] == 1 and plan["ada_bx"] == (1 if (name, M) == ("RXL", 64) else 0)
+    # shared_u (guidance: 2 x 64 rows) changes the adaLN row tiles only
+    if M == 128:
+        sh = R.expected_plan(Dm, Hm, F, 1, 256, 64, 128, 64, 1)
+        R.check_pins(sh, PINS[(name, M)], (name, M, "shared_u"))
+        assert sh["MTc"] == 2
+
+
+def test_the_pins_are_checked():
+    plan = R.expected_plan(768, 16, 3072, 1, 256, 64, 128, 128, 0)
+    _fails(R.check_pins, plan, dict(PINS[("RB", 128)], PER_fc2=4))
+    _fails(R.check_pins, plan, dict(roles=dict(fc2="k_bx<2,4,4>")))
+    _fails(R.check_pins, R.expected_plan(768, 16, 3072, 1, 256, 64, 128, 128, 0, no_bx=True), PINS[("RB", 128)])
+
+
+# ------------------------------------------------------------------------------------------------------------------- released widths: planted faults
+def _int_gemm(seed, N, K, M):
+    rs = RS(seed)
+    W = rs.randint(-4, 5, size=(N, K)).astype(np.float32)
+    X = (rs.randint(-2, 3, size=(32, K)) * 0.25 * (rs.rand(32, K) < 1.0 / 16)).astype(np.float32)
+    X[M:] = 3.0e30
+    return W, X
+
+
+def _as_slabs(P64, n_pieces, M):
+    got = np.full((n_pieces, 32, P64.shape[2]), R.SENTINEL, dtype=np.float32)
+    got[:P64.shape[0], :M] = P64.astype(np.float32)
+    return got
+
+
+def test_a_k_bx_that_stops_behind_step_4_at_per_8():
+    """RAR-B's FC2 at 128 rows in small: k_bx at PER 8, S slabs of 64 k-blocks; the integer-operand check sees a wave that leaves
+    its steps 5..8 out"""
+    N, S, PER, M = 64, 2, 8, 9
+    W, X = _int_gemm(20, N, S * 64 * PER, M)
+    rng = R.bx_ranges(N // 32, S, PER)
+    R.check_gemm_exact(_as_slabs(R.bx_pieces64(W, X[:M], N // 32, S, PER), S + 1, M), W, X, rng, M)
+    _fails(R.check_gemm_exact, _as_slabs(R.bx_pieces64(W, X[:M], N // 32, S, PER, fault="drop_steps_5_8"), S + 1, M), W, X, rng, M)
+    # a piece past the plan that was written is caught by the same check
+    over = _as_slabs(R.bx_pieces64(W, X[:M], N // 32, S, PER), S + 1, M)
+    over[S, :M] = 0.0
+    _fails(R.check_gemm_exact, over, W, X, rng, M)
+
+
+def test_slab_6_of_8_missing_in_the_fold():
+    rs = RS(21)
+    M, S = 9, 8
+    x = rs.randint(-64, 65, size=(M, D)).astype(np.float32)
+    slabs = [rs.randint(-512, 513, size=(M, D)).astype(np.float32) for _ in range(S)]
+    bias = rs.randint(-2, 3, size=D).astype(np.float32)
+    gate = (2.0 ** rs.randint(-2, 3, size=(M, D))).astype(np.float32)
+    want = R.gated_fold32(x, gate, bias, slabs)
+    R.check_exact(R.gated_fold32(x, gate, bias, slabs), want, "gated fold")
+    _fails(R.check_exact, R.gated_fold32(x, gate, bias, slabs, fault="missing_slab6"), want, "gated fold")
+    # dense: outside the derived distance as well
+    ss = [rs.standard_normal((M, D)).astype(np.float32) for _ in range(S)]
+    xs, gd = rs.standard_normal((M, D)).astype(np.float32), rs.standard_normal((M, D)).astype(np.float32)
+    v, tol = R.gated_fold64(xs, gd, bias, ss)
+    assert np.all(np.abs(R.gated_fold32(xs, gd, bias, ss).astype(np.float64) - v) <= tol)
+    assert np.any(np.abs(R.gated_fold32(xs, gd, bias, ss, fault="missing_slab6").astype(np.float64) - v) > tol)
+
+
+def test_the_third_qkv_piece_at_head_dim_48():
+    """S = 3 pieces on the four row groups of a head_dim-48 prologue (S < RPI): the third piece dropped moves the plain v row (bit
+    check) and the k-normed row (2 x the fp32 algebra, and the derived distance)"""
+    hd, Hh = 48, 2
+    Dm = hd * Hh
+    assert R.attn_row_groups(hd) == 4 and R.attn_row_groups(64) == 4 and R.attn_row_groups(88) == 2 and R.attn_row_groups(32) == 8
+    rs = RS(22)
+    P = (rs.standard_normal((3, 7, 3 * Dm)) * 0.4).astype(np.float32)
+    vec = lambda s, o: (o + s * rs.standard_normal(hd)).astype(np.float32)  # noqa: E731
+    bias, qw, qb, kw, kb = (rs.standard_normal(3 * Dm) * 0.1).astype(np.float32), vec(0.1, 1), vec(0.1, 0), vec(0.1, 1), vec(0.1, 0)
+    (q64, k64, v64), (q32, k32, v32), (nq, nk, nv) = R.attn_prologue(P, bias, qw, qb, kw, kb, Hh, hd)
+    assert np.all(np.abs(k32 - k64) <= R.prologue_tol(nk, hd))
+    _, (fq, fk, fv), _ = R.attn_prologue(P, bias, qw, qb, kw, kb, Hh, hd, fault="drop_piece3")
+    _fails(R.check_exact, fv, v32, "V row")
+    _fails(R.check_appended, fk, k64, nk, k32, "K row")
+    assert np.any(np.abs(fk - k64) > R.prologue_tol(nk, hd))
+
+
+def _loop_case(hd, T, seed=23, M=3, Hh=2):
+    """a one-hot and a dense cache of T rows (the new one last) as the GPU sweep lays them out: 3e30 at and past row T - 1"""
+    rs = RS(seed + T)
+    q = rs.standard_normal((M, Hh, hd)).astype(np.float32)
+    knew, vnew = rs.standard_normal((M, Hh, hd)).astype(np.float32), rs.standard_normal((M, Hh, hd)).astype(np.float32)
+    Kd = rs.standard_normal((M, Hh, T + 2, hd)).astype(np.float32)
+    Vc = rs.standard_normal((M, Hh, T + 2, hd)).astype(np.float32)
+    Kd[:, :, T - 1:] = 3.0e30
+    Vc[:, :, T - 1:] = 3.0e30
+    return q, knew, vnew, Kd, Vc
+
+
+def _onehot_caught(hd, T, E, fault):
+    """does the one-hot sweep (every cached position the winner of some pair) see the fault at this length?"""
+    q, knew, vnew, Kd, Vc = _loop_case(hd, T)
+    scale = 1.0 / np.sqrt(hd)
+    for win in range(T - 1):
+        Ko = Kd.copy()
+        Ko[:, :, :T - 1] *= 0.01
+        Ko[:, :, win] = q * (400.0 / scale) / (q.astype(np.float64) ** 2).sum(-1, keepdims=True)
+        y = R.attn_loop64(q, Ko, Vc, knew, vnew, T, hd, E, fault).astype(np.float32)
+        if fault is None:
+            R.check_onehot(y, Vc[:, :, win])
+        elif R.diff_bits(y, Vc[:, :, win]):
+            return True
+    return False
+
+
+def _dense_caught(hd, T, E, fault):
+    q, knew, vnew, Kd, Vc = _loop_case(hd, T)
+    scale = 1.0 / np.sqrt(hd)
+    K64 = np.concatenate([Kd[:, :, :T - 1], knew[:, :, None]], 2).astype(np.float64)
+    V64 = np.concatenate([Vc[:, :, :T - 1], vnew[:, :, None]], 2).astype(np.float64)
+    zero = np.zeros(q.shape)
+    ref, tol = R.attn_dense_bound(q.astype(np.float64), zero, K64, zero, V64, zero, scale, E, 1)
+    y = R.attn_loop64(q, Kd, Vc, knew, vnew, T, hd, E, fault).astype(np.float32)
+    if fault is None:
+        assert R.check_attn_dense(y, ref, tol) <= 1.0
+        assert np.allclose(y, R.attn_mode1_ref(q.astype(np.float64), K64, V64, hd), rtol=1e-5, atol=1e-6)
+        return False
+    return bool(np.any(np.abs(y - ref) > tol)) or not np.isfinite(y).all()
+
+
+@pytest.mark.parametrize("hd,E", [(48, 8), (80, 8), (88, 4)])
+def test_the_loop_statement_is_the_plain_softmax(hd, E):
+    for T in (1, 2, E, E + 1, 3 * E + 2, 4 * E + 1):
+        assert not _dense_caught(hd, T, E, None)
+        if T > 1:
+            assert not _onehot_caught(hd, T, E, None)
+
+
+def test_buffer_b_refilled_from_chunk_1_again():
+    """the refill `c + 3 NWA` of buffer B: first consumed in chunk 3, whose first slot is a cached row from 3 E + 2 rows on (at
+    3 E + 1 it holds the new row, which comes from registers) -- 18 rows at E = 8 never get there"""
+    hd, E = 80, 8
+    assert R.attn_loop_rows(18, E, hd, "refill_b_chunk1") == R.attn_loop_rows(18, E, hd)           # the parent's longest cache: invisible
+    for T in (3 * E + 2, 4 * E + 1, 8 * E):
+        assert _onehot_caught(hd, T, E, "refill_b_chunk1") and _dense_caught(hd, T, E, "refill_b_chunk1")
+    assert not _onehot_caught(hd, 3 * E + 1, E, "refill_b_chunk1") and not _dense_caught(hd, 3 * E + 1, E, "refill_b_chunk1")
+
+
+def test_the_last_chunk_skipped_at_an_odd_chunk_count():
+    """`if (c + NWA < nchunk)` guards buffer B; a loop that stops a pair early loses the last chunk of an odd count"""
+    hd, E = 64, 8
+    for T in (2 * E + 1, 2 * E + 2, 3 * E, 4 * E + 1, 4 * E + 3):          # 3, 3, 3, 5 and 5 chunks
+        # (the last chunk of k E + 1 rows holds the new row alone: no cached winner lives there, the dense check is the one that sees it)
+        assert _onehot_caught(hd, T, E, "skip_last_odd") == (T % E != 1)
+        assert _dense_caught(hd, T, E, "skip_last_odd")
+    assert not _dense_caught(hd, 4 * E, E, "skip_last_odd") and not _onehot_caught(hd, 4 * E, E, "skip_last_odd")
+
+
+@pytest.mark.parametrize("hd,E", [(80, 8), (48, 8)])
+def test_the_appended_row_taken_from_the_stale_cache_row(hd, E):
+    """phases (T - 1) mod E = 2..5 of the appended row: the parent's lengths 1 / E - 1 / E / E + 1 / 2 E + 1 / 18 land on 0, 1, 6, 7
+    only.  The sweep fills rows at and past T - 1 with 3e30, so a stale row wins (one-hot) or poisons the output (dense)"""
+    assert sorted({(t - 1) % E for t in (1, E - 1, E, E + 1, 2 * E + 1, 18)}) == [0, 1, 6, 7]
+    for ph in (2, 3, 4, 5):
+        for T in (ph + 1, E + ph + 1, 3 * E + ph + 1):
+            assert _dense_caught(hd, T, E, "stale_append")
+            if T > 1:
+                assert _onehot_caught(hd, T, E, "stale_append")
+    for T in (1, E, E + 1, 2 * E + 1, 18):
+        assert not _dense_caught(hd, T, E, "stale_append")
+
+
+def test_the_tail_partial_of_the_wrong_lane_row_at_head_dim_80():
+    """k_attn_decode80: the score of row 4 u + g16 takes its last 16 floats from quad u of ITS 16-lane row.  A neighbouring row's quad
+    leaves every one-hot winner in place (the main 64 floats lead by far) -- the dense check is the one that sees it"""
+    hd, E = 80, 8
+    for T in (E + 3, 4 * E + 1, 97):
+        assert _dense_caught(hd, T, E, "tail_wrong_row")
+    assert not _onehot_caught(hd, E + 3, E, "tail_wrong_row")
+    assert R.attn_loop_rows(33, 8, 48, "tail_wrong_row") == R.attn_loop_rows(33, 8, 48)            # other head_dims have no tail

@@ -1907,6 +1907,30 @@ static int launch_bx_xr(const BxrArgs& q, int N, hipStream_t st) {
 #else
 #define WMAR_KV_LD(P) (*(P))
 #endif
+// a + b in fp32 and, in err, what that addition rounded away (Knuth's TwoSum: exact for any order of |a|, |b|; no multiplication, so
+// -ffp-contract cannot touch it)
+__device__ __forceinline__ float two_sum(float a, float b, float& err) {
+    const float s = a + b, bb = s - a;
+    err = (a - (s - bb)) + (b - bb);
+    return s;
+}
+// (s, c) += (x, xc) per component: s the running fp32 sum, c the sum of what its additions rounded away
+__device__ __forceinline__ void csum4_add(float4& s, float4& c, const float4 x, const float4 xc) {
+    float e;
+    s.x = two_sum(s.x, x.x, e); c.x += xc.x + e;
+    s.y = two_sum(s.y, x.y, e); c.y += xc.y + e;
+    s.z = two_sum(s.z, x.z, e); c.z += xc.z + e;
+    s.w = two_sum(s.w, x.w, e); c.w += xc.w + e;
+}
+// (s + b) + (c + what s + b rounded away): the piece sum plus bias, rounded (almost always) once
+__device__ __forceinline__ float4 csum4_finish(const float4 s, const float4 c, const float4 b) {
+    float4 r; float e;
+    r.x = two_sum(s.x, b.x, e); r.x += c.x + e;
+    r.y = two_sum(s.y, b.y, e); r.y += c.y + e;
+    r.z = two_sum(s.z, b.z, e); r.z += c.z + e;
+    r.w = two_sum(s.w, b.w, e); r.w += c.w + e;
+    return r;
+}
 // One wave per (sequence, head).  K/V rows are hd floats; LPR = hd/4 lanes cover a row with
 // float4s and RPI = 64/LPR rows are read per wave-wide load (1 KiB, coalesced).
 struct AttnArgs {
@@ -2058,10 +2082,28 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
         const double mean = sm * invK;
         const float mu = (float)mean;
         const float rstd = rsqrtf((float)var_f64(sq * invK, mean) + 1e-5f);
-        float4 accs[3];
+        float4 accs[3], accc[2];     // accc (mode 1): what the additions of the q and k pieces rounded away (csum4_add)
 #pragma unroll
         for (int which = 0; which < 3; ++which) {
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (MODE == 1 && which < 2) {
+                // q and k go through a LayerNorm over their head: an element that cancels in the piece sum keeps the roundings of
+                // the partial sums, which the norm then scales by rstd -- several times the element's own ulp.  The pieces are
+                // added with their rounding errors carried along (same order: per row group, then the groups' butterfly).
+                float4 cc4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int pi = 0; pi < PMAX; ++pi)
+                    if (rsel + pi * RPI < a.S) csum4_add(acc, cc4, sl[which][pi], zero);
+#pragma unroll
+                for (int o = LPR; o < 64; o <<= 1) {
+                    const float4 ps = make_float4(__shfl_xor(acc.x, o), __shfl_xor(acc.y, o), __shfl_xor(acc.z, o), __shfl_xor(acc.w, o));
+                    const float4 pc = make_float4(__shfl_xor(cc4.x, o), __shfl_xor(cc4.y, o), __shfl_xor(cc4.z, o), __shfl_xor(cc4.w, o));
+                    csum4_add(acc, cc4, ps, pc);
+                }
+                accs[which] = acc; accc[which] = cc4;
+                continue;
+            }
 #pragma unroll
             for (int pi = 0; pi < PMAX; ++pi)
                 if (rsel + pi * RPI < a.S) {
@@ -2085,6 +2127,8 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
                                            rstd * (acc.y - mu * cc[which].y) + bb[which].y,
                                            rstd * (acc.z - mu * cc[which].z) + bb[which].z,
                                            rstd * (acc.w - mu * cc[which].w) + bb[which].w);
+                } else if (which < 2) {
+                    r[which] = csum4_finish(acc, accc[which], bb[which]);
                 } else {
                     r[which] = make_float4(acc.x + bb[which].x, acc.y + bb[which].y, acc.z + bb[which].z, acc.w + bb[which].w);
                 }
@@ -2318,6 +2362,8 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode80(AttnArgs a) {
         const double mean = sm * invK;
         const float mu = (float)mean;
         const float rstd = rsqrtf((float)var_f64(sq * invK, mean) + 1e-5f);
+        // (the plain fp32 piece sum for q and k as well, unlike k_attn_decode<.., MODE 1>: RAR-XL's tokens are pinned one by one against
+        // the oracle at this width, and its 80-value norm holds the derived distance with the plain sum)
         float4 accs[3];
 #pragma unroll
         for (int which = 0; which < 3; ++which) {
