@@ -1,6 +1,6 @@
 // Dev tool: k_fc1x (24-column tiles, 256 workgroups) against k_gemm<2,4,EPI_GELU,LN> (32-column tiles, 192 workgroups) on the
 // same inputs: max |difference| of the packed hidden activation and time per launch (weights cycling through 12 buffers).
-//#define WMAR_FX_TRACE 1
+// With -DWMAR_STAMPS also the in-loop stamps of k_fc1x's wave 0, averaged over the workgroups.
 #include "../wmar_amd/csrc/gpt.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -40,7 +40,7 @@ int main() {
     g.out_packed = o1; g.B = 64;
     Fc1xArgs f{};
     f.Xp = X; f.bias = bias; f.c1 = c1; f.stats = stats; f.n_chunks = nch; f.K = K; f.out = o2; f.KU = K / 16;
-    unsigned long long* tr; (void)hipMalloc(&tr, 256 * 4 * 8); (void)hipMemset(tr, 0, 256 * 4 * 8); f.trace = tr;
+    unsigned long long* tr; (void)hipMalloc(&tr, 256 * 8 * 8); (void)hipMemset(tr, 0, 256 * 8 * 8); f.trace = tr;
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     for (int which = 0; which < 2; ++which)
         for (int rep = 0; rep < 3; ++rep) {
@@ -53,8 +53,8 @@ int main() {
             float ms; (void)hipEventElapsedTime(&ms, e0, e1);
             if (rep == 2) printf("%s: %.2f us per launch\n", which ? "k_fc1x (256 x 24 columns)" : "k_gemm (192 x 32 columns)", ms * 1000.f / NL);
         }
-    { std::vector<unsigned long long> h(256 * 4); (void)hipMemcpy(h.data(), tr, h.size() * 8, hipMemcpyDeviceToHost);
-      double s1 = 0, s2 = 0, s3 = 0; for (int i = 0; i < 256; ++i) { s1 += h[i*4+1]-h[i*4]; s2 += h[i*4+2]-h[i*4+1]; s3 += h[i*4+3]-h[i*4+2]; }
+    { std::vector<unsigned long long> h(256 * 8); (void)hipMemcpy(h.data(), tr, h.size() * 8, hipMemcpyDeviceToHost);     // WMAR_STAMPS: [1] entry, [2] landed, [3] loop done, [4] exit
+      double s1 = 0, s2 = 0, s3 = 0; for (int i = 0; i < 256; ++i) { s1 += h[i*8+2]-h[i*8+1]; s2 += h[i*8+3]-h[i*8+2]; s3 += h[i*8+4]-h[i*8+3]; }
       printf("k_fc1x ticks (wave 0 avg): first operands %.0f, main loop %.0f, epilogue %.0f\n", s1/256, s2/256, s3/256); }
     std::vector<float> a(hid * 4), b(hid * 4);
     (void)hipMemcpy(a.data(), o1, a.size() * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(b.data(), o2, b.size() * 4, hipMemcpyDeviceToHost);

@@ -140,17 +140,11 @@ __device__ __forceinline__ float cham_rstd(const double* __restrict__ ssq, int n
 // same number of weight bytes whatever N and K are.  When a workgroup leaves a group it writes its
 // partial sums as one "piece" of that group; consumers add the pieces of a group in piece order
 // (fixed, so results do not depend on timing).  sk_* below is the shared index arithmetic.
-#ifndef WMAR_BG_KC
-#define WMAR_BG_KC 8
-#endif
-constexpr int BG_KC = WMAR_BG_KC;         // k-blocks (of 16) per unit
-#ifndef WMAR_BG_TG
-#define WMAR_BG_TG 4
-#endif
+constexpr int BG_KC = 8;         // k-blocks (of 16) per unit
 // column tiles per group: the waves of a workgroup share one staged activation chunk.  4 (one tile per wave), not 8: a group's K range is
 // then cut into half as many pieces -- the fp32 partial-sum pieces of the four GEMMs of a block were 66 MB written and read again per
 // 422 MB of weights; measured 5.15 -> 4.67 ms per step on the 7B model (the activation chunk is read twice as often from L2 instead)
-constexpr int BG_TG = WMAR_BG_TG;
+constexpr int BG_TG = 4;
 constexpr int BG_MAXP = 16;      // pieces per group the slab buffers are sized for
 enum { BEPI_SLAB = 0, BEPI_LOGITS = 2 };
 
@@ -496,14 +490,12 @@ static __global__ void k_rope_table(float2* tab, int T, int half, float theta) {
     tab[idx] = make_float2(cs, sn);
 }
 
-#ifndef WMAR_CHAM_ATT_CH
-#define WMAR_CHAM_ATT_CH 4      // 1-KiB loads of K (and of V) per chunk of k_cham_attn (bf16 rows: 16 cached rows of head_dim 128 at 4)
-#endif
+constexpr int CHAM_ATT_CH = 4;  // 1-KiB loads of K (and of V) per chunk of k_cham_attn (bf16 rows: 16 cached rows of head_dim 128 at 4)
 template <int HD, int NWA>
 __global__ __launch_bounds__(NWA * 64) void k_cham_attn(ChamAttnArgs a) {
     constexpr int LPR = HD / 8;            // lanes per cached row (8 bf16 each)
     constexpr int RPI = 64 / LPR;          // rows per wave-wide load
-    constexpr int CH = WMAR_CHAM_ATT_CH;
+    constexpr int CH = CHAM_ATT_CH;
     constexpr int ROWS = CH * RPI;
     __shared__ __attribute__((aligned(16))) float part[NWA][HD + 4];
     __shared__ __attribute__((aligned(16))) float qkv_s[3][HD];
@@ -518,12 +510,8 @@ __global__ __launch_bounds__(NWA * 64) void k_cham_attn(ChamAttnArgs a) {
     uint16_t* Vc = a.vcache + (((long long)m * a.Hkv + hk) * a.Tmax) * HD + sub * 8;
     const int nchunk = (T + ROWS - 1) / ROWS;
 
-// K/V rows stream once per step: non-temporal loads (see k_attn_decode; -DWMAR_ATT_PLAIN_KV restores plain loads)
-#ifndef WMAR_ATT_PLAIN_KV
+// K/V rows stream once per step: non-temporal loads (see k_attn_decode)
 #define CA_KV_LD(P_) ld_nt_u4((const uint4*)(P_))
-#else
-#define CA_KV_LD(P_) (*(const uint4*)(P_))
-#endif
 #define CA_LOAD(KB_, VB_, C0)                                                             \
     _Pragma("unroll") for (int u = 0; u < CH; ++u) {                                      \
         const int t = min((C0) * ROWS + u * RPI + rsel, T - 1);                           \

@@ -102,10 +102,8 @@ __device__ __forceinline__ T wave_reduce_many(T (&v)[R], int lane, int* idx_out)
 #pragma unroll
             for (int i = 0; i < P / 2; ++i) {
                 if (i < cnt / 2) {
-#ifndef WMAR_SG_NO_SWAP
                     if (step == 0) { t[i] = tb_pair<32>(t[2 * i], t[2 * i + 1]); continue; }
                     if (step == 1) { t[i] = tb_pair<16>(t[2 * i], t[2 * i + 1]); continue; }
-#endif
                     const T keep = up ? t[2 * i + 1] : t[2 * i];
                     const T send = up ? t[2 * i] : t[2 * i + 1];
                     t[i] = keep + __shfl_xor(send, off);
@@ -114,12 +112,9 @@ __device__ __forceinline__ T wave_reduce_many(T (&v)[R], int lane, int* idx_out)
             idx |= (up ? 1 : 0) << j;
             cnt /= 2; ++j;
         } else {
-#ifndef WMAR_SG_NO_SWAP
             if (step == 0) t[0] = tb_pair<32>(t[0], t[0]);
             else if (step == 1) t[0] = tb_pair<16>(t[0], t[0]);
-            else
-#endif
-            t[0] += __shfl_xor(t[0], off);
+            else t[0] += __shfl_xor(t[0], off);
         }
         off >>= 1;
     }

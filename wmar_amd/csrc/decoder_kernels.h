@@ -20,15 +20,11 @@ __device__ __forceinline__ float4 ld_nt(const float4* p) {
 // Output the NEXT kernel reads (QKV split-K pieces: 8.3 MB per launch, FC2 slabs, the hidden activation): a write-through store (sc1),
 // so the bytes leave the XCD's L2 while the kernel runs instead of in the write-back at its end, which the next kernel waits for
 // (guide: boundary + dirty bytes / 6 TB/s).  Round 4, same-box A/B over the 256-step loop: 4.140 -> 4.110 ms per step.  Same values,
-// only the cache policy differs; -DWMAR_PLAIN_STORES restores plain stores.  (Data a later phase of the SAME launch reads through the
-// L2 -- the slabs of k_bx_xr -- must stay plain: an sc1 store drops the line.)
+// only the cache policy differs.  (Data a later phase of the SAME launch reads through the L2 -- the slabs of k_bx_xr -- must stay
+// plain: an sc1 store drops the line.)
 __device__ __forceinline__ void st_out(float4* p, const float4 v) {
-#ifndef WMAR_PLAIN_STORES
     const f32x4 q = {v.x, v.y, v.z, v.w};
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(q) : "memory");
-#else
-    *p = v;
-#endif
 }
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 __device__ __forceinline__ float2 ld_nt2(const float2* p) {
@@ -42,7 +38,9 @@ __device__ __forceinline__ float2 ld_nt2(const float2* p) {
 // table of DESIGN section 6): [0] s_memrealtime at entry (100 MHz, chip-wide: gaps BETWEEN launches), [1] s_memtime at entry,
 // [2] first operands landed, [3] main loop done, [4] exit (stores issued and acknowledged), [5] s_memrealtime at exit, [6] a kernel-
 // specific mark (k_bx_xr: barrier passed; attention: q/k/v finished), [7] the XCC id.  The "landed" stamp waits for the first loads
-// with s_waitcnt vmcnt(0): a diagnostic build, a few percent slower than the product.
+// with s_waitcnt vmcnt(0): a diagnostic build, a few percent slower than the product.  (Attention records [2] only with one wave per
+// (sequence, head), where the product waits at that point too; the 2- and 4-wave kernels leave it 0 and scripts/stamp_table.py then
+// counts from the entry stamp.)
 #ifdef WMAR_STAMPS
 #define WMAR_ST_BEGIN unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; st_[0] = __builtin_amdgcn_s_memrealtime(); st_[1] = __builtin_amdgcn_s_memtime();
 #define WMAR_ST(I) { asm volatile("" ::: "memory"); st_[I] = __builtin_amdgcn_s_memtime(); }
@@ -67,9 +65,7 @@ constexpr int MAX_SLABS = 8;
 constexpr int QKV_SLABS_MAX = 8;   // the QKV projection arrives in at most 8 split-K pieces
 constexpr int STAT_CHUNKS_MAX = 64;   // n_embd <= 8192
 constexpr int GEMM_STAGE = 4;   // k-blocks (of 8) per register stage of the skinny GEMM
-#ifndef WMAR_GEMM_INTERLEAVE
-#define WMAR_GEMM_INTERLEAVE 2   // MFMAs between two operand loads of the main loop (0: loads in one batch per stage)
-#endif
+constexpr int GEMM_INTERLEAVE = 2;   // MFMAs between two operand loads of the main loop
 
 // ------------------------------------------------------------------------ weight packing
 // gamma (nullable): the LayerNorm scale of the layer that feeds this Linear, folded into
@@ -268,7 +264,7 @@ struct GemmArgs {
     long long unused_[6];                               // arguments of the removed epilogue 2: the fields below keep their kernel-argument offsets
     float* logits; int V;                               // EPI_LOGITS
     int B;
-    unsigned long long* trace;                          // dev only (WMAR_GEMM_TRACE): 4 timestamps per workgroup
+    unsigned long long* trace;                          // dev only (WMAR_STAMPS): 8 stamps per workgroup
 };
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
@@ -315,9 +311,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
     }
     const int half = lane >> 5;
     WMAR_ST_BEGIN
-#ifdef WMAR_GEMM_TRACE
-    unsigned long long tr0 = __builtin_amdgcn_s_memtime(), tr1 = 0, tr2 = 0;
-#endif
 
     f32x16 acc[NTW][MTW];
 #pragma unroll
@@ -396,20 +389,15 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
         WMAR_LN_PROLOGUE
         __builtin_amdgcn_sched_barrier(0);
         WMAR_ST_LANDED(2)
-#ifdef WMAR_GEMM_TRACE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tr1 = __builtin_amdgcn_s_memtime();
-#endif
-#if WMAR_GEMM_INTERLEAVE > 0
-        // one load between every WMAR_GEMM_INTERLEAVE MFMAs: a wave issues in order, so a batch of loads in front of the MFMAs
+        // one load between every GEMM_INTERLEAVE MFMAs: a wave issues in order, so a batch of loads in front of the MFMAs
         // keeps the matrix pipe idle for as long as the batch takes to issue (~30 cycles per 1 KiB load); one load fits in the
         // 64-cycle shadow of an MFMA
 #define WMAR_INTERLEAVE()                                                                          \
         _Pragma("unroll") for (int i_ = 0; i_ < U * (NTW + MTW); ++i_) {                          \
-            __builtin_amdgcn_sched_group_barrier(0x008, WMAR_GEMM_INTERLEAVE, 0);                  \
+            __builtin_amdgcn_sched_group_barrier(0x008, GEMM_INTERLEAVE, 0);                       \
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                     \
         }                                                                                          \
-        __builtin_amdgcn_sched_group_barrier(0x008, 4 * U * MTW * NTW - WMAR_GEMM_INTERLEAVE * U * (NTW + MTW), 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4 * U * MTW * NTW - GEMM_INTERLEAVE * U * (NTW + MTW), 0);
         for (int it = 0; it < nfull; ++it) {
             WMAR_LOAD(wB, xB, WMAR_STAGE_KB(2 * it + 1))
             WMAR_MMA(wA, xA)
@@ -421,19 +409,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
             __builtin_amdgcn_sched_barrier(0);
         }
 #undef WMAR_INTERLEAVE
-#else
-        for (int it = 0; it < nfull; ++it) {
-            WMAR_LOAD(wB, xB, WMAR_STAGE_KB(2 * it + 1))
-            __builtin_amdgcn_sched_barrier(0);
-            WMAR_MMA(wA, xA)
-            __builtin_amdgcn_sched_barrier(0);
-            // last round: re-read an in-bounds stage instead of branching around the loads
-            WMAR_LOAD(wA, xA, WMAR_STAGE_KB((2 * it + 2) % nst))
-            __builtin_amdgcn_sched_barrier(0);
-            WMAR_MMA(wB, xB)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
 #undef WMAR_STAGE_KB
         kb = kb0 + nst * U;
     } else {
@@ -472,9 +447,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
 #undef WMAR_MMA
 
     WMAR_ST(3)
-#ifdef WMAR_GEMM_TRACE
-    tr2 = __builtin_amdgcn_s_memtime();
-#endif
     // in-workgroup K reduction (fixed order) + epilogue
     // 16-byte LDS accesses: a wave parks its accumulators as MTW*4 float4 rows (the 4 registers of one output group are
     // adjacent) and the reducing wave reads one float4 per partner -- a quarter of the LDS instructions of a dword layout
@@ -530,13 +502,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
         }
     }
     WMAR_ST_END(a.trace, blockIdx.x)
-#ifdef WMAR_GEMM_TRACE
-    if (a.trace && threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* t = a.trace + (long long)blockIdx.x * 4;
-        t[0] = tr0; t[1] = tr1; t[2] = tr2; t[3] = __builtin_amdgcn_s_memtime();
-    }
-#endif
 }
 
 // --------------------------------------------------------- FC1 (+ LayerNorm algebra + GELU) on 24-column tiles
@@ -554,9 +519,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs a) {
 // partial sums of a row sit in different blocks (16x16: different registers, 4x4: lanes l and l+32) and are added once, after
 // the K loop.  Four waves split K and meet in LDS (fixed order), as in k_gemm.  (First version: operands turned into "row =
 // lane" registers with v_permlane32_swap and one accumulator set -- each swap in front of its MFMA cost ~20 cycles of idle pipe.)
-#ifndef FX_ABL
-#define FX_ABL 0     // dev ablations: 1 = no loads in the main loop, 4 = no 4x4 MFMAs
-#endif
 struct Fc1xArgs {
     const float4* W16;         // [N/24][K/16][64] x 4 registers: register q, lane 16*blk + col: pair 2q + (blk&1), k or k+4 by blk>>1
     const float2* W8;          // [N/24][K/16][64] x 2 registers (columns 16-19 / 20-23): lane 4*blk + col: pair blk&7, k or k+4 by blk>>3
@@ -566,7 +528,7 @@ struct Fc1xArgs {
     const double* stats; int n_chunks; int K;
     float4* out;               // packed hidden activation [N/8][2][64]
     int KU;                    // K / 16
-    unsigned long long* trace; // dev only (WMAR_FX_TRACE): 4 timestamps per workgroup
+    unsigned long long* trace; // dev only (WMAR_STAMPS): 8 stamps per workgroup
 };
 
 // pair p = 4*kb + j of a 16-k unit covers k = 8*kb + j ("lo") and k + 4 ("hi")
@@ -641,7 +603,6 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
         if (sel == 1) c16 = __builtin_amdgcn_mfma_f32_16x16x1f32(aq, bv, c16, 1, 1, 0);
     };
     auto fx4 = [&](f32x4& c4a, f32x4& c4b, float bv, const float2& w8v, int pair) {     // 2 x 8 cycles
-        if (FX_ABL & 4) return;
 #define WMAR_FX_CASE(PV)                                                                          \
         if (pair == PV) {                                                                         \
             c4a = __builtin_amdgcn_mfma_f32_4x4x1f32(w8v.x, bv, c4a, 3, PV, 0);                   \
@@ -661,7 +622,7 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
             const float b0 = j == 0 ? XC[kb][0].x : (j == 1 ? XC[kb][0].y : (j == 2 ? XC[kb][0].z : XC[kb][0].w)); \
             const float b1 = j == 0 ? XC[kb][1].x : (j == 1 ? XC[kb][1].y : (j == 2 ? XC[kb][1].z : XC[kb][1].w)); \
             fx16(acc16[0], b0, aq, pair & 1);                                                     \
-            if (!(FX_ABL & 1) && (LOADQ)) {                                                       \
+            if (LOADQ) {                                                                          \
                 if (pair == 0) WQL = ld_nt(W16 + (long long)un_ * 64);                            \
                 if (pair == 1) W8L = ld_nt2(W8 + (long long)un_ * 64);                            \
                 if (pair >= 2 && pair < 6)                                                        \
@@ -676,9 +637,6 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
     }
 
     WMAR_ST_BEGIN
-#ifdef WMAR_FX_TRACE
-    const unsigned long long tr0 = __builtin_amdgcn_s_memtime();
-#endif
     WMAR_FX_LOAD(xA, wqA, w8A, WMAR_FX_UNIT(0))
     WMAR_FX_LOAD(xB, wqB, w8B, WMAR_FX_UNIT(1))
     WMAR_FX_LOAD(xC, wqC, w8C, WMAR_FX_UNIT(2))
@@ -703,10 +661,6 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
     const float4 ccB_ = *(const float4*)(a.c1 + nB_), bbB_ = *(const float4*)(a.bias + nB_);
     __builtin_amdgcn_sched_barrier(0);
     WMAR_ST_LANDED(2)
-#ifdef WMAR_FX_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long tr1 = __builtin_amdgcn_s_memtime();
-#endif
     int it = 0;
     for (; it + 4 < per; it += 4) {
         WMAR_FX_MMA(xA, wqA, w8A, xD, wqD, w8D, WMAR_FX_UNIT(it + 3), true)
@@ -724,9 +678,6 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
 #undef WMAR_FX_UNIT
 
     WMAR_ST(3)
-#ifdef WMAR_FX_TRACE
-    const unsigned long long tr2 = __builtin_amdgcn_s_memtime();
-#endif
     // "k" + "k+4" partial sums, then the cross-wave K reduction in LDS (fixed order), LayerNorm algebra, bias, GELU, packed store.
     // red[w][g]: g = 2*i + b: 16x16 part, rows 32 i + 16 b + lane%16, columns 4*(lane/16)..+3;  g = 4 / 5: columns 16-19 / 20-23, row = lane
 #pragma unroll
@@ -778,13 +729,6 @@ static __global__ __launch_bounds__(256) void k_fc1x(Fc1xArgs a) {
         st_out(a.out + ((long long)(n >> 3) * 2 + (m >> 5)) * 64 + (m & 31) + 32 * ((n >> 2) & 1), make_float4(o[0], o[1], o[2], o[3]));
     }
     WMAR_ST_END(a.trace, blockIdx.x)
-#ifdef WMAR_FX_TRACE
-    if (a.trace && threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* t = a.trace + (long long)blockIdx.x * 4;
-        t[0] = tr0; t[1] = tr1; t[2] = tr2; t[3] = __builtin_amdgcn_s_memtime();
-    }
-#endif
 }
 
 // --------------------------------------------------------- FC2 on 24-column tiles x ONE row tile x half of K (plan variant)
@@ -945,10 +889,6 @@ static __global__ __launch_bounds__(256) void k_fc2x(Fc2xArgs a) {
 //   * every wave stores its accumulators as one of S split-K pieces, which the attention prologue sums in slice order.
 // Weights: a wave walks its own column tile, loads issued two chunks (2 x 2048 MFMA cycles) ahead of use.
 constexpr int QX_CK = 4;      // k-blocks per chunk (one staged by each wave)
-#ifndef QX_ABL
-#define QX_ABL 0     // dev ablations (trace builds): 1 = no weight loads in the loop, 2 = no chunk barriers, 4 = no LDS reads in the loop
-#endif
-#define WMAR_QX_SYNC() if (!(QX_ABL & 2)) __syncthreads();
 #ifndef QX_SPLIT
 #define QX_SPLIT 2             // k-blocks multiplied before the chunk barrier; the next chunk's LDS reads land under the rest
 #endif
@@ -1060,13 +1000,13 @@ __global__ __launch_bounds__(512) void k_qkvx(QkvxArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             WMAR_QX_ISSUE(xvB, bbB, slB, skbB, c + 3)
             __builtin_amdgcn_sched_barrier(0);
-            WMAR_QX_SYNC()                                 // barrier(c)
+            __syncthreads();                               // barrier(c)
             if (c + 2 >= nch) break;
             WMAR_QX_FINISH(xvA, bbA, slA, skbA, 0)         // chunk c+2
             __builtin_amdgcn_sched_barrier(0);
             WMAR_QX_ISSUE(xvA, bbA, slA, skbA, c + 4)
             __builtin_amdgcn_sched_barrier(0);
-            WMAR_QX_SYNC()                                 // barrier(c+1)
+            __syncthreads();                               // barrier(c+1)
         }
 #undef WMAR_QX_ISSUE
 #undef WMAR_QX_FINISH
@@ -1089,9 +1029,6 @@ __global__ __launch_bounds__(512) void k_qkvx(QkvxArgs a) {
     }
 
     // ------------------------------------------------------------------------------------------ multiplying waves
-#ifdef QX_PRIO
-    __builtin_amdgcn_s_setprio(QX_PRIO);
-#endif
     const int nt = g * 4 + w;
     f32x16 acc[MTW];
 #pragma unroll
@@ -1131,13 +1068,13 @@ __global__ __launch_bounds__(512) void k_qkvx(QkvxArgs a) {
 #endif
 #define WMAR_QX_STEP(C, WCUR, WFAR, XCUR, XNEXT, BUFNEXT)                                              \
     WMAR_QX_STAMP(C)                                                                                    \
-    if (!(QX_ABL & 1)) { WMAR_QX_W(WFAR, (C) + 3) }                                                     \
+    WMAR_QX_W(WFAR, (C) + 3)                                                                            \
     __builtin_amdgcn_sched_barrier(0);                                                                  \
     WMAR_QX_MMA(WCUR, XCUR, C, 0, QX_SPLIT)                                                             \
     __builtin_amdgcn_sched_barrier(0);                                                                  \
     if ((C) + 1 < nch) {                                                                                \
-        WMAR_QX_SYNC()                                                                                  \
-        if (!(QX_ABL & 4)) { WMAR_QX_READ(XNEXT, BUFNEXT) }                                             \
+        __syncthreads();                                                                                \
+        WMAR_QX_READ(XNEXT, BUFNEXT)                                                                    \
     }                                                                                                   \
     __builtin_amdgcn_sched_barrier(0);                                                                  \
     WMAR_QX_MMA(WCUR, XCUR, C, QX_SPLIT, QX_CK)                                                         \
@@ -1231,6 +1168,8 @@ static __global__ void k_pack_bx(const float* __restrict__ W, const float* __res
     if (gamma) { v.x *= gamma[k]; v.y *= gamma[k + 1]; v.z *= gamma[k + 2]; v.w *= gamma[k + 3]; }
     Wq[idx + (long long)tile_off * KU * 128] = v;
 }
+
+#define WMAR_BX_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)      // k_qkvx_bx, k_bx, k_bx_xr
 
 constexpr int QX_TR_STRIDE = 36;      // floats per row of the epilogue's transpose tile (32 + 4: 16-byte rows on distinct banks)
 template <int S_IN>
@@ -1368,7 +1307,6 @@ __global__ __launch_bounds__(512) void k_qkvx_bx(QkvxArgs a) {
         _Pragma("unroll") for (int i = 0; i < MTW; ++i)                                                 \
             _Pragma("unroll") for (int p = 0; p < 3; ++p) XF[st][i][p] = xq[BUF][st][i][p][lane];
 #define WMAR_QX_BF(V) __builtin_bit_cast(bf16x8, V)
-#define WMAR_QX_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)
 // one 16-k step: split the step's weights (VALU), twelve MFMAs, the small products first
 #define WMAR_QX_MMA(WBUF, XF, C, ST)                                                                   \
     if ((C) * QX_CK + 2 * (ST) < nkb) {                                                                 \
@@ -1379,12 +1317,12 @@ __global__ __launch_bounds__(512) void k_qkvx_bx(QkvxArgs a) {
         bx_split2(WBUF[2 * (ST) + 1].z, WBUF[2 * (ST) + 1].w, h_[3], m_[3], l_[3]);                     \
         const bf16x8 wh = WMAR_QX_BF((u32x4{h_[0], h_[1], h_[2], h_[3]})), wm = WMAR_QX_BF((u32x4{m_[0], m_[1], m_[2], m_[3]})), \
                      wl = WMAR_QX_BF((u32x4{l_[0], l_[1], l_[2], l_[3]}));                              \
-        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_QX_MFMA(wl, WMAR_QX_BF(XF[ST][i][0]), acc[i]); \
-        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_QX_MFMA(wh, WMAR_QX_BF(XF[ST][i][2]), acc[i]); \
-        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_QX_MFMA(wm, WMAR_QX_BF(XF[ST][i][1]), acc[i]); \
-        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_QX_MFMA(wm, WMAR_QX_BF(XF[ST][i][0]), acc[i]); \
-        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_QX_MFMA(wh, WMAR_QX_BF(XF[ST][i][1]), acc[i]); \
-        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_QX_MFMA(wh, WMAR_QX_BF(XF[ST][i][0]), acc[i]); \
+        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_BX_MFMA(wl, WMAR_QX_BF(XF[ST][i][0]), acc[i]); \
+        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_BX_MFMA(wh, WMAR_QX_BF(XF[ST][i][2]), acc[i]); \
+        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_BX_MFMA(wm, WMAR_QX_BF(XF[ST][i][1]), acc[i]); \
+        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_BX_MFMA(wm, WMAR_QX_BF(XF[ST][i][0]), acc[i]); \
+        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_BX_MFMA(wh, WMAR_QX_BF(XF[ST][i][1]), acc[i]); \
+        _Pragma("unroll") for (int i = 0; i < MTW; ++i) WMAR_BX_MFMA(wh, WMAR_QX_BF(XF[ST][i][0]), acc[i]); \
     }
 // one chunk: request the weights three chunks ahead, multiply the first step, pass the chunk barrier and read the next chunk's
 // operands, multiply the second step
@@ -1420,7 +1358,6 @@ __global__ __launch_bounds__(512) void k_qkvx_bx(QkvxArgs a) {
 #undef WMAR_QX_W
 #undef WMAR_QX_READ
 #undef WMAR_QX_MMA
-#undef WMAR_QX_MFMA
 #undef WMAR_QX_BF
 #undef WMAR_QX_STEP
     // One split-K piece per wave, ROW-MAJOR (round 5): piece s is [64 rows][3 D] floats, so the attention workgroup of (sequence,
@@ -1486,8 +1423,6 @@ struct BxArgs {
     int rowmajor;              // (NW == 4, no GELU) slab s as a ROW-MAJOR piece [32 MTW rows][N] instead of the packed layout: what the
     int N;                     // attention prologue reads per (sequence, head) is then contiguous (k_qkvx_bx's epilogue, round 5)
 };
-
-#define WMAR_BX_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)
 
 // NW = waves per workgroup (4; 8 for RAR's FC1, round 5): the waves split the K slice, NW x PER x 16 k per workgroup.  A wave keeps one
 // step in flight beyond the one it computes, so a launch whose steps are bound by the latency of their loads takes PER x that latency:
@@ -1883,30 +1818,15 @@ static int launch_bx_xr(const BxrArgs& q, int N, hipStream_t st) {
 // K/V rows are streamed once per step and the cache (9.7 GB at batch 64) is far larger than the L2s and the memory-side cache: they
 // are loaded NON-TEMPORALLY -- round 4, same-box A/B over the 256-step loop: 4.112 -> 3.98 ms per step (Taming), 3.948 -> 3.899 (RAR-XL):
 // with plain loads 100 MB of K/V per layer swept the slabs, pieces and activations of the neighbouring launches out of the L2s.
-// -DWMAR_ATT_PLAIN_KV restores plain loads.
 // 1-KiB loads of K (and of V) per chunk of k_attn_decode.  Round 5: 2 (8 cached rows of head_dim 64 per chunk, two chunks = 8 KiB in
 // flight per wave) instead of 8.  With 32 KiB in flight per wave the 1536 waves of a 64-row launch had 50 MB queued at the memory
 // system -- four times what 6 TB/s x its latency can use -- so every dependent round of a wave waited ~8 us, some waves far longer
 // (in-loop stamps: streaming phase 9.6 us mean / 14.8 max, last workgroup out 4 us after the mean).  Same-box round-robin A/B over
 // the 256-step loop (scripts/ab_loop.py, 12 runs each): CH 8 / 4 / 3 / 2 / 1 = 3.894 / 3.851 / 3.840 / 3.798 / 3.829 ms per step.
-#ifndef WMAR_ATT_CH
-#define WMAR_ATT_CH 2
-#endif
-#ifndef WMAR_A80_NU
-#define WMAR_A80_NU 2           // k_attn_decode80: 1-KiB main loads of K (and of V) per chunk, 4 cached rows each (round 5: 2 instead of
-                                // 4 -- RAR-XL 4.04 -> 3.98 ms per step, same box; 1: 3.97)
-#endif
-// Order of the first requests of a one-wave workgroup (LATE in k_attn_decode): 0 = first chunk requested together with the prologue's
-// operands (round 4), 1 = both chunks once the operands are here, 2 = first chunk once they are here, the second behind the q / k / v
-// algebra.  At CH 2 the three are within noise (3.798 / 3.814 / 3.798); at CH 8: 3.915 / 3.893 / 3.894.
-#ifndef WMAR_ATT_LATE_KV
-#define WMAR_ATT_LATE_KV 2
-#endif
-#ifndef WMAR_ATT_PLAIN_KV
-#define WMAR_KV_LD(P) ld_nt(P)
-#else
-#define WMAR_KV_LD(P) (*(P))
-#endif
+constexpr int ATT_CH = 2;
+// k_attn_decode80: 1-KiB main loads of K (and of V) per chunk, 4 cached rows each (round 5: 2 instead of 4 -- RAR-XL 4.04 -> 3.98 ms per
+// step, same box; 1: 3.97)
+constexpr int A80_NU = 2;
 // a + b in fp32 and, in err, what that addition rounded away (Knuth's TwoSum: exact for any order of |a|, |b|; no multiplication, so
 // -ffp-contract cannot touch it)
 __device__ __forceinline__ float two_sum(float a, float b, float& err) {
@@ -1944,6 +1864,7 @@ struct AttnArgs {
     double invK;               // 1 / K (host-computed: a double division costs the prologue ~100 cycles)
     const float* c1;           // [3D] row sums of the gamma-folded QKV weights (mode 0)
     const float* bias;         // [3D] bias (+ W beta in mode 0)
+    // rowmajor and mode are what the host dispatches on: the kernels take them as the template parameters RM and MODE and never read them
     int rowmajor;              // the pieces are row-major [rows][3 D] (written by k_qkvx_bx) instead of the packed operand layout
     int mode;                  // 0: minGPT (LN1 folded, finish with LN algebra); 1: RAR (plain bias, then per-head
                                //    LayerNorm of q and k -- Attention.q_norm / k_norm, rar.py:76-94)
@@ -1956,16 +1877,202 @@ struct AttnArgs {
     int D, H, Tmax, MT;
     float scale;
     int dbg;                   // dev builds only (-DWMAR_DEV_KNOBS, WMAR_ATT_DBG): 2 = skip K/V streaming
-    unsigned long long* trace; // dev only (WMAR_ATT_TRACE): 5 timestamps per workgroup
+    unsigned long long* trace; // dev only (WMAR_STAMPS): 8 stamps per workgroup
 };
+
+// ---- The prologue of k_attn_decode and k_attn_decode80: wave 0 of the workgroup of (sequence b, head h) finishes its 3 x hd columns
+// of the QKV projection and appends k and v to the cache.  A head row lies on LPR lanes, of which HD / 4 carry a float4 (lane_on; sub =
+// the lane's float4, 0 on idle lanes); rsel = lane / LPR is the lane's row group, one of RPI = 64 / LPR.  It comes in two parts, so
+// that a kernel can request its first cache chunk in between:
+//   attn_pro_issue   every load of the prologue, into registers;
+//   attn_pro_finish  (wave 0, behind the first chunk's requests) the q / k / v algebra, q | k | v to LDS, k and v to cache row T - 1.
+// MODE (AttnArgs::mode) and RM (AttnArgs::rowmajor) are template parameters (round 5): as run-time branches around the prologue's
+// loads they left merge points behind which hipcc's s_waitcnt pass waited for EVERY outstanding load (vmcnt(0)) -- the cache chunks
+// requested in front of the q / k / v algebra had to land before it could even begin.
+constexpr int attn_pmax(int RPI) { return (QKV_SLABS_MAX + RPI - 1) / RPI; }      // split-K pieces a lane holds (see attn_pro_issue)
+
+// A kernel calls this in front of its first cache chunk.  The prologue's loads go FIRST: loads return in issue order, so behind 16 KiB
+// of cache rows per wave the QKV pieces would arrive only after the chip-wide burst of first chunks has drained (~4 us); ahead of it
+// they are back in ~1.5 us and q, k, v are finished while the first chunk is still in flight.
+// (Measured dead end: clamping the first chunk to the cache's capacity instead of its fill, so that its loads need not wait
+// for the scalar load of the position, saves 1.3 us at 64 rows and costs 3 us below 32 rows -- stale rows are then streamed.)
+template <int HD, int RPI, int MODE, bool RM>
+__device__ __forceinline__ void attn_pro_issue(const AttnArgs& a, const int b, const int h, const int w, const int lane, const int sub,
+                                               const int rsel, double2& st0, float4 (&sl)[3][attn_pmax(RPI)], float4 (&cc)[3],
+                                               float4 (&bb)[3]) {
+    constexpr int PMAX = attn_pmax(RPI);
+    const int Mpad = a.MT * 32;
+    const int mt = b >> 5;
+    // Every load of the prologue is issued here, before the first wait: LN partial sums (one chunk per lane), the QKV pieces, the
+    // folded-LN row sums and the bias.
+    // Every prologue load is UNCONDITIONAL per lane (indices clamped, unused values masked where they are summed): a load under a
+    // per-lane condition (`cond ? load : 0`) compiles to an exec-masked branch whose result is merged right behind it, i.e. one
+    // `s_waitcnt vmcnt(0)` per load -- a dozen serialized L2 round trips instead of one (round 3: the ISA showed exactly that).
+    st0 = make_double2(0.0, 0.0);
+    if (w == 0) st0 = *(const double2*)(a.stats + ((long long)min(lane, a.n_chunks - 1) * Mpad + b) * 2);
+#pragma unroll
+    for (int which = 0; which < 3; ++which) {
+        const int n = which * a.D + h * HD + sub * 4;          // first of this lane's 4 columns
+        // packed operand layout, or row-major pieces [rows][3 D] (k_qkvx_bx, round 5): this lane's float4 of row b
+        const long long idx = RM ? ((long long)b * (3 * a.D) + n) >> 2
+                                 : ((long long)(n >> 3) * a.MT + mt) * 64 + (b & 31) + 32 * ((n >> 2) & 1);
+        if (w == 0) {           // wave-uniform
+            // The S split-K pieces of this head's 3 x hd columns are spread over the wave's RPI row groups (piece p is fetched by
+            // group p % RPI), so that a lane holds at most PMAX pieces: all loads are still in flight together, without 3 x 8
+            // float4 registers per lane (the kernel's occupancy is set by its registers).  The partial sums meet in a fixed
+            // xor-butterfly over the groups (attn_pro_finish): the summation order depends on S only.
+#pragma unroll
+            for (int pi = 0; pi < PMAX; ++pi) {
+                const int pc = min(rsel + pi * RPI, a.S - 1);
+                sl[which][pi] = a.qkv_slabs[(long long)pc * a.slab_stride + idx];
+            }
+            cc[which] = *(const float4*)((MODE == 0 ? a.c1 : a.bias) + n);     // (mode 1 has no c1: any valid address, value unused)
+            bb[which] = *(const float4*)(a.bias + n);
+        }
+    }
+}
+
+// CSUM (mode 1): the pieces of q and k are added with their rounding errors carried along.  k_attn_decode<.., MODE 1> does; head_dim 80
+// keeps the plain fp32 piece sum for q and k as well: RAR-XL's tokens are pinned one by one against the oracle at this width, and its
+// 80-value norm holds the derived distance with the plain sum.
+// Krow / Vrow: this lane's float4 of row 0 of the (sequence, head)'s cache.
+template <int HD, int LPR, int MODE, bool CSUM>
+__device__ __forceinline__ void attn_pro_finish(const AttnArgs& a, const int lane, const int sub, const int rsel, const bool lane_on,
+                                                const int T, const double2 st0, const float4 (&sl)[3][attn_pmax(64 / LPR)],
+                                                const float4 (&cc)[3], const float4 (&bb)[3], float (&qkv_s)[3][HD], float* Krow,
+                                                float* Vrow) {
+    constexpr int RPI = 64 / LPR, PMAX = attn_pmax(RPI);
+    static_assert(!CSUM || MODE == 1, "the compensated q / k piece sum belongs to mode 1");
+    double sm = lane < a.n_chunks ? st0.x : 0.0, sq = lane < a.n_chunks ? st0.y : 0.0;
+    // (n_chunks <= STAT_CHUNKS_MAX = 64: one chunk per lane; a loop over further chunks here would put a load in a loop and make
+    // hipcc wait for ALL outstanding loads, the first cache chunk included)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sm += __shfl_xor(sm, o); sq += __shfl_xor(sq, o); }
+    const double invK = a.invK;
+    const double mean = sm * invK;
+    const float mu = (float)mean;
+    const float rstd = rsqrtf((float)var_f64(sq * invK, mean) + 1e-5f);
+    float4 accs[3], accc[2];     // accc (CSUM): what the additions of the q and k pieces rounded away (csum4_add)
+#pragma unroll
+    for (int which = 0; which < 3; ++which) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (CSUM && which < 2) {
+            // q and k go through a LayerNorm over their head: an element that cancels in the piece sum keeps the roundings of
+            // the partial sums, which the norm then scales by rstd -- several times the element's own ulp.  The pieces are
+            // added with their rounding errors carried along (same order: per row group, then the groups' butterfly).
+            float4 cc4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int pi = 0; pi < PMAX; ++pi)
+                if (rsel + pi * RPI < a.S) csum4_add(acc, cc4, sl[which][pi], zero);
+#pragma unroll
+            for (int o = LPR; o < 64; o <<= 1) {
+                const float4 ps = make_float4(__shfl_xor(acc.x, o), __shfl_xor(acc.y, o), __shfl_xor(acc.z, o), __shfl_xor(acc.w, o));
+                const float4 pc = make_float4(__shfl_xor(cc4.x, o), __shfl_xor(cc4.y, o), __shfl_xor(cc4.z, o), __shfl_xor(cc4.w, o));
+                csum4_add(acc, cc4, ps, pc);
+            }
+            accs[which] = acc; accc[which] = cc4;
+            continue;
+        }
+#pragma unroll
+        for (int pi = 0; pi < PMAX; ++pi)
+            if (rsel + pi * RPI < a.S) {
+                acc.x += sl[which][pi].x; acc.y += sl[which][pi].y;
+                acc.z += sl[which][pi].z; acc.w += sl[which][pi].w;
+            }
+#pragma unroll
+        for (int o = LPR; o < 64; o <<= 1) {
+            acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
+            acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
+        }
+        accs[which] = acc;
+    }
+    if (rsel == 0) {
+        float4 r[3];
+#pragma unroll
+        for (int which = 0; which < 3; ++which) {
+            const float4 acc = accs[which];
+            if (MODE == 0) {
+                r[which] = make_float4(rstd * (acc.x - mu * cc[which].x) + bb[which].x,
+                                       rstd * (acc.y - mu * cc[which].y) + bb[which].y,
+                                       rstd * (acc.z - mu * cc[which].z) + bb[which].z,
+                                       rstd * (acc.w - mu * cc[which].w) + bb[which].w);
+            } else if (CSUM && which < 2) {
+                r[which] = csum4_finish(acc, accc[which], bb[which]);
+            } else {
+                r[which] = make_float4(acc.x + bb[which].x, acc.y + bb[which].y, acc.z + bb[which].z, acc.w + bb[which].w);
+            }
+        }
+        if (MODE == 1) {
+            // q_norm / k_norm: LayerNorm over the hd values of this head (eps 1e-6, affine)
+#pragma unroll
+            for (int which = 0; which < 2; ++which) {
+                float4 v4 = lane_on ? r[which] : make_float4(0.f, 0.f, 0.f, 0.f);
+                float sm1 = v4.x + v4.y + v4.z + v4.w;
+#pragma unroll
+                for (int o = 1; o < LPR; o <<= 1) sm1 += __shfl_xor(sm1, o);
+                const float mean = sm1 * (1.0f / HD);
+                float4 dv = make_float4(v4.x - mean, v4.y - mean, v4.z - mean, v4.w - mean);
+                float sq1 = lane_on ? dv.x * dv.x + dv.y * dv.y + dv.z * dv.z + dv.w * dv.w : 0.f;
+#pragma unroll
+                for (int o = 1; o < LPR; o <<= 1) sq1 += __shfl_xor(sq1, o);
+                const float rs = rsqrtf(sq1 * (1.0f / HD) + 1e-6f);
+                const float4 gw = *(const float4*)((which == 0 ? a.qn_w : a.kn_w) + sub * 4);
+                const float4 gb = *(const float4*)((which == 0 ? a.qn_b : a.kn_b) + sub * 4);
+                r[which] = make_float4(dv.x * rs * gw.x + gb.x, dv.y * rs * gw.y + gb.y, dv.z * rs * gw.z + gb.z,
+                                       dv.w * rs * gw.w + gb.w);
+            }
+        }
+        if (lane_on) {
+#pragma unroll
+            for (int which = 0; which < 3; ++which) *(float4*)(&qkv_s[which][sub * 4]) = r[which];
+            // present = (k, v) of this step -> cache row T-1 (mingpt.py:77 / rar.py:96-107)
+            *(float4*)(Krow + (long long)(T - 1) * HD) = r[1];
+            *(float4*)(Vrow + (long long)(T - 1) * HD) = r[2];
+        }
+    }
+}
+
+// One wave per workgroup: the hand-over of q / k / v (and of the partial results) through LDS needs no s_barrier -- and hipcc's
+// __syncthreads() drains EVERY outstanding load first (s_waitcnt vmcnt(0)): the cache chunks requested above would have to land before
+// the streaming loop may even start (stamps: "finish q/k/v" 6.6 us with two chunks in flight).  LDS operations of one wave execute in order.
+template <int NWA>
+__device__ __forceinline__ void attn_wg_sync() { if (NWA > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier(); }
+
+// The NWA partial results (part[w]: weighted V sum [HD], running max, sum) meet in LDS; the lanes `on` of wave 0 -- lane sub owns floats
+// 4 sub .. + 3 of the head's row -- rescale them to the common max and store y[b][h * HD + 4 sub .. + 3].
+template <int HD, int NWA>
+__device__ __forceinline__ void attn_merge_store(const AttnArgs& a, const float (&part)[NWA][HD + 4], const int b, const int h, const int w,
+                                                 const int sub, const bool on) {
+    attn_wg_sync<NWA>();
+    if (w == 0 && on) {
+        float M = part[0][HD];
+#pragma unroll
+        for (int i = 1; i < NWA; ++i) M = fmaxf(M, part[i][HD]);
+        float L = 0.f;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int i = 0; i < NWA; ++i) {
+            const float f = __expf(part[i][HD] - M);   // waves without rows: exp(-inf) = 0
+            const float4 pa = *(const float4*)(&part[i][sub * 4]);
+            L += part[i][HD + 1] * f;
+            o.x += pa.x * f; o.y += pa.y * f; o.z += pa.z * f; o.w += pa.w * f;
+        }
+        const float inv = 1.0f / L;
+        // into the packed activation layout, or as bf16 pieces
+        const int k = h * HD + sub * 4;
+        const int kb = k >> 3, hf = (k >> 2) & 1;
+        const int mt = b >> 5;
+        const float4 yv = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);
+        if (a.yq) bx_store_planes4(a.yq, a.MT, kb, hf, mt, b & 31, yv);
+        else a.y[((long long)kb * a.MT + mt) * 64 + (b & 31) + 32 * hf] = yv;
+    }
+}
 
 // One workgroup of NWA waves per (sequence, head).  The cached rows are cut into chunks of
 // CH 1-KiB loads (CH*RPI rows); wave w takes chunks w, w+NWA, ...  and keeps a running
 // (max, sum, weighted V sum) in registers -- K and V of a chunk are requested together, the next
 // chunk is in flight while the current one is reduced.  The NWA partial results meet in LDS.
-// MODE (AttnArgs::mode) and RM (AttnArgs::rowmajor) are template parameters (round 5): as run-time branches around the prologue's
-// loads they left merge points behind which hipcc's s_waitcnt pass waited for EVERY outstanding load (vmcnt(0)) -- the cache chunks
-// requested in front of the q / k / v algebra had to land before it could even begin.
 template <int HD, int NWA, int MODE = 0, bool RM = false>
 __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
     // LPRA lanes (one float4 each) cover a cache row; rows are laid on LPR = next power of two lanes so
@@ -1973,7 +2080,7 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
     constexpr int LPRA = HD / 4;
     constexpr int LPR = LPRA <= 8 ? 8 : (LPRA <= 16 ? 16 : 32);
     constexpr int RPI = 64 / LPR;
-    constexpr int CH = WMAR_ATT_CH;
+    constexpr int CH = ATT_CH;
     constexpr int ROWS = CH * RPI;
     static_assert(HD % 4 == 0 && LPRA <= 32, "head_dim must be a multiple of 4, at most 128");
     __shared__ __attribute__((aligned(16))) float part[NWA][HD + 4];    // per wave: weighted V sum [HD], max, sum (16-B rows)
@@ -1997,179 +2104,32 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
 #define WMAR_ATT_LOAD(KB, VB, C0)                                                        \
     _Pragma("unroll") for (int u = 0; u < CH; ++u) {                                     \
         const int t = min((C0) * ROWS + u * RPI + rsel, T - 1);                          \
-        KB[u] = WMAR_KV_LD((const float4*)(Kc + (long long)t * HD));                     \
-        VB[u] = WMAR_KV_LD((const float4*)(Vc + (long long)t * HD));                     \
+        KB[u] = ld_nt((const float4*)(Kc + (long long)t * HD));                          \
+        VB[u] = ld_nt((const float4*)(Vc + (long long)t * HD));                          \
     }
     float4 kA[CH], vA[CH], kB[CH], vB[CH];
     float4 q, knew, vnew;
     WMAR_ST_BEGIN
-#ifdef WMAR_ATT_TRACE
-    unsigned long long tr[5];
-    tr[0] = __builtin_amdgcn_s_memtime();
-#endif
-    // (Measured dead end: clamping the first chunk to the cache's capacity instead of its fill, so that its loads need not wait
-    // for the scalar load of the position, saves 1.3 us at 64 rows and costs 3 us below 32 rows -- stale rows are then streamed.)
-    // The prologue's loads go FIRST: loads return in issue order, so behind 16 KiB of cache rows per wave the QKV pieces would
-    // arrive only after the chip-wide burst of first chunks has drained (~4 us); ahead of it they are back in ~1.5 us and q, k, v
-    // are finished while the first chunk is still in flight.
-    // every load of the prologue is issued before the first wait: LN partial sums (one chunk per
-    // lane), the QKV slab(s), the folded-LN row sums and the bias (16 lanes each)
-    const int Mpad = a.MT * 32;
-    const int mt = b >> 5;
-    double sm = 0, sq = 0;
-    // Every prologue load is UNCONDITIONAL per lane (indices clamped, unused values masked where they are summed): a load under a
-    // per-lane condition (`cond ? load : 0`) compiles to an exec-masked branch whose result is merged right behind it, i.e. one
-    // `s_waitcnt vmcnt(0)` per load -- a dozen serialized L2 round trips instead of one (round 3: the ISA showed exactly that).
-    double2 st0 = make_double2(0.0, 0.0);
-    if (w == 0) st0 = *(const double2*)(a.stats + ((long long)min(lane, a.n_chunks - 1) * Mpad + b) * 2);
-    // The S split-K pieces of this head's 3 x hd columns are spread over the wave's RPI row groups (piece p is fetched by
-    // group p % RPI), so that a lane holds at most PMAX pieces: all loads are still in flight together, without 3 x 8
-    // float4 registers per lane (the kernel's occupancy is set by its registers).  The partial sums meet in a fixed
-    // xor-butterfly over the groups: the summation order depends on S only.
-    constexpr int PMAX = (QKV_SLABS_MAX + RPI - 1) / RPI;
-    float4 sl[3][PMAX], cc[3], bb[3];
-#pragma unroll
-    for (int which = 0; which < 3; ++which) {
-        const int n = which * a.D + h * HD + sub * 4;          // first of this lane's 4 columns
-        // packed operand layout, or row-major pieces [rows][3 D] (k_qkvx_bx, round 5): this lane's float4 of row b
-        const long long idx = RM ? ((long long)b * (3 * a.D) + n) >> 2
-                                         : ((long long)(n >> 3) * a.MT + mt) * 64 + (b & 31) + 32 * ((n >> 2) & 1);
-        if (w == 0) {           // wave-uniform
-#pragma unroll
-            for (int pi = 0; pi < PMAX; ++pi) {
-                const int pc = min(rsel + pi * RPI, a.S - 1);
-                sl[which][pi] = a.qkv_slabs[(long long)pc * a.slab_stride + idx];
-            }
-            cc[which] = *(const float4*)((MODE == 0 ? a.c1 : a.bias) + n);     // (mode 1 has no c1: any valid address, value unused)
-            bb[which] = *(const float4*)(a.bias + n);
-        }
-    }
+    double2 st0;
+    float4 sl[3][attn_pmax(RPI)], cc[3], bb[3];
+    attn_pro_issue<HD, RPI, MODE, RM>(a, b, h, w, lane, sub, rsel, st0, sl, cc, bb);
     __builtin_amdgcn_sched_barrier(0);
-    // LATE (round 5, one wave per (sequence, head)): the cache chunks are requested only once the prologue's operands are HERE.
+    // One wave per (sequence, head) (round 5): the cache chunks are requested only once the prologue's operands are HERE.
     // In-loop stamps (profiles/r05_stamp_table_*): with the first chunk requested up front, the six waves of a CU queued 96 KiB of K/V
     // in front of each other's 5 KiB of prologue operands -- they landed 4.2 us after entry on average, 12.3 at worst, and the
     // late waves were the launch's stragglers (last workgroup out 4.2 us after the mean).  Now every wave gets its operands at
-    // L2 latency, requests TWO chunks, and finishes q / k / v while they fly.
-    constexpr bool LATE = WMAR_ATT_LATE_KV && NWA == 1;
-    constexpr bool LATE2 = LATE && WMAR_ATT_LATE_KV == 1;      // both chunks in front of the q / k / v algebra (2: the second one behind it)
-    if (LATE) {
+    // L2 latency, requests the first chunk, finishes q / k / v while it flies and requests the second behind that algebra.
+    // (Measured, the order of these first requests: first chunk together with the prologue's operands / both chunks once the operands
+    // are here / this one -- 3.798 / 3.814 / 3.798 ms per step; with 32-row chunks 3.915 / 3.893 / 3.894.)
+    if (NWA == 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef WMAR_STAMPS
-        st_[2] = __builtin_amdgcn_s_memtime();
-#endif
+        WMAR_ST(2)
     }
     WMAR_ATT_LOAD(kA, vA, w)                    // unconditional (clamped rows): see the refills below
-    if (LATE2) { WMAR_ATT_LOAD(kB, vB, w + NWA) }
     __builtin_amdgcn_sched_barrier(0);
-    if (w == 0) {
-#ifdef WMAR_STAMPS
-        if (!LATE) {
-            // (the prologue's operands only: the cache chunk behind them stays in flight -- 16 K/V loads were issued after them)
-            asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            st_[2] = __builtin_amdgcn_s_memtime();
-        }
-#endif
-#ifdef WMAR_ATT_TRACE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tr[1] = __builtin_amdgcn_s_memtime();
-#endif
-        sm = lane < a.n_chunks ? st0.x : 0.0; sq = lane < a.n_chunks ? st0.y : 0.0;
-        // (n_chunks <= STAT_CHUNKS_MAX = 64: one chunk per lane; a loop over further chunks here would put a load in a loop and make
-        // hipcc wait for ALL outstanding loads, the first cache chunk included)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { sm += __shfl_xor(sm, o); sq += __shfl_xor(sq, o); }
-        const double invK = a.invK;
-        const double mean = sm * invK;
-        const float mu = (float)mean;
-        const float rstd = rsqrtf((float)var_f64(sq * invK, mean) + 1e-5f);
-        float4 accs[3], accc[2];     // accc (mode 1): what the additions of the q and k pieces rounded away (csum4_add)
-#pragma unroll
-        for (int which = 0; which < 3; ++which) {
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (MODE == 1 && which < 2) {
-                // q and k go through a LayerNorm over their head: an element that cancels in the piece sum keeps the roundings of
-                // the partial sums, which the norm then scales by rstd -- several times the element's own ulp.  The pieces are
-                // added with their rounding errors carried along (same order: per row group, then the groups' butterfly).
-                float4 cc4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int pi = 0; pi < PMAX; ++pi)
-                    if (rsel + pi * RPI < a.S) csum4_add(acc, cc4, sl[which][pi], zero);
-#pragma unroll
-                for (int o = LPR; o < 64; o <<= 1) {
-                    const float4 ps = make_float4(__shfl_xor(acc.x, o), __shfl_xor(acc.y, o), __shfl_xor(acc.z, o), __shfl_xor(acc.w, o));
-                    const float4 pc = make_float4(__shfl_xor(cc4.x, o), __shfl_xor(cc4.y, o), __shfl_xor(cc4.z, o), __shfl_xor(cc4.w, o));
-                    csum4_add(acc, cc4, ps, pc);
-                }
-                accs[which] = acc; accc[which] = cc4;
-                continue;
-            }
-#pragma unroll
-            for (int pi = 0; pi < PMAX; ++pi)
-                if (rsel + pi * RPI < a.S) {
-                    acc.x += sl[which][pi].x; acc.y += sl[which][pi].y;
-                    acc.z += sl[which][pi].z; acc.w += sl[which][pi].w;
-                }
-#pragma unroll
-            for (int o = LPR; o < 64; o <<= 1) {
-                acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
-                acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
-            }
-            accs[which] = acc;
-        }
-        if (rsel == 0) {
-            float4 r[3];
-#pragma unroll
-            for (int which = 0; which < 3; ++which) {
-                const float4 acc = accs[which];
-                if (MODE == 0) {
-                    r[which] = make_float4(rstd * (acc.x - mu * cc[which].x) + bb[which].x,
-                                           rstd * (acc.y - mu * cc[which].y) + bb[which].y,
-                                           rstd * (acc.z - mu * cc[which].z) + bb[which].z,
-                                           rstd * (acc.w - mu * cc[which].w) + bb[which].w);
-                } else if (which < 2) {
-                    r[which] = csum4_finish(acc, accc[which], bb[which]);
-                } else {
-                    r[which] = make_float4(acc.x + bb[which].x, acc.y + bb[which].y, acc.z + bb[which].z, acc.w + bb[which].w);
-                }
-            }
-            if (MODE == 1) {
-                // q_norm / k_norm: LayerNorm over the hd values of this head (eps 1e-6, affine)
-#pragma unroll
-                for (int which = 0; which < 2; ++which) {
-                    float4 v4 = lane_on ? r[which] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    float sm1 = v4.x + v4.y + v4.z + v4.w;
-#pragma unroll
-                    for (int o = 1; o < LPR; o <<= 1) sm1 += __shfl_xor(sm1, o);
-                    const float mean = sm1 * (1.0f / HD);
-                    float4 dv = make_float4(v4.x - mean, v4.y - mean, v4.z - mean, v4.w - mean);
-                    float sq1 = lane_on ? dv.x * dv.x + dv.y * dv.y + dv.z * dv.z + dv.w * dv.w : 0.f;
-#pragma unroll
-                    for (int o = 1; o < LPR; o <<= 1) sq1 += __shfl_xor(sq1, o);
-                    const float rs = rsqrtf(sq1 * (1.0f / HD) + 1e-6f);
-                    const float4 gw = *(const float4*)((which == 0 ? a.qn_w : a.kn_w) + sub * 4);
-                    const float4 gb = *(const float4*)((which == 0 ? a.qn_b : a.kn_b) + sub * 4);
-                    r[which] = make_float4(dv.x * rs * gw.x + gb.x, dv.y * rs * gw.y + gb.y, dv.z * rs * gw.z + gb.z,
-                                           dv.w * rs * gw.w + gb.w);
-                }
-            }
-            if (lane_on) {
-#pragma unroll
-                for (int which = 0; which < 3; ++which) *(float4*)(&qkv_s[which][sub * 4]) = r[which];
-                // present = (k, v) of this step -> cache row T-1 (mingpt.py:77 / rar.py:96-107)
-                *(float4*)(Kc + (long long)(T - 1) * HD) = r[1];
-                *(float4*)(Vc + (long long)(T - 1) * HD) = r[2];
-            }
-        }
-    }
-    // One wave per workgroup: the hand-over of q / k / v through LDS needs no s_barrier -- and hipcc's __syncthreads() drains EVERY
-    // outstanding load first (s_waitcnt vmcnt(0)): the cache chunks requested above would have to land before the streaming loop may
-    // even start (stamps: "finish q/k/v" 6.6 us with two chunks in flight).  LDS operations of one wave execute in order.
-    if (NWA > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
+    if (w == 0) attn_pro_finish<HD, LPR, MODE, MODE == 1>(a, lane, sub, rsel, lane_on, T, st0, sl, cc, bb, qkv_s, Kc, Vc);
+    attn_wg_sync<NWA>();
     WMAR_ST(6)
-#ifdef WMAR_ATT_TRACE
-    tr[2] = __builtin_amdgcn_s_memtime();
-#endif
     q = lane_on ? *(const float4*)(&qkv_s[0][sub * 4]) : make_float4(0.f, 0.f, 0.f, 0.f);
     knew = *(const float4*)(&qkv_s[1][sub * 4]);
     vnew = *(const float4*)(&qkv_s[2][sub * 4]);
@@ -2204,7 +2164,7 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
     // The refills inside the loop are UNCONDITIONAL (rows past the cache clamp to row T-1: L1 hits): a load under a run-time branch
     // makes hipcc's s_waitcnt pass take the smaller outstanding count of the two paths at the merge, i.e. every use of chunk c
     // then waits for chunk c+1's loads as well and the double buffer degenerates to one chunk in flight.
-    if (!LATE2) { WMAR_ATT_LOAD(kB, vB, w + NWA) }
+    WMAR_ATT_LOAD(kB, vB, w + NWA)
     __builtin_amdgcn_sched_barrier(0);
     for (int c = w; c < nchunk; c += 2 * NWA) {
         WMAR_ATT_CHUNK(kA, vA, c)
@@ -2219,9 +2179,6 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
 #undef WMAR_ATT_LOAD
 #undef WMAR_ATT_CHUNK
     WMAR_ST(3)
-#ifdef WMAR_ATT_TRACE
-    tr[3] = __builtin_amdgcn_s_memtime();
-#endif
     // fold the RPI row groups of this wave (l and acc are per-lane partials over the lane's rows)
 #pragma unroll
     for (int o = LPR; o < 64; o <<= 1) {
@@ -2233,37 +2190,8 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
         *(float4*)(&part[w][sub * 4]) = acc;
         if (sub == 0) { part[w][HD] = m; part[w][HD + 1] = l; }
     }
-    if (NWA > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
-    if (w == 0 && rsel == 0 && lane_on) {
-        float M = part[0][HD];
-#pragma unroll
-        for (int i = 1; i < NWA; ++i) M = fmaxf(M, part[i][HD]);
-        float L = 0.f;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < NWA; ++i) {
-            const float f = __expf(part[i][HD] - M);   // waves without rows: exp(-inf) = 0
-            const float4 pa = *(const float4*)(&part[i][sub * 4]);
-            L += part[i][HD + 1] * f;
-            o.x += pa.x * f; o.y += pa.y * f; o.z += pa.z * f; o.w += pa.w * f;
-        }
-        const float inv = 1.0f / L;
-        // y[b][h*HD + sub*4 .. +3] into the packed activation layout
-        const int k = h * HD + sub * 4;
-        const int kb = k >> 3, hf = (k >> 2) & 1;
-        const int mt = b >> 5;
-        const float4 yv = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);
-        if (a.yq) bx_store_planes4(a.yq, a.MT, kb, hf, mt, b & 31, yv);
-        else a.y[((long long)kb * a.MT + mt) * 64 + (b & 31) + 32 * hf] = yv;
-    }
+    attn_merge_store<HD, NWA>(a, part, b, h, w, sub, rsel == 0 && lane_on);
     WMAR_ST_END(a.trace, blockIdx.x)
-#ifdef WMAR_ATT_TRACE
-    if (a.trace && threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tr[4] = __builtin_amdgcn_s_memtime();
-        for (int i = 0; i < 5; ++i) a.trace[(long long)blockIdx.x * 5 + i] = tr[i];
-    }
-#endif
 }
 
 // ------------------------------------------------- decode attention at head_dim 80 (RAR-XL), every lane busy (round 4)
@@ -2275,17 +2203,17 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode(AttnArgs a) {
 // 4 ((lane / 4) % 4) + lane / 16 in lane quad lane / 4 -- i.e. a tail lane's row is the row of ITS OWN lane group for u = (lane / 4) % 4,
 // so it picks the main partial score out of its own registers (3 selects, no cross-lane traffic), and a main lane fetches the tail
 // partial of row (u, g) from lane 16 g + 4 u of its own 16-lane row (one __shfl per main load).  The prologue (QKV pieces, bias,
-// q / k LayerNorm over the 80 values, cache append) is k_attn_decode's.
-template <int NWA, int MODE = 1>     // MODE: AttnArgs::mode at compile time (see k_attn_decode); RAR is the only head_dim-80 user
-__global__ __launch_bounds__(NWA * 64) void k_attn_decode80(AttnArgs a) {
+// q / k LayerNorm over the 80 values, cache append) and the final store are k_attn_decode's, in mode 1 with the plain piece sum.
+// One wave per (sequence, head): RAR, the only head_dim-80 user, runs nothing else (RarPlan::attn_waves).
+template <bool RM>
+__global__ __launch_bounds__(64) void k_attn_decode80(AttnArgs a) {
     // NU main loads per chunk (4 rows each): chunks of 4 NU rows.  The tail load always spans 16 rows' worth of lanes; with NU < 4 the
     // lane quads of the rows past the chunk re-read a clamped row and contribute nothing (their weight is 0).
-    constexpr int HD = 80, LPRA = 20, LPR = 32, RPI = 2, NU = WMAR_A80_NU, ROWS = 4 * NU;
-    __shared__ __attribute__((aligned(16))) float part[NWA][HD + 4];
+    constexpr int HD = 80, LPRA = 20, LPR = 32, RPI = 2, NU = A80_NU, ROWS = 4 * NU;
+    __shared__ __attribute__((aligned(16))) float part[1][HD + 4];
     __shared__ __attribute__((aligned(16))) float qkv_s[3][HD];
     const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
     const int lane = threadIdx.x & 63;
-    const int w = NWA == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int T = *a.pos_dev + 1;
     // prologue roles (k_attn_decode's layout: 32 lanes per row, 20 active)
     const int subr = lane % LPR, rsel = lane / LPR;
@@ -2305,126 +2233,21 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode80(AttnArgs a) {
 #define WMAR_A80_LOAD(KM, KT, VM, VT, C0)                                                \
     _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                     \
         const int t = min((C0) * ROWS + 4 * u + g16, T - 1);                             \
-        KM[u] = WMAR_KV_LD((const float4*)(Kmain + (long long)t * HD));                  \
-        VM[u] = WMAR_KV_LD((const float4*)(Vmain + (long long)t * HD));                  \
+        KM[u] = ld_nt((const float4*)(Kmain + (long long)t * HD));                       \
+        VM[u] = ld_nt((const float4*)(Vmain + (long long)t * HD));                       \
     }                                                                                    \
     { const int t = min((C0) * ROWS + 4 * min(ut, NU - 1) + g16, T - 1);                 \
-      KT = WMAR_KV_LD((const float4*)(Ktail + (long long)t * HD));                       \
-      VT = WMAR_KV_LD((const float4*)(Vtail + (long long)t * HD)); }
+      KT = ld_nt((const float4*)(Ktail + (long long)t * HD));                            \
+      VT = ld_nt((const float4*)(Vtail + (long long)t * HD)); }
     float4 kmA[NU], vmA[NU], ktA, vtA, kmB[NU], vmB[NU], ktB, vtB;
-    // (Measured dead end: clamping the first chunk to the cache's capacity instead of its fill, so that its loads need not wait
-    // for the scalar load of the position, saves 1.3 us at 64 rows and costs 3 us below 32 rows -- stale rows are then streamed.)
-    // The prologue's loads go FIRST: loads return in issue order, so behind 16 KiB of cache rows per wave the QKV pieces would
-    // arrive only after the chip-wide burst of first chunks has drained (~4 us); ahead of it they are back in ~1.5 us and q, k, v
-    // are finished while the first chunk is still in flight.
-    // every load of the prologue is issued before the first wait: LN partial sums (one chunk per
-    // lane), the QKV slab(s), the folded-LN row sums and the bias (16 lanes each)
-    const int Mpad = a.MT * 32;
-    const int mt = b >> 5;
-    double sm = 0, sq = 0;
-    // Every prologue load is UNCONDITIONAL per lane (indices clamped, unused values masked where they are summed): a load under a
-    // per-lane condition (`cond ? load : 0`) compiles to an exec-masked branch whose result is merged right behind it, i.e. one
-    // `s_waitcnt vmcnt(0)` per load -- a dozen serialized L2 round trips instead of one (round 3: the ISA showed exactly that).
-    double2 st0 = make_double2(0.0, 0.0);
-    if (w == 0) st0 = *(const double2*)(a.stats + ((long long)min(lane, a.n_chunks - 1) * Mpad + b) * 2);
-    // The S split-K pieces of this head's 3 x hd columns are spread over the wave's RPI row groups (piece p is fetched by
-    // group p % RPI), so that a lane holds at most PMAX pieces: all loads are still in flight together, without 3 x 8
-    // float4 registers per lane (the kernel's occupancy is set by its registers).  The partial sums meet in a fixed
-    // xor-butterfly over the groups: the summation order depends on S only.
-    constexpr int PMAX = (QKV_SLABS_MAX + RPI - 1) / RPI;
-    float4 sl[3][PMAX], cc[3], bb[3];
-#pragma unroll
-    for (int which = 0; which < 3; ++which) {
-        const int n = which * a.D + h * HD + sub * 4;          // first of this lane's 4 columns
-        // packed operand layout, or row-major pieces [rows][3 D] (k_qkvx_bx, round 5): this lane's float4 of row b
-        const long long idx = a.rowmajor ? ((long long)b * (3 * a.D) + n) >> 2
-                                         : ((long long)(n >> 3) * a.MT + mt) * 64 + (b & 31) + 32 * ((n >> 2) & 1);
-        if (w == 0) {           // wave-uniform
-#pragma unroll
-            for (int pi = 0; pi < PMAX; ++pi) {
-                const int pc = min(rsel + pi * RPI, a.S - 1);
-                sl[which][pi] = a.qkv_slabs[(long long)pc * a.slab_stride + idx];
-            }
-            cc[which] = *(const float4*)((MODE == 0 ? a.c1 : a.bias) + n);     // (mode 1 has no c1: any valid address, value unused)
-            bb[which] = *(const float4*)(a.bias + n);
-        }
-    }
+    double2 st0;
+    float4 sl[3][attn_pmax(RPI)], cc[3], bb[3];
+    attn_pro_issue<HD, RPI, 1, RM>(a, b, h, 0, lane, sub, rsel, st0, sl, cc, bb);
     __builtin_amdgcn_sched_barrier(0);
-    WMAR_A80_LOAD(kmA, ktA, vmA, vtA, w)
+    WMAR_A80_LOAD(kmA, ktA, vmA, vtA, 0)
     __builtin_amdgcn_sched_barrier(0);
-    if (w == 0) {
-        sm = lane < a.n_chunks ? st0.x : 0.0; sq = lane < a.n_chunks ? st0.y : 0.0;
-        // (n_chunks <= STAT_CHUNKS_MAX = 64: one chunk per lane; a loop over further chunks here would put a load in a loop and make
-        // hipcc wait for ALL outstanding loads, the first cache chunk included)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { sm += __shfl_xor(sm, o); sq += __shfl_xor(sq, o); }
-        const double invK = a.invK;
-        const double mean = sm * invK;
-        const float mu = (float)mean;
-        const float rstd = rsqrtf((float)var_f64(sq * invK, mean) + 1e-5f);
-        // (the plain fp32 piece sum for q and k as well, unlike k_attn_decode<.., MODE 1>: RAR-XL's tokens are pinned one by one against
-        // the oracle at this width, and its 80-value norm holds the derived distance with the plain sum)
-        float4 accs[3];
-#pragma unroll
-        for (int which = 0; which < 3; ++which) {
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int pi = 0; pi < PMAX; ++pi)
-                if (rsel + pi * RPI < a.S) {
-                    acc.x += sl[which][pi].x; acc.y += sl[which][pi].y;
-                    acc.z += sl[which][pi].z; acc.w += sl[which][pi].w;
-                }
-#pragma unroll
-            for (int o = LPR; o < 64; o <<= 1) {
-                acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
-                acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
-            }
-            accs[which] = acc;
-        }
-        if (rsel == 0) {
-            float4 r[3];
-#pragma unroll
-            for (int which = 0; which < 3; ++which) {
-                const float4 acc = accs[which];
-                if (MODE == 0) {
-                    r[which] = make_float4(rstd * (acc.x - mu * cc[which].x) + bb[which].x,
-                                           rstd * (acc.y - mu * cc[which].y) + bb[which].y,
-                                           rstd * (acc.z - mu * cc[which].z) + bb[which].z,
-                                           rstd * (acc.w - mu * cc[which].w) + bb[which].w);
-                } else {
-                    r[which] = make_float4(acc.x + bb[which].x, acc.y + bb[which].y, acc.z + bb[which].z, acc.w + bb[which].w);
-                }
-            }
-            if (MODE == 1) {
-                // q_norm / k_norm: LayerNorm over the hd values of this head (eps 1e-6, affine)
-#pragma unroll
-                for (int which = 0; which < 2; ++which) {
-                    float4 v4 = lane_on ? r[which] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    float sm1 = v4.x + v4.y + v4.z + v4.w;
-#pragma unroll
-                    for (int o = 1; o < LPR; o <<= 1) sm1 += __shfl_xor(sm1, o);
-                    const float mean = sm1 * (1.0f / HD);
-                    float4 dv = make_float4(v4.x - mean, v4.y - mean, v4.z - mean, v4.w - mean);
-                    float sq1 = lane_on ? dv.x * dv.x + dv.y * dv.y + dv.z * dv.z + dv.w * dv.w : 0.f;
-#pragma unroll
-                    for (int o = 1; o < LPR; o <<= 1) sq1 += __shfl_xor(sq1, o);
-                    const float rs = rsqrtf(sq1 * (1.0f / HD) + 1e-6f);
-                    const float4 gw = *(const float4*)((which == 0 ? a.qn_w : a.kn_w) + sub * 4);
-                    const float4 gb = *(const float4*)((which == 0 ? a.qn_b : a.kn_b) + sub * 4);
-                    r[which] = make_float4(dv.x * rs * gw.x + gb.x, dv.y * rs * gw.y + gb.y, dv.z * rs * gw.z + gb.z,
-                                           dv.w * rs * gw.w + gb.w);
-                }
-            }
-            if (lane_on) {
-#pragma unroll
-                for (int which = 0; which < 3; ++which) *(float4*)(&qkv_s[which][sub * 4]) = r[which];
-                // present = (k, v) of this step -> cache row T-1 (mingpt.py:77 / rar.py:96-107)
-                *(float4*)(Kc + (long long)(T - 1) * HD + sub * 4) = r[1];
-                *(float4*)(Vc + (long long)(T - 1) * HD + sub * 4) = r[2];
-            }
-        }
-    }
-    if (NWA > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();     // one wave: no s_barrier, no vmcnt(0) drain (k_attn_decode)
+    attn_pro_finish<HD, LPR, 1, false>(a, lane, sub, rsel, lane_on, T, st0, sl, cc, bb, qkv_s, Kc + sub * 4, Vc + sub * 4);
+    attn_wg_sync<1>();
     const float4 qM = *(const float4*)(&qkv_s[0][m16 * 4]), qT = *(const float4*)(&qkv_s[0][64 + t4 * 4]);
     const float4 knM = *(const float4*)(&qkv_s[1][m16 * 4]), knT = *(const float4*)(&qkv_s[1][64 + t4 * 4]);
     const float4 vnM = *(const float4*)(&qkv_s[2][m16 * 4]), vnT = *(const float4*)(&qkv_s[2][64 + t4 * 4]);
@@ -2468,16 +2291,16 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode80(AttnArgs a) {
         m = mn;                                                                          \
     }
     // refills are UNCONDITIONAL (clamped rows): see k_attn_decode
-    WMAR_A80_LOAD(kmB, ktB, vmB, vtB, w + NWA)
+    WMAR_A80_LOAD(kmB, ktB, vmB, vtB, 1)
     __builtin_amdgcn_sched_barrier(0);
-    for (int c = w; c < nchunk; c += 2 * NWA) {
+    for (int c = 0; c < nchunk; c += 2) {
         WMAR_A80_CHUNK(kmA, ktA, vmA, vtA, c)
         __builtin_amdgcn_sched_barrier(0);
-        WMAR_A80_LOAD(kmA, ktA, vmA, vtA, c + 2 * NWA)
+        WMAR_A80_LOAD(kmA, ktA, vmA, vtA, c + 2)
         __builtin_amdgcn_sched_barrier(0);
-        if (c + NWA < nchunk) { WMAR_A80_CHUNK(kmB, ktB, vmB, vtB, c + NWA) }
+        if (c + 1 < nchunk) { WMAR_A80_CHUNK(kmB, ktB, vmB, vtB, c + 1) }
         __builtin_amdgcn_sched_barrier(0);
-        WMAR_A80_LOAD(kmB, ktB, vmB, vtB, c + 3 * NWA)
+        WMAR_A80_LOAD(kmB, ktB, vmB, vtB, c + 3)
         __builtin_amdgcn_sched_barrier(0);
     }
 #undef WMAR_A80_LOAD
@@ -2492,31 +2315,10 @@ __global__ __launch_bounds__(NWA * 64) void k_attn_decode80(AttnArgs a) {
     for (int o = 4; o < 64; o <<= 1) {
         accT.x += __shfl_xor(accT.x, o); accT.y += __shfl_xor(accT.y, o); accT.z += __shfl_xor(accT.z, o); accT.w += __shfl_xor(accT.w, o);
     }
-    if (lane < 16) *(float4*)(&part[w][lane * 4]) = accM;
-    if (lane < 4) *(float4*)(&part[w][64 + lane * 4]) = accT;
-    if (lane == 0) { part[w][HD] = m; part[w][HD + 1] = l; }
-    if (NWA > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();     // one wave: no s_barrier, no vmcnt(0) drain (k_attn_decode)
-    if (w == 0 && lane < LPRA) {
-        float M = part[0][HD];
-#pragma unroll
-        for (int i = 1; i < NWA; ++i) M = fmaxf(M, part[i][HD]);
-        float L = 0.f;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < NWA; ++i) {
-            const float f = __expf(part[i][HD] - M);   // waves without rows: exp(-inf) = 0
-            const float4 pa = *(const float4*)(&part[i][lane * 4]);
-            L += part[i][HD + 1] * f;
-            o.x += pa.x * f; o.y += pa.y * f; o.z += pa.z * f; o.w += pa.w * f;
-        }
-        const float inv = 1.0f / L;
-        const int k = h * HD + lane * 4;
-        const int kb = k >> 3, hf = (k >> 2) & 1;
-        const int mt = b >> 5;
-        const float4 yv = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);
-        if (a.yq) bx_store_planes4(a.yq, a.MT, kb, hf, mt, b & 31, yv);
-        else a.y[((long long)kb * a.MT + mt) * 64 + (b & 31) + 32 * hf] = yv;
-    }
+    if (lane < 16) *(float4*)(&part[0][lane * 4]) = accM;
+    if (lane < 4) *(float4*)(&part[0][64 + lane * 4]) = accT;
+    if (lane == 0) { part[0][HD] = m; part[0][HD + 1] = l; }
+    attn_merge_store<HD, 1>(a, part, b, h, 0, lane, lane < LPRA);
 }
 
 }  // namespace wmar

@@ -1148,9 +1148,7 @@ int wmar_gpt_get_timing(wmar_gpt* g, double* total_us, int64_t* calls, double* s
     return WMAR_OK;
 }
 
-#ifndef WMAR_GRAPH_STEPS_DEFAULT
-#define WMAR_GRAPH_STEPS_DEFAULT 4       // 2 / 4 / 8 / 16 measured alike (3.723 -> 3.712 ms per step: the seam between two replays is ~10 us)
-#endif
+constexpr int GRAPH_STEPS_DEFAULT = 4;   // 2 / 4 / 8 / 16 measured alike (3.723 -> 3.712 ms per step: the seam between two replays is ~10 us)
 static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_sample_params* sp, const int64_t* cond_dev,
                              int64_t B, int32_t steps, const float* q_dev, int64_t* tokens_out_dev,
                              float* logits_trace_dev, void* stream) {
@@ -1190,10 +1188,10 @@ static int gpt_generate_once(wmar_gpt* g, const wmar_wm_ctx* wm, const wmar_samp
     };
 
     // Steps per captured graph: a run that stays in ONE attention phase (the default schedule) replays groups of
-    // WMAR_GRAPH_STEPS_DEFAULT steps, so that the ~10 us seam between two graph launches is paid once per group.
+    // GRAPH_STEPS_DEFAULT steps, so that the ~10 us seam between two graph launches is paid once per group.
     bool one_phase = true;
     for (int n = 1; n < steps; ++n) one_phase = one_phase && phase_of(n) == phase_of(0);
-    const int gs = (one_phase && steps % WMAR_GRAPH_STEPS_DEFAULT == 0) ? WMAR_GRAPH_STEPS_DEFAULT : 1;
+    const int gs = (one_phase && steps % GRAPH_STEPS_DEFAULT == 0) ? GRAPH_STEPS_DEFAULT : 1;
     // The captured step only depends on pointers and scalars: the instantiated graphs are reused when a call repeats them (bench /
     // harness loops) and its steps pass through attention phases that have one.
     GraphKey key;

@@ -551,13 +551,8 @@ struct RarPlan {
     // and q / k / v instead of 20 lines of the packed layout (k_attn_decode80 takes either)
     bool qkv_rm() const { return bx && g->hd == 80; }
     int S_qkv() const { return bx ? g->bx_qkv.S : 1; }
-    int attn_waves() const {
-        int nwa = 1;      // measured at 128 rows, head_dim 80, 256 positions: 4.58 / 4.75 / 4.83 ms per step with 1 / 2 / 4 waves per (sequence, head)
-#ifdef WMAR_DEV_KNOBS
-        { const char* e = getenv("WMAR_RAR_ATT_NW"); if (e) nwa = atoi(e); }
-#endif
-        return nwa;
-    }
+    // measured at 128 rows, head_dim 80, 256 positions: 4.58 / 4.75 / 4.83 ms per step with 1 / 2 / 4 waves per (sequence, head)
+    int attn_waves() const { return 1; }
     // the head_dim the attention launch is instantiated for (wmar_rar_create admits 32, 48, 64, 80, 88, 128)
     int attn_hd() const {
         switch (g->hd) { case 32: case 48: case 64: case 80: case 88: return g->hd; default: return 128; }
@@ -586,20 +581,15 @@ struct RarPlan {
         t.kcache = g->kcache + l * lstride; t.vcache = g->vcache + l * lstride; t.y = g->y; t.yq = bx ? g->yq : nullptr; t.pos_dev = g->ctr;
         t.D = D; t.H = g->H; t.Tmax = g->T; t.MT = MT; t.scale = 1.0f / sqrtf((float)g->hd);
         const dim3 grid((unsigned)(M * g->H));
-        const int nwa = attn_waves();
-#define WMAR_RAR_ATT(HDV)                                                                                   \
-        if (nwa == 1) hipLaunchKernelGGL((k_attn_decode<HDV, 1, 1, false>), grid, dim3(64), 0, st, t);                \
-        else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode<HDV, 4, 1, false>), grid, dim3(256), 0, st, t);          \
-        else hipLaunchKernelGGL((k_attn_decode<HDV, 2, 1, false>), grid, dim3(128), 0, st, t);
+#define WMAR_RAR_ATT(HDV) hipLaunchKernelGGL((k_attn_decode<HDV, 1, 1, false>), grid, dim3(64), 0, st, t);
         switch (attn_hd()) {
             case 32: WMAR_RAR_ATT(32) break;
             case 48: WMAR_RAR_ATT(48) break;
             case 64: WMAR_RAR_ATT(64) break;
             case 80:
                 // all 64 lanes busy (k_attn_decode80) instead of k_attn_decode's 20 of 32
-                if (nwa == 1) hipLaunchKernelGGL((k_attn_decode80<1>), grid, dim3(64), 0, st, t);
-                else if (nwa == 4) hipLaunchKernelGGL((k_attn_decode80<4>), grid, dim3(256), 0, st, t);
-                else hipLaunchKernelGGL((k_attn_decode80<2>), grid, dim3(128), 0, st, t);
+                if (qkv_rm()) hipLaunchKernelGGL((k_attn_decode80<true>), grid, dim3(64), 0, st, t);
+                else hipLaunchKernelGGL((k_attn_decode80<false>), grid, dim3(64), 0, st, t);
                 break;
             case 88: WMAR_RAR_ATT(88) break;
             default: WMAR_RAR_ATT(128) break;
@@ -1231,6 +1221,8 @@ int wmar_rar_probe_plan(wmar_rar* g, int64_t M, int64_t Bhalf, int32_t shared_u,
     ks += ";mod_in=k_modulate;qkv=";
     if (p.bx) snprintf(t, sizeof t, "k_bx<2,%d,4>%s", g->bx_qkv.PER, p.qkv_rm() ? " rowmajor" : ""); else snprintf(t, sizeof t, "k_gemm<%d,EPI_PACKED>", split_tiles);
     ks += t; ks += ";attn=";
+    // (the number behind k_attn_decode80 and the middle one of k_attn_decode<HD,1,1> is the wave count, always 1 here; the names keep the
+    // form the tests and DESIGN.md know, though k_attn_decode80's one template parameter is now RM)
     if (p.attn_hd() == 80) snprintf(t, sizeof t, "k_attn_decode80<%d>%s", nwa, p.qkv_rm() ? " rowmajor" : ""); else snprintf(t, sizeof t, "k_attn_decode<%d,%d,1>", p.attn_hd(), nwa);
     ks += t; ks += ";proj=";
     if (p.bx) snprintf(t, sizeof t, "k_bx<1,%d,4>", g->bx_proj.PER); else snprintf(t, sizeof t, "k_gemm<%d,EPI_PACKED>", split_tiles);
