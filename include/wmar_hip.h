@@ -227,6 +227,11 @@ int wmar_gpt_generate_hooked(wmar_gpt* g, const wmar_sample_params* sp, const in
  * since the last check are invalid, the engine continues on the two-launch path.  WMAR_INJECT_SYNC_FAIL=1 at creation (tests)
  * raises the flag in front of the first fused call. */
 int wmar_gpt_check(wmar_gpt* g, void* stream);
+/* Captured graphs: how many graph slots the engine has captured AND instantiated since its creation, for the fused loop
+ * (wmar_gpt_generate) and the hooked one (wmar_gpt_generate_hooked).  A call that reuses the graphs of an earlier call leaves both
+ * counts as they were; a call that captures adds one per slot it fills.  Read-only, host arithmetic; either pointer may be null.
+ * wmar_rar_graph_counts and wmar_cham_graph_counts are the same for those engines. */
+int wmar_gpt_graph_counts(const wmar_gpt* g, int64_t* fused, int64_t* hooked);
 int wmar_gpt_set_timing(wmar_gpt* g, int32_t enabled);
 /* Decode attention runs 1 / 2 / 4 waves per (sequence, head) while the cache holds <= one_wave_upto / <= two_waves_upto /
  * more rows (one captured step graph per phase).  Defaults were measured at batch 64 on MI355X; a tuning entry point only --
@@ -367,6 +372,7 @@ int wmar_rar_generate_gumbel_ctx(wmar_rar* g, const int64_t* class_ids_dev, int6
  * launch is still in use, and how many calls were re-run. */
 int wmar_rar_launch_status(const wmar_rar* g, int32_t* fused, int32_t* fallbacks);
 int wmar_rar_check(wmar_rar* g, void* stream);
+int wmar_rar_graph_counts(const wmar_rar* g, int64_t* fused, int64_t* hooked);      /* see wmar_gpt_graph_counts */
 
 /* Test-only stage access to a live engine (no engine path calls these; tests/test_gpu_rar_kernels.py holds the launches of a RAR
  * position to a float64 reference one at a time).  A position IS the sequence of stages below, one launch each (RESID_* on the
@@ -506,6 +512,7 @@ int wmar_cham_create(const wmar_cham_config* cfg, const char* const* names, cons
                      int32_t n_tensors, void* stream, wmar_cham** out);
 void wmar_cham_destroy(wmar_cham* g);
 int64_t wmar_cham_device_bytes(const wmar_cham* g);
+int wmar_cham_graph_counts(const wmar_cham* g, int64_t* fused, int64_t* hooked);    /* see wmar_gpt_graph_counts */
 
 /* One token per sequence: row m consumes tok_dev[m] at position pos_dev[m] (its KV cache must hold
  * positions 0..pos-1) -> logits_dev float [M, vocab] (nullable: cache update only).  This is

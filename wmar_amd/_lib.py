@@ -36,6 +36,7 @@ SYMBOLS = [
     "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
     "wmar_wam_create", "wmar_wam_destroy", "wmar_wam_device_bytes", "wmar_wam_embed", "wmar_wam_add_sync",
     "wmar_wam_probe_jnd", "wmar_wam_probe_latent_msg", "wmar_wam_probe_tail",
+    "wmar_gpt_graph_counts", "wmar_rar_graph_counts", "wmar_cham_graph_counts",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
 
@@ -196,6 +197,7 @@ def load():
         fn = getattr(L, "wmar_%s_probe_copy" % eng)
         fn.restype = i64
         fn.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp]
+        getattr(L, "wmar_%s_graph_counts" % eng).argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.wmar_gpt_probe_plan.argtypes = [vp, i64, i32, C.c_char_p, i64]
     L.wmar_rar_create.argtypes = [C.POINTER(RarConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
     L.wmar_rar_destroy.argtypes = [vp]

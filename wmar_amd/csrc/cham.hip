@@ -329,6 +329,12 @@ int wmar_cham_create(const wmar_cham_config* cfg, const char* const* names, cons
 
 void wmar_cham_destroy(wmar_cham* g) { delete g; }
 int64_t wmar_cham_device_bytes(const wmar_cham* g) { return g ? g->mem.bytes : 0; }
+int wmar_cham_graph_counts(const wmar_cham* g, int64_t* fused, int64_t* hooked) {
+    WMAR_REQUIRE(g, "cham_graph_counts: null argument");
+    if (fused) *fused = g->gr.captures;
+    if (hooked) *hooked = g->grh.captures;
+    return WMAR_OK;
+}
 
 int wmar_cham_forward_tokens(wmar_cham* g, const int64_t* tok_dev, const int32_t* pos_dev, int64_t M, float* logits_dev,
                              void* stream) {

@@ -127,6 +127,7 @@ struct GraphSlots {
     hipGraph_t graph[N] = {};
     hipGraphExec_t exec[N] = {};
     bool pending = false;
+    int64_t captures = 0;        // successful capture() calls since creation: tells a reuse from a recapture (wmar_*_graph_counts)
     bool has(int slot) const { return exec[slot] != nullptr; }
     int init() {
         WMAR_HIP_CHECK(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
@@ -157,6 +158,7 @@ struct GraphSlots {
             set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); rc = WMAR_EHIP;
         }
         if (rc != WMAR_OK) drop();
+        else captures += 1;
         return rc;
     }
     int replay(int slot, hipStream_t st) {

@@ -857,6 +857,13 @@ int wmar_gpt_check(wmar_gpt* g, void* stream) {
     return WMAR_OK;
 }
 
+int wmar_gpt_graph_counts(const wmar_gpt* g, int64_t* fused, int64_t* hooked) {
+    WMAR_REQUIRE(g, "gpt_graph_counts: null argument");
+    if (fused) *fused = g->gr.captures;
+    if (hooked) *hooked = g->grh.captures;
+    return WMAR_OK;
+}
+
 void wmar_gpt_destroy(wmar_gpt* g) { delete g; }
 int64_t wmar_gpt_device_bytes(const wmar_gpt* g) { return g ? g->mem.bytes : 0; }
 

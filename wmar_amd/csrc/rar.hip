@@ -175,7 +175,7 @@ static __global__ __launch_bounds__(256) void k_modulate(ModArgs a) {
 // x' = x + gate * (bias + sum_s slab[s])  (k_resid_stats), then  h = LayerNorm(x'; eps 1e-6) * (1 + scale) + shift  (k_modulate) of the
 // SAME rows: the modulation needs the statistics of whole rows, i.e. of all n_chunks workgroups of a row tile.  They are tiny (32 rows
 // x 16 bytes per workgroup), so instead of a second launch (~5 us in the captured step, twice per block) every workgroup publishes
-// its partial sums with agent-scope 8-byte atomic stores into a buffer of its own launch site that a memset node poisoned (all ones:
+// its partial sums with agent-scope 8-byte atomic stores into a buffer of its own launch site that k_rar_poison set to poison (all ones:
 // a NaN no sum can produce) at the start of the position -- the data is the flag -- and polls the other chunks' words of its row tile
 // with agent-scope loads until none is poison (at most 64 x 4 workgroups of 256 threads: all resident), then modulates its OWN chunk,
 // still in registers.  Summation order is the chunk order (fixed): bit-identical to the two-launch path.
@@ -441,6 +441,12 @@ struct wmar_rar {
 
 namespace {
 
+// p[0..n) = all ones: "not published yet" for the partial sums k_resid_mod polls (RarPlan::poison)
+static __global__ void k_rar_poison(unsigned long long* p, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = ~0ull;
+}
+
 struct RarPlan {
     wmar_rar* g;
     int M, Bhalf;           // rows this call (2B with guidance), B
@@ -533,7 +539,7 @@ struct RarPlan {
         return launch_resid_mod(a, nrm * MT, kpw, g->rm_fused, st);
     }
     // words of one k_resid_mod launch site at THIS plan's row count: [chunks][32 MT][2]; the sites are packed at this size, so the
-    // poison memset of a position covers exactly what the launches poll
+    // poison launch of a position covers exactly what the launches poll
     int rm_kpw() const { return KBD <= 256 ? 1 : 4; }
     int rm_chunks() const { return (KBD + 4 * rm_kpw() - 1) / (4 * rm_kpw()); }
     size_t site_words() const { return (size_t)rm_chunks() * MT * 32 * 2; }
@@ -690,11 +696,11 @@ struct RarPlan {
         return WMAR_OK;
     }
     // poison ("not published yet") the partial sums of k_resid_mod's launch sites [site0, site0 + n)
+    // A kernel node, not a memset node: the hooked loop keeps its graphs and replays them in later calls.
     int poison(int site0, int n) {
-        if (hipMemsetAsync(g->part + (size_t)site0 * site_words(), 0xff, (size_t)n * site_words() * 8, st) != hipSuccess) {
-            set_error("rar position: poisoning the partial sums failed"); return WMAR_EHIP;
-        }
-        return WMAR_OK;
+        const size_t words = (size_t)n * site_words();
+        hipLaunchKernelGGL(k_rar_poison, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, g->part + (size_t)site0 * site_words(), words);
+        return launch_status("k_rar_poison");
     }
     int position(bool with_head, float* logits) {
         int rc;
@@ -898,6 +904,12 @@ int wmar_rar_launch_status(const wmar_rar* g, int32_t* fused, int32_t* fallbacks
     WMAR_REQUIRE(g, "rar_launch_status: null argument");
     if (fused) *fused = g->rm_fused ? 1 : 0;
     if (fallbacks) *fallbacks = g->fallbacks;
+    return WMAR_OK;
+}
+int wmar_rar_graph_counts(const wmar_rar* g, int64_t* fused, int64_t* hooked) {
+    WMAR_REQUIRE(g, "rar_graph_counts: null argument");
+    if (fused) *fused = g->gr.captures;
+    if (hooked) *hooked = g->grh.captures;
     return WMAR_OK;
 }
 int64_t wmar_rar_device_bytes(const wmar_rar* g) { return g ? g->mem.bytes : 0; }

@@ -52,6 +52,16 @@ class _Engine:
         return int(getattr(self._L, self._prefix + "_device_bytes")(self._h))
 
 
+class _GraphCounts:
+    """The decode engines: how many graph slots the fused and the hooked loop have captured since the engine was created."""
+
+    def graph_counts(self) -> Dict[str, int]:
+        """{"fused": n, "hooked": n}; a call that reuses the graphs of an earlier call leaves both unchanged."""
+        a, b = C.c_int64(), C.c_int64()
+        _lib.check(getattr(self._L, self._prefix + "_graph_counts")(self._h, C.byref(a), C.byref(b)))
+        return {"fused": int(a.value), "hooked": int(b.value)}
+
+
 class _LogitsHook:
     """The host side of a hooked generation (include/wmar_hip.h, "hooked generation"): owns the two buffers the engine and the
     processor share and wraps the processor as the library's C callback.
@@ -129,7 +139,7 @@ class _TokenizerEngine(_Engine):
         return (codes, pre) if return_prequant else codes
 
 
-class GPTEngine(_Engine):
+class GPTEngine(_Engine, _GraphCounts):
     """minGPT with a static KV cache; replaces GPT.forward_with_past + sample_with_past
     (deps/taming/modules/transformer/mingpt.py:183-214, 326-368)."""
 
@@ -254,7 +264,7 @@ class VQGANEngine(_TokenizerEngine):
         self._create(c, state, lambda k: not k.startswith("loss."), device, max_batch)
 
 
-class RAREngine(_Engine):
+class RAREngine(_Engine, _GraphCounts):
     """RAR generator with KV cache, adaLN, qk-norm and classifier-free guidance; replaces
     RAR.forward_fn / RAR.generate (deps/rar/modeling/rar.py:319-459)."""
 
@@ -376,7 +386,7 @@ class MaskgitVQEngine(_TokenizerEngine):
         self._create(c, state, lambda k: k.startswith(("encoder.", "decoder.", "quantize.")), device, max_batch)
 
 
-class ChameleonEngine(_Engine):
+class ChameleonEngine(_Engine, _GraphCounts):
     """Chameleon / Anole transformer decode with KV cache, three guidance streams and the fused sampler; replaces
     ChameleonModelAdapter + Transformer.forward_with_attn_bias + the ImageDecoder token loop
     (deps/chameleon/inference/model_adapter.py:36-119, transformer.py:288-337, chameleon.py:299-389)."""
