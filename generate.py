@@ -62,8 +62,11 @@ def get_parser():
                              "instead of the networks --syncpath names")
     parser.add_argument("--sync_embedder", type=str, default="torch", choices=["torch", "native"],
                         help="with --sync true and a WAM --syncpath (wam_mit*.pth): 'native' runs add_sync's embedder on the device "
-                             "(wmar_wam_add_sync) from the checkpoint's embedder.* tensors, without the WAM checkout; the extractor "
-                             "of remove_sync still comes from the checkout or from --sync_factory")
+                             "(wmar_wam_add_sync) from the checkpoint's embedder.* tensors, without the WAM checkout")
+    parser.add_argument("--sync_extractor", type=str, default="torch", choices=["torch", "native"],
+                        help="with --sync true and a WAM --syncpath (wam_mit*.pth): 'native' runs remove_sync's extractor on the device "
+                             "(wmar_wamx_detect) from the checkpoint's detector.* tensors; with --sync_embedder native as well, "
+                             "--sync true needs no WAM checkout")
     parser.add_argument("--seed", type=int, nargs="?", help="seed", default=42)
     parser.add_argument("--synthetic", type=str2bool, default=False, help="random-init weights instead of checkpoints")
     parser.add_argument("--synthetic_config", type=str, default="full", choices=["full", "harness"],
@@ -102,6 +105,12 @@ def check_wm_args(args):
         if "wam_mit" not in str(getattr(args, "syncpath", None) or ""):
             raise ValueError(f"--sync_embedder native needs a WAM checkpoint (--syncpath .../wam_mit*.pth), got {getattr(args, 'syncpath', None)!r}: "
                              "SyncSeal has no native embedder")
+    if getattr(args, "sync_extractor", "torch") == "native":
+        if not getattr(args, "sync", False):
+            raise ValueError("--sync_extractor native is only read with --sync true")
+        if "wam_mit" not in str(getattr(args, "syncpath", None) or ""):
+            raise ValueError(f"--sync_extractor native needs a WAM checkpoint (--syncpath .../wam_mit*.pth), got {getattr(args, 'syncpath', None)!r}: "
+                             "SyncSeal has no native extractor")
 
 
 def main():

@@ -968,6 +968,67 @@ int wmar_wam_probe_latent_msg(const float* latents_dev, int64_t n_images, int32_
 int wmar_wam_probe_tail(const float* y_dev, const float* imgs_dev, int32_t in_mode, int64_t B, int32_t R, const uint8_t* masks_dev,
                         int32_t K, float scaling_w, float scaling_i, int32_t attenuation, float* out_dev, float* preds_dev, void* stream);
 
+/* ------------------------------------------------------------------------ synchronisation layer (WAM extractor)
+ * deps/watermark_anything: models/extractor.py SegmentationExtractor = modules/vit.py ImageEncoderViT (sam_base of configs/
+ * extractor.yaml: patch embedding + pos_embed, blocks of windowed / global attention with decomposed relative positions, mlp_ratio 4,
+ * the neck) + modules/pixel_decoder.py PixelDecoder (bilinear Upsample stages, last_layer) -- models/wam.py Wam.detect for images of
+ * the network's own size (no resize).  Tensors by key name relative to `detector.` (image_encoder.*, pixel_decoder.*).
+ * global_attn_indexes: the blocks that attend over the whole grid; the others inside window_size x window_size windows.
+ * wmar_wamx_create refuses, with a text: a grid (img_size / patch_size) that is no multiple of window_size (the reference pads such
+ * grids with zero tokens that take part as keys; not built); a grid that is no multiple of the 8 x 8 conv tile, a patch size that is
+ * no multiple of 4; embed_dim % num_heads != 0, a head width that is no multiple of 4 or above 64, windows above 32 x 32 or K and V of
+ * a window beyond the LDS; upscaling factors other than 2, 4, 8, a product other than patch_size, out_chans not divisible by it; nbits
+ * outside 1..64; a missing tensor (WMAR_EMISSING, the text names it).  The ABI carries no tensor shapes: that each rel_pos table has
+ * 2 S - 1 rows (S the block's window or grid size; get_rel_pos then never interpolates) is checked by the caller (wam_extractor.py).
+ * Images float [B, 3, R, R] in WAM-normalised space -> preds float [B, nbits + 1, R, R] (NCHW; channel 0 the mask logit, then the
+ * bit logits; no sigmoid).  The batch is walked in groups of max_batch; no value crosses a group, so the chunking changes no bit.
+ * R other than img_size is WMAR_EINVAL, nothing is launched and the output is untouched.  No call but the probes waits for its
+ * launches; two runs give the same bits. */
+typedef struct wmar_wamx_config {
+    int32_t img_size, patch_size, embed_dim, depth, num_heads, window_size;
+    int32_t n_global;
+    int32_t global_attn_indexes[16];
+    int32_t out_chans;
+    int32_t n_stages;
+    int32_t upscale_stages[4];
+    int32_t nbits;
+    int32_t max_batch;
+} wmar_wamx_config;
+
+typedef struct wmar_wamx wmar_wamx;
+
+int wmar_wamx_create(const wmar_wamx_config* cfg, const char* const* names, const void* const* tensors_dev, int32_t n_tensors, void* stream,
+                     wmar_wamx** out);
+void wmar_wamx_destroy(wmar_wamx* w);
+int64_t wmar_wamx_device_bytes(const wmar_wamx* w);
+int wmar_wamx_detect(wmar_wamx* w, const float* imgs_norm_dev, int64_t B, int32_t R, float* preds_dev, void* stream);
+
+/* Probes (tests, debugging): one kernel of the extractor at a time, through the launches the engine uses; each waits for the stream.
+ * Activations are NHWC with channels padded to a multiple of 8 (padding zero), written pad8(C) below.
+ * wmar_wamx_probe_layernorm: x_dev [n, pad8(C)] -> mr_dev float [n, 2] = (mean, 1 / sqrt(biased variance + eps)) per token over its C
+ * channels (the normalisation itself is applied by the consuming conv while it stages its patch).
+ * wmar_wamx_probe_patch_embed: imgs_dev [B, 3, R, R], w_dev [D, 3, patch, patch], bias_dev [D], pos_dev [R / patch, R / patch, D]
+ * -> out_dev [B, R / patch, R / patch, D] = conv + bias + pos.
+ * wmar_wamx_probe_attn: qkv_dev [B, grid, grid, 3 * num_heads * head_dim] (channel which * D + head * head_dim + c), windows of
+ * S x S tokens (S = grid: global), rel_h_dev / rel_w_dev [2 S - 1, head_dim] -> out_dev [B, grid, grid, num_heads * head_dim].
+ * wmar_wamx_probe_upstage: x_dev [B, Hs, Hs, pad8(Cin)], optionally LayerNorm(eps 1e-6; gamma / beta [Cin]) (+ GELU if ln_gelu) of
+ * it, bilinear upsampling by f, ReflectionPad2d(1), 3 x 3 conv w_dev [Cout, Cin, 3, 3] without bias -> out_dev
+ * [B, Hs f, Hs f, pad8(Cout)] (the stage's own LayerNorm + GELU are applied by the NEXT conv).
+ * wmar_wamx_probe_last: x_dev [B, H, H, pad8(Cin)], the same optional LayerNorm (+ GELU), 1 x 1 conv w_dev [Cout, Cin, 1, 1] +
+ * bias_dev -> out_dev [B, Cout, H, H] (NCHW).
+ * wmar_wamx_probe_block: block `block` of an engine (norm1 .. MLP residual) on x_dev [B, grid, grid, embed_dim], B <= max_batch ->
+ * out_dev of the same shape. */
+int wmar_wamx_probe_layernorm(const float* x_dev, int64_t n, int32_t C, float eps, float* mr_dev, void* stream);
+int wmar_wamx_probe_patch_embed(const float* imgs_dev, int64_t B, int32_t R, int32_t patch, const float* w_dev, const float* bias_dev,
+                                const float* pos_dev, int32_t D, float* out_dev, void* stream);
+int wmar_wamx_probe_attn(const float* qkv_dev, int64_t B, int32_t grid, int32_t S, int32_t num_heads, int32_t head_dim, const float* rel_h_dev,
+                         const float* rel_w_dev, float* out_dev, void* stream);
+int wmar_wamx_probe_upstage(const float* x_dev, int64_t B, int32_t Hs, int32_t Cin, int32_t f, const float* ln_gamma_dev,
+                            const float* ln_beta_dev, int32_t ln_gelu, const float* w_dev, int32_t Cout, float* out_dev, void* stream);
+int wmar_wamx_probe_last(const float* x_dev, int64_t B, int32_t H, int32_t Cin, const float* ln_gamma_dev, const float* ln_beta_dev,
+                         int32_t ln_gelu, const float* w_dev, const float* bias_dev, int32_t Cout, float* out_dev, void* stream);
+int wmar_wamx_probe_block(wmar_wamx* w, int32_t block, const float* x_dev, int64_t B, float* out_dev, void* stream);
+
 /* ------------------------------------------------------------------------ exchange step (RCCL over xGMI)
  * The sharded job (one process per GPU; rank r == the reference's `--chunk_id r --num_chunks world`, generate.py:204, :304) has no
  * data-path collective.  Its two exchanges -- the finished key table from rank 0 once, the per-image records once per step

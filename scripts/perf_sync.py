@@ -1,7 +1,9 @@
 """Dev tool: the synchronisation layer's device half (csrc/sync.hip).  Times, as the median of 20 event-bracketed calls after 3
 warm-ups: wmar_sync_fit for B = 64 at 256^2 and B = 16 at 512^2 (label maps of tests/sync_cases.py, tiled), and a whole
 WamSync.remove_sync of 64 images with the colour-coded stand-in WAM of tests/sync_standins.py (no network: normalise, positions, fit,
-the [B, 4] copy, revert).  Then the host path (tests/sync_reference.py = the reference's scipy arithmetic) per image, if scipy is here.
+the [B, 4] copy, revert), and the WAM extractor at the released shape with synthetic weights: WamExtractor.detect (wmar_wamx_detect)
+of 64 images at 256^2 against the float32 torch restatement of the same network (tests/wam_extractor_reference.py) on the same GPU,
+and a remove_sync of the 64 images through it.  Then the host path (tests/sync_reference.py = the reference's scipy arithmetic) per image, if scipy is here.
 usage: perf_sync.py [--quick]   (--quick: 3 timed calls, no host path -- for a rocprofv3 --kernel-trace --stats run)"""
 import os, sys, time
 import numpy as np
@@ -41,6 +43,26 @@ for S, B in ((256, 64), (512, 16)):
 imgs = torch.from_numpy(np.concatenate([SC.e2e_images()] * 16)).cuda()
 ms = median_ms(lambda: ws.remove_sync(imgs))
 print(f"remove_sync B=64 S=256 (stand-in WAM): {ms:.3f} ms per call (sanity bound: 125 ms, the batch's VQGAN decode + re-encode)", flush=True)
+# ---- the extractor: native against the float32 torch restatement, released shape, 34 GMAC per image
+from tests import wam_extractor_cases as XC
+from tests import wam_extractor_reference as XR
+from wmar_amd.utils import synth
+from wmar_amd.watermarking.wam_extractor import WamExtractor
+xcfg = synth.WAMX_RELEASED
+xstate = synth.synth_wamx_state(xcfg, XC.RELEASED_SEED)
+ext = WamExtractor(xcfg, xstate, "cuda", max_batch=64)
+xs = XR.to_dtype(xstate, torch.float32, "cuda")
+xin = torch.from_numpy(np.concatenate([XC.images_norm(XC.RELEASED_SEED, 4, 256)] * 16)).cuda()
+with torch.no_grad():
+    d = float((ext.detect(xin[:4])["preds"] - XR.forward(xs, xcfg, xin[:4], library=True)).abs().max())
+    ms_n = median_ms(lambda: ext.detect(xin))
+    ms_t = median_ms(lambda: XR.forward(xs, xcfg, xin, library=True))
+gmac = 34.0 * 64
+print(f"extractor detect B=64 S=256: native {ms_n:.2f} ms ({gmac * 2 / ms_n:.1f} TFLOP/s of 34 GMAC per image), float32 torch restatement "
+      f"{ms_t:.2f} ms ({gmac * 2 / ms_t:.1f} TFLOP/s); max |native - torch| on 4 images {d:.3g}; engine {ext.device_bytes / 2 ** 20:.0f} MiB", flush=True)
+wsx = WamSync(None, "cuda", wam=object(), extractor=ext)
+ms = median_ms(lambda: wsx.remove_sync(imgs))
+print(f"remove_sync B=64 S=256 (native extractor, synthetic weights): {ms:.3f} ms per call", flush=True)
 if not QUICK:
     try:
         from tests import sync_reference as SR

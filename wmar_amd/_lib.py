@@ -36,6 +36,8 @@ SYMBOLS = [
     "wmar_sync_positions", "wmar_sync_workspace_bytes", "wmar_sync_fit", "wmar_sync_rotate_labels",
     "wmar_wam_create", "wmar_wam_destroy", "wmar_wam_device_bytes", "wmar_wam_embed", "wmar_wam_add_sync",
     "wmar_wam_probe_jnd", "wmar_wam_probe_latent_msg", "wmar_wam_probe_tail",
+    "wmar_wamx_create", "wmar_wamx_destroy", "wmar_wamx_device_bytes", "wmar_wamx_detect", "wmar_wamx_probe_layernorm",
+    "wmar_wamx_probe_patch_embed", "wmar_wamx_probe_attn", "wmar_wamx_probe_upstage", "wmar_wamx_probe_last", "wmar_wamx_probe_block",
     "wmar_gpt_graph_counts", "wmar_rar_graph_counts", "wmar_cham_graph_counts",
     "wmar_comm_unique_id", "wmar_comm_init", "wmar_comm_bcast", "wmar_comm_allgather", "wmar_comm_rank", "wmar_comm_world", "wmar_comm_destroy",
 ]
@@ -95,6 +97,13 @@ class WamConfig(C.Structure):
                 ("nbits", C.c_int32), ("n_levels", C.c_int32), ("ch_mult", C.c_int32 * 8), ("n_attn_res", C.c_int32),
                 ("attn_resolutions", C.c_int32 * 8), ("max_batch", C.c_int32), ("scaling_w", C.c_float), ("scaling_i", C.c_float),
                 ("attenuation", C.c_int32)]
+
+
+class WamxConfig(C.Structure):
+    _fields_ = [("img_size", C.c_int32), ("patch_size", C.c_int32), ("embed_dim", C.c_int32), ("depth", C.c_int32),
+                ("num_heads", C.c_int32), ("window_size", C.c_int32), ("n_global", C.c_int32), ("global_attn_indexes", C.c_int32 * 16),
+                ("out_chans", C.c_int32), ("n_stages", C.c_int32), ("upscale_stages", C.c_int32 * 4), ("nbits", C.c_int32),
+                ("max_batch", C.c_int32)]
 
 
 class LpipsConfig(C.Structure):
@@ -259,6 +268,18 @@ def load():
         L.wmar_wam_probe_jnd.argtypes = [vp, i64, i32, vp, vp]
         L.wmar_wam_probe_latent_msg.argtypes = [vp, i64, i32, i32, i32, vp, vp, i64, i64, i32, i32, vp, vp]
         L.wmar_wam_probe_tail.argtypes = [vp, vp, i32, i64, i32, vp, i32, f32, f32, i32, vp, vp, vp]
+        L.wmar_wamx_create.argtypes = [C.POINTER(WamxConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
+        L.wmar_wamx_destroy.argtypes = [vp]
+        L.wmar_wamx_destroy.restype = None
+        L.wmar_wamx_device_bytes.restype = i64
+        L.wmar_wamx_device_bytes.argtypes = [vp]
+        L.wmar_wamx_detect.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.wmar_wamx_probe_layernorm.argtypes = [vp, i64, i32, f32, vp, vp]
+        L.wmar_wamx_probe_patch_embed.argtypes = [vp, i64, i32, i32, vp, vp, vp, i32, vp, vp]
+        L.wmar_wamx_probe_attn.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.wmar_wamx_probe_upstage.argtypes = [vp, i64, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+        L.wmar_wamx_probe_last.argtypes = [vp, i64, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp]
+        L.wmar_wamx_probe_block.argtypes = [vp, i32, vp, i64, vp, vp]
         L.wmar_lpips_create.argtypes = [C.POINTER(LpipsConfig), C.POINTER(C.c_char_p), C.POINTER(vp), i32, vp, C.POINTER(vp)]
         L.wmar_lpips_destroy.argtypes = [vp]
         L.wmar_lpips_destroy.restype = None

@@ -74,6 +74,9 @@ def build_sync_manager(args, device):
     factory = getattr(args, "sync_factory", None)
     # --sync_embedder native: add_sync's embedder from the checkpoint's embedder.* tensors on the device (wam_embedder.py)
     native = {"embedder": "native"} if getattr(args, "sync_embedder", "torch") == "native" else {}
+    # --sync_extractor native: remove_sync's extractor from the checkpoint's detector.* tensors on the device (wam_extractor.py)
+    if getattr(args, "sync_extractor", "torch") == "native":
+        native["extractor"] = "native"
     if not factory:
         if native:
             return SyncManager(args.syncpath, device, sync=WamSync(args.syncpath, device, **native))

@@ -1682,3 +1682,6 @@ int wmar_mvq_encode(wmar_mvq* v, const float* images_dev, int64_t B, int64_t* co
 
 // ============================================================================ the WAM embedder (synchronisation layer)
 #include "wam.h"
+
+// ============================================================================ the WAM extractor (synchronisation layer)
+#include "wam_extractor.h"

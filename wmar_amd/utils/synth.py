@@ -331,6 +331,105 @@ def synth_wam_state(cfg: WamConfig, seed: int = 0, device="cpu") -> Dict[str, to
     return out
 
 
+# ----------------------------------------------------------------------------- WAM extractor (synchronisation layer)
+@dataclasses.dataclass
+class WamExtractorConfig:
+    """The extractor of the released WAM checkpoint (deps/watermark_anything/configs/extractor.yaml sam_base, params.json nbits 32,
+    img_size 256): a SAM-style ViT (windowed and global blocks with decomposed relative positions), a neck and a pixel decoder of
+    bilinear upscaling stages.  mlp_ratio 4, qkv_bias, use_rel_pos and the bilinear upscale type are fixed."""
+    img_size: int = 256
+    patch_size: int = 16
+    embed_dim: int = 768
+    depth: int = 12
+    num_heads: int = 12
+    window_size: int = 8
+    global_attn_indexes: Tuple[int, ...] = (2, 5, 8, 11)
+    out_chans: int = 768
+    upscale_stages: Tuple[int, ...] = (4, 2, 2)
+    nbits: int = 32
+
+    @property
+    def grid(self) -> int:
+        return self.img_size // self.patch_size
+
+    @property
+    def head_dim(self) -> int:
+        return self.embed_dim // self.num_heads
+
+
+WAMX_RELEASED = WamExtractorConfig()
+# an 8 x 8 grid: four 16-token windows, global blocks of 64 tokens with 15-row tables; pixel decoder 96 -> 24 -> 12 -> 6 channels
+WAMX_SMALL = WamExtractorConfig(img_size=128, embed_dim=96, num_heads=3, depth=4, global_attn_indexes=(1, 3), window_size=4, out_chans=96)
+
+
+def wamx_shapes(cfg: WamExtractorConfig) -> Dict[str, Tuple[int, ...]]:
+    """Keys relative to ``detector.`` (models/extractor.py: image_encoder = modules/vit.py ImageEncoderViT, pixel_decoder =
+    modules/pixel_decoder.py PixelDecoder)."""
+    s: Dict[str, Tuple[int, ...]] = {}
+    D, g, hd = cfg.embed_dim, cfg.grid, cfg.head_dim
+    e = "image_encoder."
+    s[e + "pos_embed"] = (1, g, g, D)
+    s[e + "patch_embed.proj.weight"] = (D, 3, cfg.patch_size, cfg.patch_size)
+    s[e + "patch_embed.proj.bias"] = (D,)
+    for i in range(cfg.depth):
+        p = f"{e}blocks.{i}."
+        S = g if i in cfg.global_attn_indexes else cfg.window_size
+        s[p + "norm1.weight"] = (D,); s[p + "norm1.bias"] = (D,)
+        s[p + "attn.rel_pos_h"] = (2 * S - 1, hd); s[p + "attn.rel_pos_w"] = (2 * S - 1, hd)
+        s[p + "attn.qkv.weight"] = (3 * D, D); s[p + "attn.qkv.bias"] = (3 * D,)
+        s[p + "attn.proj.weight"] = (D, D); s[p + "attn.proj.bias"] = (D,)
+        s[p + "norm2.weight"] = (D,); s[p + "norm2.bias"] = (D,)
+        s[p + "mlp.lin1.weight"] = (4 * D, D); s[p + "mlp.lin1.bias"] = (4 * D,)
+        s[p + "mlp.lin2.weight"] = (D, 4 * D); s[p + "mlp.lin2.bias"] = (D,)
+    C = cfg.out_chans
+    s[e + "neck.0.weight"] = (C, D, 1, 1)
+    s[e + "neck.1.weight"] = (C,); s[e + "neck.1.bias"] = (C,)
+    s[e + "neck.2.weight"] = (C, C, 3, 3)
+    s[e + "neck.3.weight"] = (C,); s[e + "neck.3.bias"] = (C,)
+    for j, f in enumerate(cfg.upscale_stages):
+        p = f"pixel_decoder.output_upscaling.{j}.upsample_block."
+        s[p + "2.weight"] = (C // f, C, 3, 3)
+        s[p + "3.weight"] = (C // f,); s[p + "3.bias"] = (C // f,)
+        C //= f
+    s["pixel_decoder.last_layer.weight"] = (cfg.nbits + 1, C, 1, 1)
+    s["pixel_decoder.last_layer.bias"] = (cfg.nbits + 1,)
+    return s
+
+
+def wamx_is_norm(key: str) -> bool:
+    """The LayerNorm tensors of the extractor: norm1 / norm2 of the blocks, and neck.1, neck.3 and upsample_block.3, whose names do
+    not say so."""
+    return any(t in key for t in (".norm1.", ".norm2.", "neck.1.", "neck.3.", "upsample_block.3."))
+
+
+def synth_wamx_state(cfg: WamExtractorConfig, seed: int = 0, device="cpu") -> Dict[str, torch.Tensor]:
+    """Random-init extractor tensors keyed like the WAM checkpoint's ``detector.*`` minus the prefix: rel_pos tables N(0, 0.2) (so
+    that the term matters), pos_embed N(0, 0.02), LayerNorms 1 + 0.1 N / 0.1 N, other biases 0.02 N, other weights uniform
+    +- sqrt(3 / fan_in)."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed + 1299709)
+    out = {}
+    for k, shp in wamx_shapes(cfg).items():
+        leaf = k.rsplit(".", 1)[-1]
+        if leaf in ("rel_pos_h", "rel_pos_w"):
+            t = torch.randn(shp, generator=g) * 0.2
+        elif leaf == "pos_embed":
+            t = torch.randn(shp, generator=g) * 0.02
+        elif wamx_is_norm(k):
+            t = torch.randn(shp, generator=g) * 0.1
+            if leaf == "weight":
+                t = t + 1.0
+        elif leaf == "bias":
+            t = torch.randn(shp, generator=g) * 0.02
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            t = (torch.rand(shp, generator=g) * 2.0 - 1.0) * (3.0 / fan_in) ** 0.5
+        out[k] = t.to(torch.float32).to(device)
+    return out
+
+
 # ----------------------------------------------------------------------------- RAR
 @dataclasses.dataclass
 class RARConfig:

@@ -2,8 +2,10 @@
 ``SyncManager`` with the reference's public surface, for the MI355X build.
 
 The neural half (the WAM embedder / extractor, the SyncSeal TorchScript) is ordinary PyTorch and is NOT part of this package: it is
-bound from the user's own checkout or handed in as an object -- except the WAM embedder, which ``WamSync(..., embedder=...)`` runs on
-the device from the checkpoint's ``embedder.*`` tensors (wam_embedder.py, wmar_amd/csrc/wam.h: ``wmar_wam_add_sync``).  What the reference computes on the host per image -- the message
+bound from the user's own checkout or handed in as an object -- except the WAM networks at their own image size, which
+``WamSync(..., embedder=..., extractor=...)`` runs on the device from the checkpoint's ``embedder.*`` / ``detector.*`` tensors
+(wam_embedder.py, wmar_amd/csrc/wam.h: ``wmar_wam_add_sync``; wam_extractor.py, wmar_amd/csrc/wam_extractor.h:
+``wmar_wamx_detect``).  What the reference computes on the host per image -- the message
 label of every pixel, and ``fit_best_aug``: four label masks rotated by 41 angles with ``scipy.ndimage.rotate``, thresholded, counted
 and searched for the best cut and flip (2.3 s per 256 x 256 image) -- runs here as kernels over the whole batch
 (wmar_amd/csrc/sync.hip: ``wmar_sync_positions``, ``wmar_sync_fit``, ``wmar_sync_rotate_labels``), and ``remove_sync`` copies one
@@ -70,10 +72,12 @@ def _positions_arg(positions, device):
 
 
 class WamSync:
-    def __init__(self, syncpath, device, wam=None, embedder=None):
+    def __init__(self, syncpath, device, wam=None, embedder=None, extractor=None):
         """``embedder``: a ``WamEmbedder`` (wam_embedder.py), or "native" to build one from ``syncpath``.  With one, ``add_sync`` on
         images of its resolution is one device call and the PyTorch network is only loaded at the first ``remove_sync`` (or the
-        first ``add_sync`` of another image size)."""
+        first ``add_sync`` of another image size).  ``extractor``: a ``WamExtractor`` (wam_extractor.py), or "native": the detect of
+        ``remove_sync`` on images of its size is one device call as well; with both, nothing is imported from a checkout unless
+        an image of another size arrives."""
         self.device = device
         self.syncpath = syncpath
         if isinstance(embedder, str):
@@ -81,9 +85,15 @@ class WamSync:
                 raise ValueError(f"embedder {embedder!r}: a WamEmbedder or 'native'")
             from .wam_embedder import WamEmbedder
             embedder = WamEmbedder.from_checkpoint(syncpath, device)
+        if isinstance(extractor, str):
+            if extractor != "native":
+                raise ValueError(f"extractor {extractor!r}: a WamExtractor or 'native'")
+            from .wam_extractor import WamExtractor
+            extractor = WamExtractor.from_checkpoint(syncpath, device)
         self.embedder = embedder
+        self.extractor = extractor
         self._wam = wam
-        if wam is None and embedder is None:
+        if wam is None and embedder is None and extractor is None:
             self._wam = _load_wam(syncpath, device)
         self.epsilon = 1
         self.min_samples = 500
@@ -95,8 +105,8 @@ class WamSync:
 
     @property
     def wam(self):
-        """The PyTorch network (embed / detect): handed in, loaded at construction, or -- with a native embedder -- loaded from the
-        user's checkout when it is first needed."""
+        """The PyTorch network (embed / detect): handed in, loaded at construction, or -- with a native embedder or extractor --
+        loaded from the user's checkout when it is first needed."""
         if self._wam is None:
             self._wam = _load_wam(self.syncpath, self.device)
         return self._wam
@@ -270,7 +280,11 @@ class WamSync:
         orig_device = imgs.device
         imgs = self.normalize(imgs.to(self.device))
         _square(imgs, "image")
-        preds = self.wam.detect(imgs)["preds"]          # [B, 33, h, h]
+        ext = self.extractor
+        if ext is not None and imgs.shape[-1] == ext.cfg.img_size:
+            preds = ext.detect(imgs.to(getattr(ext, "device", self.device)))["preds"].to(imgs.device)      # wmar_wamx_detect
+        else:
+            preds = self.wam.detect(imgs)["preds"]      # [B, 33, h, h]
         aug, wam_info = self.estimate_augmentation_with_wam(imgs, preds)
         aug_host = aug.cpu().tolist()
         reverted = self.unnormalize(self.revert_batch(imgs, aug_host)).to(orig_device)
